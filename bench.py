@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — generated frames/sec of the sampling hot path on N MI355X (one process per GPU).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N>1 runs one process per GPU: either the caller launches them (`python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...`, RANK/LOCAL_RANK/WORLD_SIZE in the env) or, when WORLD_SIZE is not set, this script spawns
@@ -60,8 +60,11 @@ DTYPES = ["bf16", "fp16", "fp8"]
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=2)
+    p.add_argument("--steps", type=int, default=None, help="timed steps (default 2; 20 with --train)")
     p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, at most 64 MB "
+                        "in all: a fixed, seeded sample of larger outputs); the inputs depend on the arguments only")
     p.add_argument("--clips", type=int, default=56, help="clips sampled in lock step per GPU")
     p.add_argument("--streams", type=int, default=2, help="concurrent clip groups per GPU (own context + stream each)")
     p.add_argument("--workload", choices=sorted(WORKLOADS), default="cfg2",
@@ -83,6 +86,10 @@ def parse():
     p.add_argument("--no-fp8-extra", action="store_true",
                    help="skip extras.fp8_same_box (one step of the same workload with the MX-fp8 convs, rank 0, after the headline is computed)")
     args = p.parse_args()
+    if args.steps is None:
+        args.steps = 20 if args.train else 2
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
     wl = WORKLOADS[args.workload]
     if args.dtype is None:
         # argparse does not check a DEFAULT against `choices`: validate the environment's value by hand (a typo such as
@@ -118,6 +125,30 @@ def cpu_model():
     except OSError:
         pass
     return "unknown"
+
+
+DUMP_BYTES = 60 << 20     # --dump-outputs: data bytes of all files together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each named array as out_dir/<name>.npy, float64 kept, every other dtype as float32.  DUMP_BYTES is shared out
+    smallest array first; an array larger than its share is replaced by a fixed, seeded sample of its flattened elements (ascending
+    index order): the same arguments select the same elements, so two builds can be compared file for file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    left = DUMP_BYTES
+    for i, name in enumerate(sorted(host, key=lambda n: host[n].nbytes)):
+        a = host[name]
+        share = left // (len(host) - i)
+        if a.nbytes > share:
+            k = max(1, share // a.itemsize)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))]
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(cfg_name, start_step, denoise=True, guidance=0.0, text=False):
@@ -326,7 +357,7 @@ def fp8_same_box(args, cfg, local_rank, build_model, clips, seeds, kw_s, cls_emb
     from sd_video_gen_amd.predict import sample_clips, sample_clips_streams
     from sd_video_gen_amd.sd_utils import SDUtils
     workers = []
-    for i in range(args.streams):                       # on the headline's own streams (see GPU_MAX_HW_QUEUES in main)
+    for i in range(args.streams):                       # on the headline's own streams (see the hardware queues in main)
         c8 = _lib.Context(local_rank)
         torch.manual_seed(0)
         workers.append((build_model(c8), SDUtils(weights="synthetic", seed=0, verbose=False, ctx=c8, fp8=True, dtype="fp16"), streams[i]))
@@ -412,7 +443,7 @@ def train_bench(args, rank, local_rank, world, dist):
             dist.barrier()
         torch.cuda.synchronize()
 
-    steps, warm = max(args.steps, 20) if args.steps == 2 else args.steps, max(args.warmup, 3)
+    steps, warm = args.steps, max(args.warmup, 3)
     for i in range(warm):
         step(i)
     sync()
@@ -430,6 +461,16 @@ def train_bench(args, rank, local_rank, world, dist):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert all(v == v for v in terms.values())
+    if rank == 0 and args.dump_outputs:
+        # the last step's loss terms and the weights its Adam update left (4096 seeded elements of each parameter: the model is GBs)
+        import numpy as np
+        model.pull_weights()
+        pick = np.random.default_rng(0)
+        sample = []
+        for _, prm in sorted(model.named_parameters()):
+            flat = prm.detach().reshape(-1).cpu().numpy()
+            sample.append(flat[np.sort(pick.choice(flat.size, size=min(flat.size, 4096), replace=False))])
+        dump_outputs(args.dump_outputs, dict({"loss_" + k: np.float64(v) for k, v in terms.items()}, params_sample=np.concatenate(sample)))
     med = statistics.median(per)
     step_bytes = 10.0 * n_par * 4          # W read by forward and by dX, dW written, Adam: p, g, m, v read and p, m, v written
     rec = {"metric": "training iterations/sec, latent Transformer (forward + criterion + backward + Adam)", "value": world * steps / dt,
@@ -467,11 +508,9 @@ def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
-    # HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4, assigned at a stream's first use): two stream
-    # groups that land on ONE queue lose their overlap (measured: the same fp16 pair 19.0 frames/s on one pair of streams, 17.8 on another;
-    # with 8 queues both 19.0 — profiles/r05_fp8_inproc_probe.txt).  The headline's two streams are the first two of the process and never
-    # aliased; the later passes of this process (fp8_same_box) would.  Must be set before the HIP runtime initialises.
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+    # HIP multiplexes a process's streams onto a fixed number of hardware queues (assigned at a stream's first use): two stream groups
+    # that land on ONE queue lose their overlap (profiles/r05_stream_queue_aliasing.txt).  The queue count is left to the environment
+    # (the GPU is shared with other processes); the later passes of this process (fp8_same_box) reuse the headline's own streams.
     import torch
     import torch.distributed as dist
     rank = int(os.environ.get("RANK", "0"))
@@ -592,6 +631,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert out.shape[0] == n_global and torch.isfinite(out).all()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"all_latents": out})       # (clips, 4 + pred_frames, D_lat) f32, gathered over the ranks
     frames = n_global * args.pred_frames * args.steps
     fps = frames / dt
 

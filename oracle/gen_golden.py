@@ -5,7 +5,8 @@ the reference's source travels.  Run:  python oracle/gen_golden.py
 G1 transformer_tiny.pt   full state_dict of a tiny reference Transformer + X/outputs (T=6 and T=5)
 G2 transformer_spot.pt   full-size spot checks: seed, sha256(state_dict), X, pred — the weights are
                          regenerated from the seed with torch's own nn modules in the reference's
-                         construction order (transformer.py:33-45)
+                         construction order (transformer.py:33-45); sha256_params leaves out the
+                         positional table, whose sin / cos / exp round by the host's math library
 G3 pe_quirk.pt           PositionalEncoding(256,0.1,64).eval()(zeros(3,6,256))
 G4 tgt_masks.pt          get_tgt_mask(5), (6)
 G5 loop_trace.pt         predict.py:136-196 loop shapes driven through the reference Transformer
@@ -26,6 +27,11 @@ def sd_hash(sd):
         h.update(k.encode())
         h.update(sd[k].detach().cpu().contiguous().numpy().tobytes())
     return h.hexdigest()
+
+
+def params_only(sd):
+    """the state_dict without the positional table: what the seed alone determines, on any host"""
+    return {k: v for k, v in sd.items() if k != "positional_encoder.pos_encoding"}
 
 
 def build_ref(config_name, **kw):
@@ -94,7 +100,7 @@ def main():
         with torch.no_grad():
             pred = predict_ref(m2, X)
         spots[cfg] = {"seed": seed, "kw": kw, "d_lat": dlat, "n_params": n_params,
-                      "sha256": sd_hash(m2.state_dict()), "X": X, "pred": pred}
+                      "sha256": sd_hash(m2.state_dict()), "sha256_params": sd_hash(params_only(m2.state_dict())), "X": X, "pred": pred}
         print(cfg, n_params, spots[cfg]["sha256"][:16], float(pred.abs().mean()))
         del m2
     torch.save(spots, os.path.join(OUT, "transformer_spot.pt"))

@@ -312,6 +312,33 @@ def test_bench_refuses_mismatched_world_size():
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
 
 
+def test_bench_steps_and_dump_outputs(tmp_path, monkeypatch):
+    """--steps is the number of timed steps on every path (--train has its own default, no minimum); --dump-outputs writes float32 /
+    float64 .npy files, under 64 MB in all, an output too large for that as the same seeded sample of its elements every time."""
+    import numpy as np
+    import bench
+    for argv, want in ((["--steps", "2", "--train"], 2), (["--train"], 20), ([], 2), (["--steps", "7", "--warmup", "0"], 7)):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        assert bench.parse().steps == want
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    small = torch.arange(12, dtype=torch.float16).reshape(3, 4)
+    big = torch.arange(9 << 20, dtype=torch.float64)            # 72 MiB: values are their own indices
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big, "loss": np.float64(0.25)})
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["big.npy", "loss.npy", "small.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64e6
+    got = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert got["small.npy"].dtype == np.float32 and np.array_equal(got["small.npy"], small.float().numpy())
+    assert got["loss.npy"].dtype == np.float64 and float(got["loss.npy"]) == 0.25
+    s = got["big.npy"]
+    assert s.dtype == np.float64 and 0.5 * bench.DUMP_BYTES < s.nbytes <= bench.DUMP_BYTES
+    assert (np.diff(s) > 0).all() and s[-1] < big.numel() and np.array_equal(s, np.round(s))    # distinct elements, index order
+    assert all(np.array_equal(got[f], np.load(tmp_path / "b" / f)) for f in files)
+
+
 def test_cli_surface_parses_like_the_reference():
     from sd_video_gen_amd import config as svg_config
     import trainers.trainer as tr
