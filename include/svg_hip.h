@@ -69,7 +69,10 @@ void svg_env_refresh(void);
 /* `kv`: "key=v[,v...];key=v" e.g. "block_out=320,640,1280,1280;layers=2;heads=8;ctx_dim=768".
  * Transformer keys: d_lat, d_model, heads, enc_layers, dec_layers, ffn (default 2048), text_dim (0; 384 for the
  *   text-conditioned variant, whose first layer is named project_image_embedding instead of embedding).
- * VAE keys: block_out (128,256,512,512), layers (2), groups (32), latent (4), f16 (0; 1 = fp16 storage instead of bf16).
+ * VAE keys: block_out (128,256,512,512), layers (2), groups (32), latent (4), f16 (0; 1 = fp16 storage instead of bf16),
+ *   stream_f32 (0; 1 = the residual stream — conv_in, every resnet's conv2 + residual, the mid-block attention's proj_attn + residual,
+ *   the up / down-sampler outputs — is stored in f32, closer to the reference's fp32 VAE; GroupNorm, conv1 and shortcut outputs and
+ *   every matrix operand stay 16-bit; works with either storage type).
  * UNet keys: block_out (320,640,1280,1280), layers (2), heads (8), ctx_dim (768), groups (32),
  *            in_ch (4), out_ch (4), attn (1,1,1,0: cross-attention per down block), fp8 (0; 1 = BASELINE configs[4]: the
  *            dense projections with K % 128 == 0 that carry no folded LayerNorm / GEGLU run in MX block-scaled fp8 —
@@ -226,6 +229,18 @@ int svg_op_conv3x3(svg_ctx* ctx, const uint16_t* x, const float* w_oihw, const f
 int svg_op_conv3x3_gn(svg_ctx* ctx, const uint16_t* x, const float* w_oihw, const float* bias, const float* gamma,
                       const float* beta, uint16_t* conv_out, uint16_t* gn_out, int B, int H, int W, int Cin, int Cout,
                       int groups, float eps, int silu, int* used_epilogue_stats, void* stream);
+/* 3x3 conv of the VAE's f32 residual stream (model key stream_f32): x (B,H,W,Cin) 16-bit, out (B,Ho,Wo,Cout) f32 = conv + bias + residual
+ * (residual: 16-bit, residual_f32: f32, or neither).  gn_out non-NULL: then the GroupNorm (+SiLU) of out into gn_out (16-bit), from the
+ * conv epilogue's column sums of the stored f32 values when that path ran (*used_epilogue_stats = 1: images >= 32 x 32 without split-K).
+ * *halo_width: 128 / 160 = the halo kernel ran with that channel tile, 0 = the implicit GEMM.  mode 0: stride 1 pad 1 (Cin 8: the
+ * small-Cin conv), 2: stride 2 pad (0,1,0,1), 3: nearest-2x upsample then stride 1 pad 1.  Cin % 64 == 0 (or 8), Cout % 4 == 0. */
+int svg_op_conv3x3_f32s(svg_ctx* ctx, const uint16_t* x, const float* w_oihw, const float* bias, const uint16_t* residual,
+                        const float* residual_f32, float* out, const float* gamma, const float* beta, uint16_t* gn_out, int B, int H,
+                        int W, int Cin, int Cout, int mode, int groups, float eps, int silu, int* halo_width, int* used_epilogue_stats,
+                        void* stream);
+/* GroupNorm (+SiLU) on NHWC f32, 16-bit output (the GroupNorms that read the VAE's f32 residual stream). */
+int svg_op_groupnorm_f32(svg_ctx* ctx, const float* x, const float* gamma, const float* beta, uint16_t* out, int B, int HW, int C,
+                         int groups, float eps, int silu, void* stream);
 /* stride-1 3x3 conv in OCP MX block-scaled fp8 (BASELINE configs[4], conv_halo_fp8.hip): x (B,H,W,Cin) 16-bit and the f32 OIHW weights
  * are quantised on the device (e4m3 + one E8M0 scale per 32 input channels), the products run on v_mfma_scale_f32_16x16x128_f8f6f4
  * with f32 accumulation; out (B,H,W,Cout) 16-bit = conv + bias (+ residual).  q_out ((B*H*W, Cp) bytes, Cp = Cin rounded up to 128)
@@ -306,6 +321,12 @@ int svg_op_gemm_fp8_f16(svg_ctx* ctx, const uint16_t* A, const uint16_t* W, cons
                         int M, int N, int K, int act, int out_f32, void* stream);
 int svg_op_groupnorm_f16(svg_ctx* ctx, const uint16_t* x, const float* gamma, const float* beta, uint16_t* out, int B, int HW,
                          int C, int groups, float eps, int silu, void* stream);
+int svg_op_conv3x3_f32s_f16(svg_ctx* ctx, const uint16_t* x, const float* w_oihw, const float* bias, const uint16_t* residual,
+                            const float* residual_f32, float* out, const float* gamma, const float* beta, uint16_t* gn_out, int B, int H,
+                            int W, int Cin, int Cout, int mode, int groups, float eps, int silu, int* halo_width, int* used_epilogue_stats,
+                            void* stream);
+int svg_op_groupnorm_f32_f16(svg_ctx* ctx, const float* x, const float* gamma, const float* beta, uint16_t* out, int B, int HW, int C,
+                             int groups, float eps, int silu, void* stream);
 int svg_op_layernorm_f16(svg_ctx* ctx, const uint16_t* x, const float* gamma, const float* beta, uint16_t* out, int M, int C,
                          float eps, void* stream);
 int svg_op_attention_f16(svg_ctx* ctx, const uint16_t* q, const uint16_t* k, const uint16_t* vt, uint16_t* out, int B, int heads,

@@ -168,6 +168,16 @@ __global__ void resize_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __res
 __global__ void f32_to_h16_kernel(const float* __restrict__ x, h16* __restrict__ y, int64_t n) {
   GRID_STRIDE(i, n) y[i] = (h16)x[i];
 }
+// the same, 8 elements (two 16-byte loads, one 16-byte store) per thread and trip: the 16-bit copy of the VAE's f32 stream
+__global__ void f32_to_h16_x8_kernel(const float* __restrict__ x, h16* __restrict__ y, int64_t n8) {
+  GRID_STRIDE(i, n8) {
+    const float4 a = ((const float4*)x)[2 * i], b = ((const float4*)x)[2 * i + 1];
+    h16x8 o;
+    o[0] = (h16)a.x; o[1] = (h16)a.y; o[2] = (h16)a.z; o[3] = (h16)a.w;
+    o[4] = (h16)b.x; o[5] = (h16)b.y; o[6] = (h16)b.z; o[7] = (h16)b.w;
+    ((h16x8*)y)[i] = o;
+  }
+}
 __global__ void h16_to_f32_kernel(const h16* __restrict__ x, float* __restrict__ y, int64_t n) {
   GRID_STRIDE(i, n) y[i] = (float)x[i];
 }
@@ -296,6 +306,11 @@ void resize_nearest_u8(const uint8_t* src, uint8_t* dst, int N, int sh, int sw, 
 void f32_to_h16(const float* x, h16* y, int64_t n, hipStream_t s) {
   hipLaunchKernelGGL(f32_to_h16_kernel, grid_for(n), dim3(256), 0, s, x, y, n);
   check_launch("f32_to_h16");
+}
+void f32_to_h16_x8(const float* x, h16* y, int64_t n, hipStream_t s) {
+  SVG_CHECK(n % 8 == 0 && ((uintptr_t)x & 31) == 0 && ((uintptr_t)y & 15) == 0, "f32_to_h16_x8: n %% 8 and 32 / 16-byte aligned pointers");
+  hipLaunchKernelGGL(f32_to_h16_x8_kernel, grid_for(n / 8), dim3(256), 0, s, x, y, n / 8);
+  check_launch("f32_to_h16_x8");
 }
 void h16_to_f32(const h16* x, float* y, int64_t n, hipStream_t s) {
   hipLaunchKernelGGL(h16_to_f32_kernel, grid_for(n), dim3(256), 0, s, x, y, n);

@@ -19,8 +19,6 @@
 namespace SDNS {
 
 // conv_halo.hip
-bool conv_halo_supported(const GemmArgs& g);
-int conv_halo_bn(const GemmArgs& g);
 void launch_conv_halo(const GemmArgs& g, dim3 grid, hipStream_t s);
 bool gemm_pp_supported(const GemmArgs& g);
 bool gemm_ws_supported(const GemmArgs& g);
@@ -40,6 +38,8 @@ __device__ __forceinline__ void epi_store_geglu(const GemmArgs& g, int z, int m,
 // WIDE: the wide tile epilogue (igemm_epi.h) — dense GEMMs with a 16-bit output and no GEGLU (the launcher decides)
 // WIDE = 2: the same 16-byte epilogue through a permutation of the W rows at load time instead of lane exchanges (igemm_epi.h: epi_perm_col) —
 // no extra registers: the form of the 160-column dense tiles (launched without split-K only: the slab path keeps natural columns)
+// WIDE = 3: not a wide form — the f32 residual stream's epilogue (GemmArgs::out_f32 == 2: f32 output, f32 or 16-bit residual, GroupNorm
+// sums of the stored f32 values); a value of this parameter rather than a new one, so that the instantiations 0-2 keep their code
 template <int BN, int AMODE, int WIDE = 0>
 __global__ void __launch_bounds__(256, 2) igemm_kernel(const GemmArgs g) {
   constexpr int NT = BN / 32;       // 16-wide n tiles per wave
@@ -285,7 +285,8 @@ __global__ void __launch_bounds__(256, 2) igemm_kernel(const GemmArgs g) {
     return;
   }
   // (an LDS-staged, 16-byte coalesced store variant measured no faster: L2 merges the 8-byte pieces)
-  epi_tile<MT, NT, AMODE == A_DENSE, WIDE>(g, z, m0 + wm * 64 + l15, 16, n0 + wn * (BN / 2) + lq * 4, acc, smem, 2, wm, wn, tm, n0);
+  epi_tile<MT, NT, AMODE == A_DENSE, WIDE == 3 ? 0 : WIDE, WIDE == 3>(g, z, m0 + wm * 64 + l15, 16, n0 + wn * (BN / 2) + lq * 4, acc, smem, 2, wm,
+                                                                     wn, tm, n0);
 }
 
 // sums the split-K slabs and applies the epilogue
@@ -317,6 +318,30 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const GemmArgs g) {
       if (g.ln_rs) v = ln_fold(g, z, m, n, v);
       epi_store(g, z, m, n, v);
     }
+  }
+}
+
+// the same for the f32 residual stream (out_f32 == 2): f32 or 16-bit residual, f32 output
+__global__ void __launch_bounds__(256) splitk_reduce_f32s_kernel(const GemmArgs g) {
+  const int z = blockIdx.y;
+  const int n4 = g.N >> 2;
+  const int64_t total = (int64_t)g.M * n4;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int m = (int)(idx / n4);
+    const int n = (int)(idx - (int64_t)m * n4) * 4;
+    f32x4 v = {0, 0, 0, 0};
+    for (int s = 0; s < g.splitk; ++s)
+      v += *(const f32x4*)(g.slabs + ((int64_t)(s * g.batch + z) * g.M + m) * g.N + n);
+    v = v * g.alpha;
+    const int64_t o = (int64_t)z * g.sC + (int64_t)m * g.ldc + n;
+    if (g.residual_f32) {
+      GemmArgs h = g;
+      h.residual = nullptr;
+      v = epi_value(h, z, m, n, v) + *(const f32x4*)(g.residual_f32 + (int64_t)z * g.sC + (int64_t)m * g.ldr + n);
+    } else {
+      v = epi_value(g, z, m, n, v);
+    }
+    *(f32x4*)((float*)g.C + o) = v;
   }
 }
 
@@ -357,10 +382,17 @@ template <int BN, int AMODE>
 constexpr bool kWideInst = (AMODE == A_DENSE && (BN == 64 || BN == 128)) || (AMODE == A_CONV_SMALLC && BN == 128);
 template <int BN, int AMODE>
 constexpr bool kPermInst = AMODE == A_DENSE && BN == 160;      // WIDE = 2 (W rows permuted at load): dense 160-column tiles
+// WIDE = 3, the f32 residual stream of the VAE: 128 / 160-column tiles (pick_bn gives no narrower one for it) of every mode the VAE uses
+template <int BN, int AMODE>
+constexpr bool kF32sInst = (BN == 128 || BN == 160) && AMODE != A_CONV_S2P1;
 
 template <int BN, int AMODE>
 void launch_inst(const GemmArgs& g, dim3 grid, hipStream_t s) {
   constexpr int smem = 2 * (BM * 128 + BN * 128);
+  if (g.out_f32 == 2) {
+    if constexpr (kF32sInst<BN, AMODE>) { hipLaunchKernelGGL((igemm_kernel<BN, AMODE, 3>), grid, dim3(256), smem, s, g); return; }
+    throw SvgError("igemm: no f32-stream instantiation for this tile width / mode");
+  }
   if constexpr (kWideInst<BN, AMODE>) {      // (BN = 160: 48 spilled registers in the exchange form — the permuted-row form below)
     if (g.act != ACT_GEGLU && !g.out_f32) { hipLaunchKernelGGL((igemm_kernel<BN, AMODE, 1>), grid, dim3(256), smem, s, g); return; }
   }
@@ -393,6 +425,8 @@ void attr_inst() {
     HIP_OK(hipFuncSetAttribute((const void*)igemm_kernel<BN, AMODE, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (BM * 128 + BN * 128)));
   if constexpr (kPermInst<BN, AMODE>)
     HIP_OK(hipFuncSetAttribute((const void*)igemm_kernel<BN, AMODE, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (BM * 128 + BN * 128)));
+  if constexpr (kF32sInst<BN, AMODE>)
+    HIP_OK(hipFuncSetAttribute((const void*)igemm_kernel<BN, AMODE, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (BM * 128 + BN * 128)));
 }
 template <int BN>
 void attr_bn() {
@@ -404,8 +438,10 @@ int pick_bn(const GemmArgs& g) {
   static const int force = getenv("SVG_GEMM_BN") ? atoi(getenv("SVG_GEMM_BN")) : 0;
   if (force && g.act != ACT_GEGLU && g.N > 64) return force;
   if (g.act == ACT_GEGLU) return 128;
-  if (g.N <= 32) return 32;
-  if (g.N <= 64) return 64;
+  if (g.out_f32 != 2) {                 // (the f32 stream has 128 / 160-column instantiations only)
+    if (g.N <= 32) return 32;
+    if (g.N <= 64) return 64;
+  }
   // per-CU serial work ~ ceil(blocks / 256) * BN (blocks beyond one per CU share the matrix pipe); ties go to the
   // width with fewer padded columns, then to the wider tile (the A panel is re-read once per column tile)
   const int64_t tm = (int64_t)cdiv(g.M, BM) * g.batch;
@@ -432,7 +468,7 @@ static int plan_splitk(const GemmArgs& g);
 int gemm_emits_gn(const GemmArgs& g0) {
   GemmArgs g = g0;
   if (g.n_valid <= 0) g.n_valid = g.N;
-  if (g.out_f32 || g.act == ACT_GEGLU || g.N > g.ldc) return 0;
+  if (g.out_f32 == 1 || g.act == ACT_GEGLU || g.N > g.ldc) return 0;
   if (g.batch != 1) return 0;
   if (plan_splitk(g) > 1) return 0;
   g.splitk = 1;
@@ -472,6 +508,9 @@ void launch_gemm(svg_ctx* ctx, const GemmArgs& g, hipStream_t s, int prof_kind) 
   }
   SVG_CHECK((int64_t)g.N * g.ldb < (1LL << 31) && g.ldb % 8 == 0, "gemm: ldb %d unsupported", g.ldb);
   if (g.act == ACT_GEGLU) SVG_CHECK(g.N % 128 == 0, "geglu: packed N must be a multiple of 128");
+  if (g.out_f32 == 2)
+    SVG_CHECK(g.act == ACT_NONE && !(g.residual && g.residual_f32) && !g.ln_rs && !g.A2, "gemm: the f32 stream takes no activation, LayerNorm fold, "
+              "second A source or two residuals");
   if (!SVG_LAUNCHING(ctx)) return;
   GemmArgs a = g;
   static const int dbg_env = getenv("SVG_GEMM_DBG") ? atoi(getenv("SVG_GEMM_DBG")) : 0;
@@ -522,7 +561,8 @@ void launch_gemm(svg_ctx* ctx, const GemmArgs& g, hipStream_t s, int prof_kind) 
   if (a.splitk > 1) {
     int64_t total = (int64_t)a.M * (a.N / 4);
     dim3 rg((unsigned)std::min<int64_t>((total + 255) / 256, 2048), a.batch);
-    hipLaunchKernelGGL(splitk_reduce_kernel, rg, dim3(256), 0, s, a);
+    if (a.out_f32 == 2) hipLaunchKernelGGL(splitk_reduce_f32s_kernel, rg, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(splitk_reduce_kernel, rg, dim3(256), 0, s, a);
     check_launch("splitk_reduce");
   }
 }

@@ -200,7 +200,9 @@ __device__ __forceinline__ int epi_perm_col(int x) {
   return j < (NT_ & ~1) ? 32 * (j >> 1) + 8 * (r >> 2) + 4 * (j & 1) + (r & 3) : x;
 }
 
-template <int MT_, int NT_, bool LN_ = false, int WIDE_ = 0>
+// RF_ (the VAE's f32 residual stream, GemmArgs::out_f32 == 2): f32 output; the residual is GemmArgs::residual_f32 (f32) or
+// GemmArgs::residual (16-bit); GN_ sums are those of the stored f32 values.  Narrow form only (natural columns).
+template <int MT_, int NT_, bool LN_ = false, int WIDE_ = 0, bool RF_ = false>
 __device__ __forceinline__ void epi_tile(const GemmArgs& g, int z, int mr, int mstep, int nc, f32x4 (&acc)[MT_][NT_],
                                          char* lds = nullptr, int WM_ = 0, int wm = 0, int wn = 0, int tile_m = 0, int n0 = 0) {
   const bool geglu = g.act == ACT_GEGLU;
@@ -220,7 +222,7 @@ __device__ __forceinline__ void epi_tile(const GemmArgs& g, int z, int mr, int m
   // that a lane's quads of tiles (j, j + 1) ARE 8 consecutive columns (epi_perm_col below: operand row r of tile j <-> column 32 (j >> 1) +
   // 8 (r >> 2) + 4 (j & 1) + (r & 3); an unpaired last tile stays natural).  No permlane instructions, no extra registers: the form for the
   // 160-column tiles, whose exchange form spills.
-  constexpr bool wide = WIDE_ != 0 && NT_ >= 2;
+  constexpr bool wide = WIDE_ != 0 && NT_ >= 2 && !RF_;
   // column of acc[i][j][0] in this lane: paired tiles cb + 16 (j & ~1) + (j & 1) * cstep, an unpaired last tile nc + 16 j (two registers,
   // not a table: these kernels sit at the 256-register limit)
   int cb = nc, cstep = 16;
@@ -264,7 +266,7 @@ __device__ __forceinline__ void epi_tile(const GemmArgs& g, int z, int mr, int m
     const int m = mr + mstep * i;
     bi[i] = (bias_z && g.bias_row && m < g.M) ? bias_z[m] : 0.f;
   }
-  const bool has_bbn = g.bias_bn != nullptr, has_res = g.residual != nullptr && !geglu;
+  const bool has_bbn = g.bias_bn != nullptr, has_res = (g.residual != nullptr || (RF_ && g.residual_f32 != nullptr)) && !geglu;
   const int ldbn = g.bias_bn_ld ? g.bias_bn_ld : g.N;
   // two row groups: halves the registers the prefetched operands need (one more exposed round trip, not twenty)
   constexpr int RG = (MT_ + 1) / 2;
@@ -368,8 +370,12 @@ __device__ __forceinline__ void epi_tile(const GemmArgs& g, int z, int mr, int m
         for (int j = 0; j < NT_; ++j) {
           const int n = nc + 16 * j;
           if (i0 + ii < MT_ && m < g.M && n < g.N) {
-            const h16x4 r = *(const h16x4*)(g.residual + (int64_t)z * g.sC + (int64_t)m * g.ldr + n);
-            ex[ii][j][0] += (float)r[0]; ex[ii][j][1] += (float)r[1]; ex[ii][j][2] += (float)r[2]; ex[ii][j][3] += (float)r[3];
+            if (RF_ && g.residual_f32) {
+              ex[ii][j] += *(const f32x4*)(g.residual_f32 + (int64_t)z * g.sC + (int64_t)m * g.ldr + n);
+            } else {
+              const h16x4 r = *(const h16x4*)(g.residual + (int64_t)z * g.sC + (int64_t)m * g.ldr + n);
+              ex[ii][j][0] += (float)r[0]; ex[ii][j][1] += (float)r[1]; ex[ii][j][2] += (float)r[2]; ex[ii][j][3] += (float)r[3];
+            }
           }
         }
       }
@@ -407,7 +413,10 @@ __device__ __forceinline__ void epi_tile(const GemmArgs& g, int z, int mr, int m
             v = gelu_erf4(v);
           }
           const int64_t o = (int64_t)z * g.sC + (int64_t)m * g.ldc + n;
-          if (g.out_f32) *(f32x4*)((float*)g.C + o) = v;
+          if (RF_) {
+            *(f32x4*)((float*)g.C + o) = v;
+            if (emit_gn) acc[i][j] = v;                      // the sums below are those of the stored f32 values
+          } else if (g.out_f32) *(f32x4*)((float*)g.C + o) = v;
           else {
             const h16x4 w = to_h16x4(v);
             *(h16x4*)((h16*)g.C + o) = w;

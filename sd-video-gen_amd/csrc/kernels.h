@@ -45,6 +45,8 @@ struct GemmArgs {
   const h16* residual = nullptr;    // [M][ldr]
   int ldr = 0;
   int act = ACT_NONE;
+  // 0: 16-bit C; 1: f32 C; 2: f32 C of the VAE's f32 residual stream (residual_f32 allowed, GroupNorm sums of the stored f32
+  // values, the halo conv) — separate kernel instantiations, so that 0 / 1 launch exactly what they did before
   int out_f32 = 0;
   // LayerNorm folded into the GEMM (W' = W * gamma, b' = b + W beta packed at load): the epilogue turns acc = x W'^T into
   // rstd[m] * acc - (rstd[m] * mean[m]) * s[n] with s[n] = sum_k W'[n][k]; applied before bias / residual / activation.
@@ -78,9 +80,13 @@ struct GemmArgs {
   int pp_merge = 0;                  // gemm_pp: one phase per slab (both k halves between two barriers) instead of two
   int pp_dma_m = 0;                  // merged ping-pong loops (gemm_pp, conv_halo): DMA instructions of a step issued among its MFMAs instead of in the load segment
   int dbg = 0;                       // ablation switch (SVG_GEMM_DBG): 1 no stores, 2 no MFMA, 3 no DMA, 5 LDS-staged epilogue
+  const float* residual_f32 = nullptr;   // [M][ldr] f32 residual (out_f32 == 2 only; exclusive with `residual`; last: the offsets of the fields above stay put)
 };
 
 void launch_gemm(svg_ctx* ctx, const GemmArgs& g, hipStream_t s, int prof_kind);
+// the halo conv (conv_halo.hip) takes g / its channel-tile width
+bool conv_halo_supported(const GemmArgs& g);
+int conv_halo_bn(const GemmArgs& g);
 // rows per row tile of the kernel gemm_auto() would launch for g, or 0 when that launch cannot emit GroupNorm statistics
 // (split-K, batched, f32 / GEGLU output)
 int gemm_emits_gn(const GemmArgs& g);
@@ -156,6 +162,9 @@ struct GnStats {
 void groupnorm(svg_ctx* ctx, const h16* x, int C1, const h16* x2, int C2, const float* gamma,
                const float* beta, h16* out, int B, int HW, int groups, float eps, int silu,
                hipStream_t s, const GnStats* st1 = nullptr, const GnStats* st2 = nullptr);
+// the same on an f32 input (the VAE's f32 residual stream), one source; st: the column sums of the stored f32 values (out_f32 == 2 epilogues)
+void groupnorm_f32(svg_ctx* ctx, const float* x, int C, const float* gamma, const float* beta, h16* out, int B, int HW, int groups, float eps,
+                   int silu, hipStream_t s, const GnStats* st = nullptr);
 // the same with an MX fp8 output (norm.hip: gn_apply_mx_kernel) for conv_halo_fp8; false = the caller takes groupnorm() + quant_act_mx()
 bool groupnorm_mx(svg_ctx* ctx, const h16* x, int C1, const h16* x2, int C2, const float* gamma, const float* beta, uint8_t* q, uint8_t* sc,
                   int B, int HW, int groups, float eps, int silu, hipStream_t s, const GnStats* st1, const GnStats* st2);
@@ -218,6 +227,8 @@ void resize_nearest_u8(const uint8_t* src, uint8_t* dst, int N, int sh, int sw, 
                        hipStream_t s);
 void f32_to_h16(const float* x, h16* y, int64_t n, hipStream_t s);
 void h16_to_f32(const h16* x, float* y, int64_t n, hipStream_t s);
+// f32 -> 16 bits, n % 8 == 0, x 32-byte and y 16-byte aligned (the 16-bit copy of the VAE's f32 stream)
+void f32_to_h16_x8(const float* x, h16* y, int64_t n, hipStream_t s);
 // timestep sinusoid (flip_sin_to_cos, shift 0): t f32[N] -> bf16 (N,dim) = [cos | sin]
 void timestep_embed(const float* t, h16* out, int N, int dim, hipStream_t s);
 void silu_h16(const h16* x, h16* y, int64_t n, hipStream_t s);

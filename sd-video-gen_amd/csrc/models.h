@@ -171,6 +171,9 @@ struct VaeAttnW { NormW gn; PackedLinear qk, v, proj; int C = 0; };
 struct VaeModel : VaeIface {
   std::vector<int> block_out{128, 256, 512, 512};
   int layers = 2, groups = 32, latent = 4;
+  // stream_f32 = 1: the residual stream (conv_in, resnet conv2 + residual, attention proj + residual, up / down-sampler outputs) is stored
+  // in f32 (the reference's VAE runs fp32); GroupNorm / conv1 / shortcut outputs and every matrix operand stay 16-bit
+  int stream_f32 = 0;
   const char* dtype() const override { return SD_F16 ? "fp16" : "bf16"; }
   // encoder
   ConvW e_conv_in, e_conv_out;
@@ -263,8 +266,11 @@ NormW load_norm(svg_ctx* ctx, WeightStore& ws, const std::string& prefix, int C)
 void add_fp8_copy(svg_ctx* ctx, PackedLinear& pl, hipStream_t s);
 float* keep_f32(svg_ctx* ctx, WeightStore& ws, const std::string& name, int64_t numel);
 // out (B,Ho,Wo,Cout) = conv3x3(x) + bias [+ per-sample bias] [+ residual]
+// output channel tile of the halo kernel conv3x3() would launch for this problem (128 / 160), 0 when it takes the implicit GEMM
+int conv3x3_halo_width(const ConvW& cw, int B, int H, int W, int amode, int out_f32);
+// out_f32: 0 16-bit, 1 f32, 2 the VAE's f32 residual stream (GemmArgs::out_f32); residual_f32: an f32 residual instead of `residual` (2 only)
 void conv3x3(svg_ctx* ctx, const h16* x, const ConvW& cw, void* out, int B, int H, int W, int amode, const float* bias_bn,
-             int bias_bn_ld, const h16* residual, int out_f32, hipStream_t s, GnEmit* emit = nullptr);
+             int bias_bn_ld, const h16* residual, int out_f32, hipStream_t s, GnEmit* emit = nullptr, const float* residual_f32 = nullptr);
 // the same stride-1 conv on MX fp8 operands (conv_halo_fp8.hip): x8 / xs = the quantised input of quant_act_mx (or of the quantising
 // GroupNorm apply pass); the caller asks conv3x3_fp8_ok() first
 // up2: nearest-2x upsample fused in front (the UNet's upsamplers): x8 is the H x W source, the output is 2H x 2W
@@ -276,6 +282,7 @@ void conv3x3_fp8(svg_ctx* ctx, const uint8_t* x8, const uint8_t* xs, const ConvW
 // channel concat [A | A2] of two tensors (columns >= k_split come from A2, row stride lda2) without materialising it.
 void linear(svg_ctx* ctx, const h16* A, int lda, const PackedLinear& pl, void* C, int ldc, int M, int act, const h16* residual,
             int ldr, int out_f32, hipStream_t s, const float* ln_rs = nullptr, const float* ln_rm = nullptr, GnEmit* emit = nullptr,
-            int rows_per_sample = 0, const h16* A2 = nullptr, int lda2 = 0, int k_split = 0, LnEmit* ln = nullptr);
+            int rows_per_sample = 0, const h16* A2 = nullptr, int lda2 = 0, int k_split = 0, LnEmit* ln = nullptr,
+            const float* residual_f32 = nullptr);
 
 }  // namespace SDNS

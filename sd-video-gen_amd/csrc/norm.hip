@@ -19,10 +19,26 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// The GroupNorm kernels read 16-bit (T = h16) or f32 (T = float: the VAE's f32 residual stream) inputs and write 16-bit outputs.
+// 8 consecutive channels of a T tensor: one 16-byte load (h16) or two (f32)
+template <typename T> struct Vec8;
+template <> struct Vec8<h16> {
+  h16x8 v;
+  __device__ __forceinline__ explicit Vec8(const h16* p) : v(*(const h16x8*)p) {}
+  __device__ __forceinline__ float operator[](int j) const { return (float)v[j]; }
+};
+typedef float f32x4n __attribute__((ext_vector_type(4)));
+template <> struct Vec8<float> {
+  f32x4n a, b;
+  __device__ __forceinline__ explicit Vec8(const float* p) : a(*(const f32x4n*)p), b(*(const f32x4n*)(p + 4)) {}
+  __device__ __forceinline__ float operator[](int j) const { return j < 4 ? a[j] : b[j - 4]; }
+};
+
 // ---- GroupNorm stage 1: per (sample, pixel-chunk) partial sums per channel-group ----------------
 // grid (nchunk, B); block = CV*PL threads where CV = C/8 channel vectors, PL pixel lanes.
 // partial[b][chunk][group][2]
-__global__ void gn_stats_kernel(const h16* __restrict__ x, int C1, const h16* __restrict__ x2, int C2,
+template <typename T>
+__global__ void gn_stats_kernel(const T* __restrict__ x, int C1, const T* __restrict__ x2, int C2,
                                 float* __restrict__ partial, int HW, int groups, int nchunk, int CV, int PL) {
   extern __shared__ float sh[];   // [PL][C][2] then reused
   const int C = C1 + C2;
@@ -38,15 +54,15 @@ __global__ void gn_stats_kernel(const h16* __restrict__ x, int C1, const h16* __
   if (tid < nthr) {
     const int cv = tid % CV, pl = tid / CV;
     const int c0 = cv * 8;
-    const h16* src; int ld, coff;
+    const T* src; int ld, coff;
     if (c0 < C1) { src = x; ld = C1; coff = c0; } else { src = x2; ld = C2; coff = c0 - C1; }
     // four pixels per trip: four independent 16-byte loads in flight per thread (a one-load-per-trip loop is a chain of
     // exposed memory latencies: ~10 trips x ~1 us)
-    const h16* sp = src + ((int64_t)b * HW + p_begin + pl) * ld + coff;
+    const T* sp = src + ((int64_t)b * HW + p_begin + pl) * ld + coff;
     const int64_t st = (int64_t)PL * ld;
     int p = p_begin + pl;
     for (; p + 3 * PL < p_end; p += 4 * PL, sp += 4 * st) {
-      const h16x8 v0 = *(const h16x8*)sp, v1 = *(const h16x8*)(sp + st), v2 = *(const h16x8*)(sp + 2 * st), v3 = *(const h16x8*)(sp + 3 * st);
+      const Vec8<T> v0(sp), v1(sp + st), v2(sp + 2 * st), v3(sp + 3 * st);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float f0 = (float)v0[j], f1 = (float)v1[j], f2 = (float)v2[j], f3 = (float)v3[j];
@@ -55,9 +71,9 @@ __global__ void gn_stats_kernel(const h16* __restrict__ x, int C1, const h16* __
       }
     }
     for (; p < p_end; p += PL, sp += st) {
-      const h16x8 v = *(const h16x8*)sp;
+      const Vec8<T> v(sp);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { float f = (float)v[j]; s[j] += f; q[j] += f * f; }
+      for (int j = 0; j < 8; ++j) { float f = v[j]; s[j] += f; q[j] += f * f; }
     }
     float* dst = sh + ((int64_t)pl * C + c0) * 2;
 #pragma unroll
@@ -82,7 +98,8 @@ __global__ void gn_stats_kernel(const h16* __restrict__ x, int C1, const h16* __
 // grid (nblk, B); block = CV*PL threads like stage 1.  Each thread owns one 8-channel vector: it folds
 // (mean, rstd, gamma, beta) into 8 (scale, shift) pairs once, then streams its pixels with 16-B loads/stores
 // and 8 FMAs per vector — no divisions or table lookups in the loop.
-__global__ void gn_apply_kernel(const h16* __restrict__ x, int C1, const h16* __restrict__ x2, int C2,
+template <typename T>
+__global__ void gn_apply_kernel(const T* __restrict__ x, int C1, const T* __restrict__ x2, int C2,
                                 const float* __restrict__ partial, const float* __restrict__ gamma,
                                 const float* __restrict__ beta, h16* __restrict__ out, int HW, int groups,
                                 int nchunk, float eps, int silu, int CV, int PL) {
@@ -124,19 +141,19 @@ __global__ void gn_apply_kernel(const h16* __restrict__ x, int C1, const h16* __
       sh[j] = beta[c0 + j] - mean_s[g] * a;
     }
   }
-  const h16* src; int ld, coff;
+  const T* src; int ld, coff;
   if (c0 < C1) { src = x; ld = C1; coff = c0; } else { src = x2; ld = C2; coff = c0 - C1; }
   const int per_blk = (HW + gridDim.x - 1) / gridDim.x;
   const int p_begin = blockIdx.x * per_blk;
   const int p_end = min(HW, p_begin + per_blk);
-  const h16* sp = src + ((int64_t)b * HW + p_begin + pl) * ld + coff;
+  const T* sp = src + ((int64_t)b * HW + p_begin + pl) * ld + coff;
   h16* dp = out + ((int64_t)b * HW + p_begin + pl) * C + c0;
   const int64_t sstep = (int64_t)PL * ld, dstep = (int64_t)PL * C;
-  auto apply = [&](const h16x8& v) -> h16x8 {
+  auto apply = [&](const Vec8<T>& v) -> h16x8 {
     h16x8 o;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      float f = fmaf((float)v[j], sc[j], sh[j]);
+      float f = fmaf(v[j], sc[j], sh[j]);
       if (silu) f = f * __builtin_amdgcn_rcpf(1.f + __expf(-f));
       o[j] = (h16)f;
     }
@@ -145,13 +162,13 @@ __global__ void gn_apply_kernel(const h16* __restrict__ x, int C1, const h16* __
   int p = p_begin + pl;
   // four pixels per trip: the four loads are issued together (see gn_stats_kernel)
   for (; p + 3 * PL < p_end; p += 4 * PL, sp += 4 * sstep, dp += 4 * dstep) {
-    const h16x8 v0 = *(const h16x8*)sp, v1 = *(const h16x8*)(sp + sstep), v2 = *(const h16x8*)(sp + 2 * sstep), v3 = *(const h16x8*)(sp + 3 * sstep);
+    const Vec8<T> v0(sp), v1(sp + sstep), v2(sp + 2 * sstep), v3(sp + 3 * sstep);
     *(h16x8*)dp = apply(v0);
     *(h16x8*)(dp + dstep) = apply(v1);
     *(h16x8*)(dp + 2 * dstep) = apply(v2);
     *(h16x8*)(dp + 3 * dstep) = apply(v3);
   }
-  for (; p < p_end; p += PL, sp += sstep, dp += dstep) *(h16x8*)dp = apply(*(const h16x8*)sp);
+  for (; p < p_end; p += PL, sp += sstep, dp += dstep) *(h16x8*)dp = apply(Vec8<T>(sp));
 }
 
 // ---- The same apply pass with an MX fp8 output (the input of conv_halo_fp8.hip): e4m3 [pixel][Cp] + one E8M0 scale per 32 channels
@@ -304,11 +321,12 @@ typedef h16 h16x4n __attribute__((ext_vector_type(4)));
 typedef h16 h16x8n __attribute__((ext_vector_type(8)));
 // VW = channels per piece: 4 (8-byte pieces: any cpg % 4 == 0) or 8 (16-byte pieces, cpg % 8 == 0 — round 5: half the vector-memory
 // instructions and half the predicated trips: 256 x 40 channels = 5 pieces per thread instead of 10)
-template <int MAXCH, int VW>
-__global__ void __launch_bounds__(256) gn_small_kernel(const h16* __restrict__ x, int C1, const h16* __restrict__ x2, int C2,
+template <int MAXCH, int VW, typename T>
+__global__ void __launch_bounds__(256) gn_small_kernel(const T* __restrict__ x, int C1, const T* __restrict__ x2, int C2,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                        h16* __restrict__ out, int HW, int groups, float eps, int silu) {
-  typedef h16 vec_t __attribute__((ext_vector_type(VW)));
+  typedef T vec_t __attribute__((ext_vector_type(VW)));
+  typedef h16 ovec_t __attribute__((ext_vector_type(VW)));
   __shared__ float red[8];
   const int C = C1 + C2, cpg = C / groups, nch = cpg / VW, total = HW * nch;
   const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
@@ -319,7 +337,7 @@ __global__ void __launch_bounds__(256) gn_small_kernel(const h16* __restrict__ x
     const int id = tid + 256 * i;
     if (id < total) {
       const int p = id / nch, c = g * cpg + (id - p * nch) * VW;
-      const h16* src = (c < C1) ? x + ((int64_t)b * HW + p) * C1 + c : x2 + ((int64_t)b * HW + p) * C2 + (c - C1);
+      const T* src = (c < C1) ? x + ((int64_t)b * HW + p) * C1 + c : x2 + ((int64_t)b * HW + p) * C2 + (c - C1);
       v[i] = *(const vec_t*)src;
 #pragma unroll
       for (int j = 0; j < VW; ++j) { const float f = (float)v[i][j]; s += f; q += f * f; }
@@ -338,7 +356,7 @@ __global__ void __launch_bounds__(256) gn_small_kernel(const h16* __restrict__ x
     const int id = tid + 256 * i;
     if (id < total) {
       const int p = id / nch, c = g * cpg + (id - p * nch) * VW;
-      vec_t o;
+      ovec_t o;
 #pragma unroll
       for (int j4 = 0; j4 < VW; j4 += 4) {
         const float4 ga = *(const float4*)(gamma + c + j4), be = *(const float4*)(beta + c + j4);
@@ -351,7 +369,7 @@ __global__ void __launch_bounds__(256) gn_small_kernel(const h16* __restrict__ x
           o[j4 + j] = (h16)f;
         }
       }
-      *(vec_t*)(out + ((int64_t)b * HW + p) * C + c) = o;
+      *(ovec_t*)(out + ((int64_t)b * HW + p) * C + c) = o;
     }
   }
 }
@@ -520,8 +538,9 @@ void gn_fold_weights(const float* W, const float* bias, const float* gamma, cons
   check_launch("gn_fold_weights");
 }
 
-void groupnorm(svg_ctx* ctx, const h16* x, int C1, const h16* x2, int C2, const float* gamma, const float* beta,
-               h16* out, int B, int HW, int groups, float eps, int silu, hipStream_t s, const GnStats* st1, const GnStats* st2) {
+template <typename T>
+static void groupnorm_t(svg_ctx* ctx, const T* x, int C1, const T* x2, int C2, const float* gamma, const float* beta,
+                        h16* out, int B, int HW, int groups, float eps, int silu, hipStream_t s, const GnStats* st1, const GnStats* st2) {
   const int C = C1 + C2;
   SVG_CHECK(C % groups == 0 && C % 8 == 0 && C1 % 8 == 0 && groups <= 64, "groupnorm: C=%d groups=%d unsupported", C, groups);
   const int CV = C / 8;
@@ -533,17 +552,17 @@ void groupnorm(svg_ctx* ctx, const h16* x, int C1, const h16* x2, int C2, const 
       if (!SVG_LAUNCHING(ctx)) return;
       char tag[96];
       snprintf(tag, sizeof(tag), "small_B%d_HW%d_C%d", B, HW, C);
-      ProfScope ps(ctx, PK_GNORM, s, 0, 2.0 * B * HW * C * 2, tag);
+      ProfScope ps(ctx, PK_GNORM, s, 0, (double)B * HW * C * (sizeof(T) + 2), tag);
       static const int vw8 = getenv("SVG_GN_SMALL_VW8") ? atoi(getenv("SVG_GN_SMALL_VW8")) : 1;
       if (vw8 && cpg % 8 == 0 && C1 % 8 == 0) {             // 16-byte pieces
         if ((int64_t)HW * (cpg / 8) <= 256 * 5)
-          hipLaunchKernelGGL((gn_small_kernel<5, 8>), dim3(groups, B), dim3(256), 0, s, x, C1, x2, C2, gamma, beta, out, HW, groups, eps, silu);
+          hipLaunchKernelGGL((gn_small_kernel<5, 8, T>), dim3(groups, B), dim3(256), 0, s, x, C1, x2, C2, gamma, beta, out, HW, groups, eps, silu);
         else
-          hipLaunchKernelGGL((gn_small_kernel<10, 8>), dim3(groups, B), dim3(256), 0, s, x, C1, x2, C2, gamma, beta, out, HW, groups, eps, silu);
+          hipLaunchKernelGGL((gn_small_kernel<10, 8, T>), dim3(groups, B), dim3(256), 0, s, x, C1, x2, C2, gamma, beta, out, HW, groups, eps, silu);
       } else if ((int64_t)HW * (cpg / 4) <= 256 * 5)
-        hipLaunchKernelGGL((gn_small_kernel<5, 4>), dim3(groups, B), dim3(256), 0, s, x, C1, x2, C2, gamma, beta, out, HW, groups, eps, silu);
+        hipLaunchKernelGGL((gn_small_kernel<5, 4, T>), dim3(groups, B), dim3(256), 0, s, x, C1, x2, C2, gamma, beta, out, HW, groups, eps, silu);
       else
-        hipLaunchKernelGGL((gn_small_kernel<20, 4>), dim3(groups, B), dim3(256), 0, s, x, C1, x2, C2, gamma, beta, out, HW, groups, eps, silu);
+        hipLaunchKernelGGL((gn_small_kernel<20, 4, T>), dim3(groups, B), dim3(256), 0, s, x, C1, x2, C2, gamma, beta, out, HW, groups, eps, silu);
       check_launch("gn_small");
       return;
     }
@@ -558,10 +577,10 @@ void groupnorm(svg_ctx* ctx, const h16* x, int C1, const h16* x2, int C2, const 
     if (SVG_LAUNCHING(ctx)) {
       char tag[96];
       snprintf(tag, sizeof(tag), "apply_B%d_HW%d_C%d", B, HW, C);
-      ProfScope ps(ctx, PK_GNORM, s, 0, 2.0 * B * HW * C * 2, tag);
+      ProfScope ps(ctx, PK_GNORM, s, 0, (double)B * HW * C * (sizeof(T) + 2), tag);
       const int threads = std::max((CV * PL + 63) / 64 * 64, 64);
       int nblk = std::max(1, std::min(HW / PL, std::max(HW / (PL * 16), (2048 + B - 1) / B)));
-      hipLaunchKernelGGL(gn_apply_kernel, dim3(nblk, B), dim3(threads), 0, s, x, C1, x2, C2, stats, gamma, beta, out, HW, groups, 0, eps,
+      hipLaunchKernelGGL(gn_apply_kernel<T>, dim3(nblk, B), dim3(threads), 0, s, x, C1, x2, C2, stats, gamma, beta, out, HW, groups, 0, eps,
                          silu, CV, PL);
       check_launch("gn_apply");
     }
@@ -574,14 +593,14 @@ void groupnorm(svg_ctx* ctx, const h16* x, int C1, const h16* x2, int C2, const 
   ctx->arena.push();
   float* partial = ctx->arena.get<float>((int64_t)B * nchunk * groups * 2);
   if (SVG_LAUNCHING(ctx)) {
-    const double bytes = (double)B * HW * C * 2;
+    const double bytes = (double)B * HW * C * sizeof(T);
     char tag[96];
     snprintf(tag, sizeof(tag), "stats_B%d_HW%d_C%d", B, HW, C);
     {
       ProfScope ps(ctx, PK_GNORM, s, 0, bytes, tag);
       const int threads = (CV * PL + 63) / 64 * 64;
       const size_t sh = (size_t)PL * C * 2 * sizeof(float);
-      hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, B), dim3(std::max(threads, 64)), sh, s, x, C1, x2, C2, partial, HW,
+      hipLaunchKernelGGL(gn_stats_kernel<T>, dim3(nchunk, B), dim3(std::max(threads, 64)), sh, s, x, C1, x2, C2, partial, HW,
                          groups, nchunk, CV, PL);
       check_launch("gn_stats");
     }
@@ -591,12 +610,21 @@ void groupnorm(svg_ctx* ctx, const h16* x, int C1, const h16* x2, int C2, const 
       const int threads = std::max((CV * PL + 63) / 64 * 64, 64);
       // ~16 pixels per thread, at least enough blocks to fill the chip
       int nblk = std::max(1, std::min(HW / PL, std::max(HW / (PL * 16), (2048 + B - 1) / B)));
-      hipLaunchKernelGGL(gn_apply_kernel, dim3(nblk, B), dim3(threads), 0, s, x, C1, x2, C2, partial, gamma, beta, out, HW,
+      hipLaunchKernelGGL(gn_apply_kernel<T>, dim3(nblk, B), dim3(threads), 0, s, x, C1, x2, C2, partial, gamma, beta, out, HW,
                          groups, nchunk, eps, silu, CV, PL);
       check_launch("gn_apply");
     }
   }
   ctx->arena.pop();
+}
+
+void groupnorm(svg_ctx* ctx, const h16* x, int C1, const h16* x2, int C2, const float* gamma, const float* beta,
+               h16* out, int B, int HW, int groups, float eps, int silu, hipStream_t s, const GnStats* st1, const GnStats* st2) {
+  groupnorm_t<h16>(ctx, x, C1, x2, C2, gamma, beta, out, B, HW, groups, eps, silu, s, st1, st2);
+}
+void groupnorm_f32(svg_ctx* ctx, const float* x, int C, const float* gamma, const float* beta, h16* out, int B, int HW, int groups, float eps,
+                   int silu, hipStream_t s, const GnStats* st) {
+  groupnorm_t<float>(ctx, x, C, nullptr, 0, gamma, beta, out, B, HW, groups, eps, silu, s, st, nullptr);
 }
 
 // GroupNorm (+SiLU) whose output is MX fp8 (e4m3 [B*HW][Cp] + E8M0 [B*HW][Cp/32], Cp = C rounded up to 128): the statistics must

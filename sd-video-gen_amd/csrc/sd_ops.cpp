@@ -151,6 +151,52 @@ int SVG_OP(svg_op_conv3x3_gn)(svg_ctx* ctx, const uint16_t* x, const float* w_oi
   API_END(ctx)
 }
 
+// conv3x3 of the VAE's f32 residual stream: f32 output (+ 16-bit or f32 residual), optionally followed by the GroupNorm on it
+int SVG_OP(svg_op_conv3x3_f32s)(svg_ctx* ctx, const uint16_t* x, const float* w_oihw, const float* bias, const uint16_t* residual,
+                                const float* residual_f32, float* out, const float* gamma, const float* beta, uint16_t* gn_out, int B, int H, int W,
+                                int Cin, int Cout, int mode, int groups, float eps, int silu, int* halo_width, int* used_epilogue_stats,
+                                void* stream) {
+  API_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  SVG_CHECK(Cout % 4 == 0 && (Cin % 64 == 0 || (Cin == 8 && mode == 0)), "conv3x3_f32s op: Cout %% 4 and Cin %% 64 (or Cin 8, mode 0) must be 0");
+  SVG_CHECK(mode == 0 || mode == 2 || mode == 3, "conv3x3_f32s op: mode 0 (stride 1), 2 (stride 2, pad (0,1,0,1)) or 3 (nearest-2x upsample)");
+  SVG_CHECK(!(residual && residual_f32), "conv3x3_f32s op: one residual");
+  SVG_CHECK(!gn_out || (gamma && beta), "conv3x3_f32s op: the GroupNorm needs gamma and beta");
+  const int amode = mode == 0 ? A_CONV_S1 : (mode == 2 ? A_CONV_S2ASYM : A_CONV_UP2);
+  const int Ho = mode == 0 ? H : (mode == 2 ? H / 2 : 2 * H), Wo = mode == 0 ? W : (mode == 2 ? W / 2 : 2 * W);
+  int used = 0, hw = 0;
+  run_planned(ctx, [&]() {
+    ConvW cw;
+    cw.Cin = Cin; cw.Cout = Cout; cw.Opad = Cout;
+    cw.w = ctx->arena.get<h16>((int64_t)Cout * 9 * Cin);
+    float* wdev = ctx->arena.get<float>((int64_t)Cout * Cin * 9);
+    cw.b = ctx->arena.get<float>(Cout);
+    if (SVG_LAUNCHING(ctx)) {
+      HIP_OK(hipMemcpyAsync(wdev, w_oihw, (size_t)Cout * Cin * 9 * sizeof(float), hipMemcpyDefault, s));
+      HIP_OK(hipMemsetAsync(cw.b, 0, Cout * sizeof(float), s));
+      if (bias) HIP_OK(hipMemcpyAsync(cw.b, bias, Cout * sizeof(float), hipMemcpyDefault, s));
+      pack_conv3x3(wdev, cw.w, Cout, Cin, Cout, Cin, s);
+    }
+    hw = conv3x3_halo_width(cw, B, H, W, amode, 2);
+    GnEmit e;
+    e.buf = ctx->arena.get<float>(gn_part_floats(B, (int64_t)Ho * Wo, Cout));
+    conv3x3(ctx, (const h16*)x, cw, out, B, H, W, amode, nullptr, 0, (const h16*)residual, 2, s, gn_out ? &e : nullptr, residual_f32);
+    used = e.st.valid() ? 1 : 0;
+    if (gn_out) groupnorm_f32(ctx, out, Cout, gamma, beta, (h16*)gn_out, B, Ho * Wo, groups, eps, silu, s, &e.st);
+  });
+  if (halo_width) *halo_width = hw;
+  if (used_epilogue_stats) *used_epilogue_stats = used;
+  API_END(ctx)
+}
+
+// GroupNorm (+SiLU) on an f32 NHWC input (the VAE's f32 residual stream), 16-bit output; statistics pass or single-launch small-HW path
+int SVG_OP(svg_op_groupnorm_f32)(svg_ctx* ctx, const float* x, const float* gamma, const float* beta, uint16_t* out, int B, int HW, int C,
+                                 int groups, float eps, int silu, void* stream) {
+  API_BEGIN
+  run_planned(ctx, [&]() { groupnorm_f32(ctx, x, C, gamma, beta, (h16*)out, B, HW, groups, eps, silu, (hipStream_t)stream); });
+  API_END(ctx)
+}
+
 // C[M,N] = [A | A2][M, K] * W[N,K]^T + bias: dense GEMM whose A operand is the channel concat of two tensors (A: k_split columns)
 int SVG_OP(svg_op_gemm_cat)(svg_ctx* ctx, const uint16_t* A, const uint16_t* A2, const uint16_t* W, const float* bias, uint16_t* C, int M, int N,
                     int K, int k_split, void* stream) {

@@ -121,8 +121,28 @@ void conv3x3_fp8(svg_ctx* ctx, const uint8_t* x8, const uint8_t* xs, const ConvW
   conv_halo_fp8(ctx, x8, xs, cw.w8, cw.w8s, cw.Opad, g, s);
 }
 
+// the implicit-GEMM problem of a 3x3 conv (no epilogue operands)
+static GemmArgs conv3x3_args(const h16* x, const ConvW& cw, int B, int H, int W, int amode, int out_f32) {
+  GemmArgs g;
+  g.A = x; g.H = H; g.W = W; g.Cin = cw.Cin;
+  g.amode = (cw.Cin == 8) ? A_CONV_SMALLC : amode;
+  SVG_CHECK(cw.Cin != 8 || amode == A_CONV_S1, "small-Cin conv supports stride 1 only");
+  switch (amode) {
+    case A_CONV_S1: g.Ho = H; g.Wo = W; break;
+    case A_CONV_S2P1: case A_CONV_S2ASYM: g.Ho = H / 2; g.Wo = W / 2; break;
+    case A_CONV_UP2: g.Ho = 2 * H; g.Wo = 2 * W; break;
+    default: throw SvgError("conv3x3: bad mode");
+  }
+  g.Wt = cw.w; g.ldb = 9 * cw.Cin; g.K = 9 * cw.Cin;
+  g.M = B * g.Ho * g.Wo; g.N = cw.Opad; g.n_valid = cw.Opad;
+  g.bias = cw.b;
+  g.out_f32 = out_f32;
+  return g;
+}
+
 void conv3x3(svg_ctx* ctx, const h16* x, const ConvW& cw, void* out, int B, int H, int W, int amode, const float* bias_bn,
-             int bias_bn_ld, const h16* residual, int out_f32, hipStream_t s, GnEmit* emit) {
+             int bias_bn_ld, const h16* residual, int out_f32, hipStream_t s, GnEmit* emit, const float* residual_f32) {
+  SVG_CHECK(!residual_f32 || (out_f32 == 2 && !residual), "conv3x3: an f32 residual needs the f32-stream output and no 16-bit residual");
   // the kernels address an operand with 32-bit byte offsets: an input or output of 2^31 elements or more (the 512 x 512
   // VAE levels beyond ~30 images) is processed in batch chunks
   {
@@ -139,35 +159,30 @@ void conv3x3(svg_ctx* ctx, const h16* x, const ConvW& cw, void* out, int B, int 
         const int64_t o = (int64_t)b0 * Ho * Wo * cw.Opad;
         conv3x3(ctx, x + (int64_t)b0 * H * W * cin, cw, out_f32 ? (void*)((float*)out + o) : (void*)((h16*)out + o), nb, H, W, amode,
                 bias_bn ? bias_bn + (int64_t)b0 * (bias_bn_ld ? bias_bn_ld : cw.Opad) : nullptr, bias_bn_ld,
-                residual ? residual + o : nullptr, out_f32, s);
+                residual ? residual + o : nullptr, out_f32, s, nullptr, residual_f32 ? residual_f32 + o : nullptr);
       }
       return;
     }
   }
-  GemmArgs g;
-  g.A = x; g.H = H; g.W = W; g.Cin = cw.Cin;
-  g.amode = (cw.Cin == 8) ? A_CONV_SMALLC : amode;
-  SVG_CHECK(cw.Cin != 8 || amode == A_CONV_S1, "small-Cin conv supports stride 1 only");
-  switch (amode) {
-    case A_CONV_S1: g.Ho = H; g.Wo = W; break;
-    case A_CONV_S2P1: case A_CONV_S2ASYM: g.Ho = H / 2; g.Wo = W / 2; break;
-    case A_CONV_UP2: g.Ho = 2 * H; g.Wo = 2 * W; break;
-    default: throw SvgError("conv3x3: bad mode");
-  }
-  g.Wt = cw.w; g.ldb = 9 * cw.Cin; g.K = 9 * cw.Cin;
-  g.M = B * g.Ho * g.Wo; g.N = cw.Opad; g.n_valid = cw.Opad;
-  g.bias = cw.b;
+  GemmArgs g = conv3x3_args(x, cw, B, H, W, amode, out_f32);
   g.bias_bn = bias_bn; g.bias_bn_ld = bias_bn_ld; g.rows_per_batch = g.Ho * g.Wo;
   g.residual = residual; g.ldr = cw.Opad;
-  g.C = out; g.ldc = cw.Opad; g.out_f32 = out_f32;
+  g.C = out; g.ldc = cw.Opad;
+  g.residual_f32 = residual_f32;
   plan_gn_emit(g, emit, g.Ho * g.Wo);
   gemm_auto(ctx, g, s, PK_CONV3);
 }
 
+int conv3x3_halo_width(const ConvW& cw, int B, int H, int W, int amode, int out_f32) {
+  const GemmArgs g = conv3x3_args(nullptr, cw, B, H, W, amode, out_f32);
+  return conv_halo_supported(g) ? conv_halo_bn(g) : 0;
+}
+
 void linear(svg_ctx* ctx, const h16* A, int lda, const PackedLinear& pl, void* C, int ldc, int M, int act, const h16* residual,
             int ldr, int out_f32, hipStream_t s, const float* ln_rs, const float* ln_rm, GnEmit* emit, int rows_per_sample,
-            const h16* A2, int lda2, int k_split, LnEmit* ln) {
+            const h16* A2, int lda2, int k_split, LnEmit* ln, const float* residual_f32) {
   if (ln) ln->tiles = 0;
+  SVG_CHECK(!residual_f32 || (out_f32 == 2 && !residual), "linear: an f32 residual needs the f32-stream output and no 16-bit residual");
   SVG_CHECK((pl.ln_s != nullptr) == (ln_rs != nullptr), "linear: LayerNorm-folded weights need the row statistics (and only they)");
   {   // 32-bit operand offsets in the kernels: split very tall problems (1 x 1 convs on the 512 x 512 VAE levels) by rows
     const int64_t lim = chunk_limit();
@@ -179,11 +194,12 @@ void linear(svg_ctx* ctx, const h16* A, int lda, const PackedLinear& pl, void* C
       const int csz = out_f32 ? 4 : 2;
       for (int m0 = 0; m0 < M; m0 += chunk)
         linear(ctx, A + (int64_t)m0 * lda, lda, pl, (char*)C + (int64_t)m0 * ldc * csz, ldc, std::min(chunk, M - m0), act,
-               residual ? residual + (int64_t)m0 * ldr : nullptr, ldr, out_f32, s, ln_rs ? ln_rs + m0 : nullptr, ln_rm ? ln_rm + m0 : nullptr);
+               residual ? residual + (int64_t)m0 * ldr : nullptr, ldr, out_f32, s, ln_rs ? ln_rs + m0 : nullptr, ln_rm ? ln_rm + m0 : nullptr,
+               nullptr, 0, nullptr, 0, 0, nullptr, residual_f32 ? residual_f32 + (int64_t)m0 * ldr : nullptr);
       return;
     }
   }
-  if (pl.w8 && !A2 && !ln_rs && act != ACT_GEGLU && M >= 1024 && lda == pl.K && gemm_fp8_supported(M, pl.N, pl.K)) {
+  if (pl.w8 && !A2 && !ln_rs && act != ACT_GEGLU && out_f32 != 2 && M >= 1024 && lda == pl.K && gemm_fp8_supported(M, pl.N, pl.K)) {
     // MX fp8: the activations are quantised per 32-element block on the way in (one extra pass over A), f32 accumulate
     ctx->arena.push();
     uint8_t* aq = ctx->arena.get<uint8_t>((int64_t)M * pl.K);
@@ -200,6 +216,7 @@ void linear(svg_ctx* ctx, const h16* A, int lda, const PackedLinear& pl, void* C
   g.A = A; g.lda = lda; g.Wt = pl.w; g.ldb = pl.K; g.M = M; g.N = pl.N; g.K = pl.K; g.n_valid = pl.N;
   g.bias = pl.b; g.act = act; g.residual = residual; g.ldr = ldr; g.C = C; g.ldc = ldc; g.out_f32 = out_f32;
   g.A2 = A2; g.lda2 = lda2; g.k_split = k_split;
+  g.residual_f32 = residual_f32;
   plan_gn_emit(g, emit, rows_per_sample);
   if (ln && ln->buf) {
     static const int use_ln = getenv("SVG_LN_EPI") ? atoi(getenv("SVG_LN_EPI")) : 1;    // 0: A/B switch, ln_stats pass as before

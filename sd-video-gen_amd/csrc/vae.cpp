@@ -10,6 +10,7 @@ void VaeModel::configure(const char* kv) {
   if (m.count("layers")) layers = (int)m["layers"][0];
   if (m.count("groups")) groups = (int)m["groups"][0];
   if (m.count("latent")) latent = (int)m["latent"][0];
+  if (m.count("stream_f32")) stream_f32 = m["stream_f32"][0] != 0 ? 1 : 0;
   ready = false;
 }
 
@@ -102,47 +103,72 @@ struct VaeRun {
   svg_ctx* ctx; VaeModel* m; hipStream_t s; int N;
   static constexpr float EPS = 1e-6f;
 
-  // an activation tensor with, when its producer's epilogue left them, the GroupNorm column sums of its row tiles
+  // an activation tensor — 16-bit (p) or, in the f32-stream mode, f32 (f) — with, when its producer's epilogue left them, the
+  // GroupNorm column sums of its row tiles
   struct Act {
     h16* p = nullptr;
+    float* f = nullptr;
     GnStats st;
   };
+  int out_mode() const { return m->stream_f32 ? 2 : 0; }
+  // a stream tensor of P x C elements in the storage of the mode
+  Act alloc_act(int64_t P, int C) {
+    Act y;
+    if (m->stream_f32) y.f = ctx->arena.get<float>(P * C); else y.p = ctx->arena.get<h16>(P * C);
+    return y;
+  }
+  void* ptr(const Act& y) const { return y.f ? (void*)y.f : (void*)y.p; }
+  // the 16-bit copy of a stream tensor that the up / down-sampler and shortcut convs read (allocated at the caller's arena scope)
+  const h16* as_h16(const Act& x, int64_t n) {
+    if (!x.f) return x.p;
+    h16* y = ctx->arena.get<h16>(n);
+    if (SVG_LAUNCHING(ctx)) { ProfScope ps(ctx, PK_ELT, s, 0, 6.0 * n); f32_to_h16_x8(x.f, y, n, s); }
+    return y;
+  }
+  void norm(const Act& x, const NormW& nw, h16* out, int HW, int silu) {
+    if (x.f) groupnorm_f32(ctx, x.f, nw.C, nw.g, nw.b, out, N, HW, m->groups, EPS, silu, s, &x.st);
+    else groupnorm(ctx, x.p, nw.C, nullptr, 0, nw.g, nw.b, out, N, HW, m->groups, EPS, silu, s, &x.st, nullptr);
+  }
   GnEmit emit_for(int64_t hw, int Cout) {
     GnEmit e;
     if (hw >= 1024) e.buf = ctx->arena.get<float>(gn_part_floats(N, hw, Cout));
     return e;
   }
-  Act conv(const h16* x, const ConvW& cw, int H, int W, int amode) {
+  // the input: a 16-bit tensor, or a stream tensor (read through its 16-bit copy)
+  Act conv(const Act& xa, const ConvW& cw, int H, int W, int amode) {
     const int Ho = amode == A_CONV_UP2 ? 2 * H : (amode == A_CONV_S2ASYM ? H / 2 : H), Wo = amode == A_CONV_UP2 ? 2 * W : (amode == A_CONV_S2ASYM ? W / 2 : W);
-    Act y;
-    y.p = ctx->arena.get<h16>((int64_t)N * Ho * Wo * cw.Opad);
+    Act y = alloc_act((int64_t)N * Ho * Wo, cw.Opad);
     GnEmit e = emit_for((int64_t)Ho * Wo, cw.Opad);
-    conv3x3(ctx, x, cw, y.p, N, H, W, amode, nullptr, 0, nullptr, 0, s, &e);
+    ctx->arena.push();
+    const h16* x = as_h16(xa, (int64_t)N * H * W * cw.Cin);
+    conv3x3(ctx, x, cw, ptr(y), N, H, W, amode, nullptr, 0, nullptr, out_mode(), s, &e);
+    ctx->arena.pop();
     y.st = e.st;
     return y;
   }
+  Act conv(h16* x, const ConvW& cw, int H, int W, int amode) { Act a; a.p = x; return conv(a, cw, H, W, amode); }
 
   // out = conv2(silu(gn2(conv1(silu(gn1(x)))))) + shortcut(x)
   Act resnet(const Act& x, const ResW& r, int H, int W) {
     const int64_t P = (int64_t)N * H * W;
-    Act out;
-    out.p = ctx->arena.get<h16>(P * r.c2.Opad);
+    Act out = alloc_act(P, r.c2.Opad);
     GnEmit eo = emit_for((int64_t)H * W, r.c2.Opad);
     ctx->arena.push();
     h16* t0 = ctx->arena.get<h16>(P * r.n1.C);
-    groupnorm(ctx, x.p, r.n1.C, nullptr, 0, r.n1.g, r.n1.b, t0, N, H * W, m->groups, EPS, 1, s, &x.st, nullptr);
+    norm(x, r.n1, t0, H * W, 1);
     h16* t1 = ctx->arena.get<h16>(P * r.c1.Opad);
     GnEmit e1 = emit_for((int64_t)H * W, r.c1.Opad);
     conv3x3(ctx, t0, r.c1, t1, N, H, W, A_CONV_S1, nullptr, 0, nullptr, 0, s, &e1);
     h16* t2 = ctx->arena.get<h16>(P * r.n2.C);
     groupnorm(ctx, t1, r.n2.C, nullptr, 0, r.n2.g, r.n2.b, t2, N, H * W, m->groups, EPS, 1, s, &e1.st, nullptr);
     const h16* res = x.p;
+    const float* res_f = x.f;
     if (r.has_sc) {
       h16* sc = ctx->arena.get<h16>(P * r.sc.N);
-      linear(ctx, x.p, r.n1.C, r.sc, sc, r.sc.N, (int)P, ACT_NONE, nullptr, 0, 0, s);
-      res = sc;
+      linear(ctx, as_h16(x, P * r.n1.C), r.n1.C, r.sc, sc, r.sc.N, (int)P, ACT_NONE, nullptr, 0, 0, s);
+      res = sc; res_f = nullptr;
     }
-    conv3x3(ctx, t2, r.c2, out.p, N, H, W, A_CONV_S1, nullptr, 0, res, 0, s, &eo);
+    conv3x3(ctx, t2, r.c2, ptr(out), N, H, W, A_CONV_S1, nullptr, 0, res, out_mode(), s, &eo, res_f);
     ctx->arena.pop();
     out.st = eo.st;
     return out;
@@ -150,15 +176,14 @@ struct VaeRun {
 
   // single-head attention over HW tokens (d = C = 512): fused (attn_vae.hip) when HW is a multiple of 64, else three GEMMs + row softmax
   Act attn(const Act& xa, const VaeAttnW& a, int H, int W) {
-    const h16* x = xa.p;
     const int HW = H * W, C = a.C;
     const int64_t P = (int64_t)N * HW;
     const int HWp = (int)align_up(HW, 8);
-    h16* out = ctx->arena.get<h16>(P * C);
+    Act y = alloc_act(P, C);
     GnEmit eo = emit_for(HW, C);
     ctx->arena.push();
     h16* n = ctx->arena.get<h16>(P * C);
-    groupnorm(ctx, x, C, nullptr, 0, a.gn.g, a.gn.b, n, N, HW, m->groups, EPS, 0, s, &xa.st, nullptr);
+    norm(xa, a.gn, n, HW, 0);
     h16* qk = ctx->arena.get<h16>(P * 2 * C);
     linear(ctx, n, C, a.qk, qk, 2 * C, (int)P, ACT_NONE, nullptr, 0, 0, s);
     // V^T[b] = Wv * n_b^T + bv (per row)
@@ -193,16 +218,15 @@ struct VaeRun {
         gemm_auto(ctx, g, s, PK_GEMM);
       }
     }
-    linear(ctx, o, C, a.proj, out, C, (int)P, ACT_NONE, x, C, 0, s, nullptr, nullptr, &eo, HW);
+    linear(ctx, o, C, a.proj, ptr(y), C, (int)P, ACT_NONE, xa.p, C, out_mode(), s, nullptr, nullptr, &eo, HW, nullptr, 0, 0, nullptr, xa.f);
     ctx->arena.pop();
-    Act y;
-    y.p = out; y.st = eo.st;
+    y.st = eo.st;
     return y;
   }
 
   h16* norm_act(const Act& x, const NormW& nw, int H, int W) {
     h16* t = ctx->arena.get<h16>((int64_t)N * H * W * nw.C);
-    groupnorm(ctx, x.p, nw.C, nullptr, 0, nw.g, nw.b, t, N, H * W, m->groups, EPS, 1, s, &x.st, nullptr);
+    norm(x, nw, t, H * W, 1);
     return t;
   }
 };
@@ -223,7 +247,7 @@ void VaeModel::encode(svg_ctx* ctx, const uint8_t* img, int N, int srcH, int src
     for (int i = 0; i < nb; ++i) {
       for (auto& rw : e_down[i]) x = r.resnet(x, rw, h, w);
       if (i < nb - 1) {
-        x = r.conv(x.p, e_downs[i], h, w, A_CONV_S2ASYM);
+        x = r.conv(x, e_downs[i], h, w, A_CONV_S2ASYM);
         h /= 2; w /= 2;
       }
     }
@@ -269,7 +293,7 @@ void VaeModel::decode(svg_ctx* ctx, const float* z, int N, int h, int w, uint8_t
     for (int i = 0; i < nb; ++i) {
       for (auto& rw : d_up[i]) x = r.resnet(x, rw, H, W);
       if (i < nb - 1) {
-        x = r.conv(x.p, d_ups[i], H, W, A_CONV_UP2);
+        x = r.conv(x, d_ups[i], H, W, A_CONV_UP2);
         H *= 2; W *= 2;
       }
     }

@@ -232,7 +232,8 @@ class LMSDiscreteScheduler:
 
 
 class SDUtils():
-    def __init__(self, weights=None, text_embeddings=None, seed=0, verbose=True, arch=None, ctx=None, fp8=None, dtype=None, vae_dtype=None):
+    def __init__(self, weights=None, text_embeddings=None, seed=0, verbose=True, arch=None, ctx=None, fp8=None, dtype=None, vae_dtype=None,
+                 vae_residual=None):
         self.config, self.args = parse_config_args()             # sd_utils.py:22
         self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
         if self.device.type != "cuda":
@@ -262,6 +263,12 @@ class SDUtils():
         self.vae_dtype = (vae_dtype or os.environ.get("SVG_VAE_DTYPE", "fp16")).lower().replace("float16", "fp16").replace("half", "fp16")
         if self.vae_dtype not in ("bf16", "fp16"):
             raise ValueError("SDUtils vae_dtype must be 'bf16' or 'fp16', got %r" % (self.vae_dtype,))
+        # 'f32' stores the VAE's residual stream (conv_in, resnet conv2 + residual, attention proj + residual, up / down-sampler outputs)
+        # in f32, closer to the reference's fp32 VAE (sd_utils.py:140,162): fewer uint8 flips of the decoded frame, every matrix operand
+        # still 16-bit (svg_hip.h, VAE key stream_f32).  'fp16' (default): the stream in the VAE's 16-bit storage.
+        self.vae_residual = (vae_residual or os.environ.get("SVG_VAE_RESIDUAL", "fp16")).lower()
+        if self.vae_residual not in ("fp16", "f32"):
+            raise ValueError("SDUtils vae_residual must be 'fp16' or 'f32', got %r" % (self.vae_residual,))
         # `arch` overrides the SD v1.4 widths (reduced-size parity tests): {'vae': {...}, 'unet': {...}}
         # (a local diffusers directory's config.json plays the same role, as it does for from_pretrained)
         local = os.environ.get("SVG_SD_WEIGHTS")
@@ -312,7 +319,7 @@ class SDUtils():
         va = self.vae_arch
         sd, self.vae_source = self._weights_for("vae", weights, lambda: sd_layout.vae_shapes(va), self._seed + 1)
         ctx.configure(_lib.SVG_VAE, block_out=list(va["block_out"]), layers=va["layers"], groups=va["groups"], latent=4,
-                      f16=int(self.vae_dtype == "fp16"))
+                      f16=int(self.vae_dtype == "fp16"), stream_f32=int(self.vae_residual == "f32"))
         ctx.load_state_dict(_lib.SVG_VAE, sd)
         vae = _VAE(ctx, ctx.finalize(_lib.SVG_VAE))
         del sd
