@@ -258,6 +258,43 @@ int svg_op_gemm_lnstats(svg_ctx* ctx, const uint16_t* A, const uint16_t* W, cons
                         int N, int K, int batch, float* rs, float* rm, int* used, void* stream);
 int svg_op_gemm_cat(svg_ctx* ctx, const uint16_t* A, const uint16_t* A2, const uint16_t* W, const float* bias, uint16_t* C,
                     int M, int N, int K, int k_split, void* stream);
+/* One GEMM / implicit-GEMM conv with the whole epilogue contract the models use (test hook): the fields mirror the library's own
+ * launch descriptor and reach the kernel selection unchanged (no packing, no folding here).  Per batch z:
+ *   C[z][m][n] = act( LN( alpha * A[z] W[z]^T )[m][n] + bias[z][n or m] + bias_bn[m / rows_per_batch][n] + residual[z][m][n] )
+ * with LN(x) = x (ln_rs NULL), rs[m] x - rm[m] s[n] (normal) or rs[t] x - rm[t] s[m], t = z * ln_zstride + n (ln_swapped; tokens
+ * n >= n_valid count as rs = rm = 0).  A[z] = A + z * sA, W[z] = Wt + z * sB, C[z] = C + z * sC, residual[z] = residual + z * sC,
+ * bias[z] = bias + z * bias_zs.  amode 0: dense A (row stride lda); 1: 3x3 stride-1 conv of NHWC A (B, H, W, Cin), 4: 3x3 conv
+ * of its nearest-2x upsample, (Ho, Wo) the output image, M = B * Ho * Wo, K = 9 * Cin, Wt packed [N][9][Cin] (tap-major).  Rows
+ * n >= n_valid of Wt read as zero.  act: 0 none, 1 SiLU, 2 GELU (erf), 3 GEGLU (Wt in 16-row h / gate tiles).  out_f32: C is f32.  vt_out: the fused q | k | V^T write
+ * (columns >= vt_n0 go transposed to vt_out[m / vt_rows][n - vt_n0][m % vt_rows], row stride vt_ld, sample stride vt_bs).
+ * path (int[3], or NULL) receives what ran: {kernel family (0 tiled igemm, 1 conv_halo, 2 gemm_pp, 3 gemm_ws), column tile, split-K}.
+ * Combinations no kernel honours per batch (bias_bn or a normal LayerNorm fold with batch > 1, bias_zs with GEGLU) and a V^T write
+ * of a partial last sample (M % vt_rows != 0) return an error without launching anything. */
+typedef struct svg_gemm_desc {
+  int amode, H, W, Cin, Ho, Wo;
+  const uint16_t* A;
+  int lda;
+  const uint16_t* Wt;
+  int ldb, n_valid;
+  void* C;
+  int ldc, M, N, K, batch;
+  int64_t sA, sB, sC;
+  float alpha;
+  const float* bias;
+  int bias_row;
+  int64_t bias_zs;
+  const float* bias_bn;
+  int rows_per_batch, bias_bn_ld;
+  const uint16_t* residual;
+  int ldr, act, out_f32;
+  const float *ln_rs, *ln_rm, *ln_s;
+  int ln_swapped;
+  int64_t ln_zstride;
+  uint16_t* vt_out;
+  int vt_n0, vt_rows, vt_ld;
+  int64_t vt_bs;
+} svg_gemm_desc;
+int svg_op_gemm_ex(svg_ctx* ctx, const svg_gemm_desc* desc, int* path, void* stream);
 /* Fused GEGLU feed-forward of a BasicTransformerBlock (C = 320): out = ff.net.2(GEGLU(ff.net.0(LayerNorm(x)))) + residual in ONE
  * kernel (the M x 4C intermediate never reaches HBM).  x, residual, out: (M,C) bf16; w1 (8C,C) = [h; gate], b1 (8C), w2 (C,4C),
  * b2 (C), LayerNorm gamma / beta (C): f32 in the state_dict layout (folded and packed inside: test hook). */
@@ -306,6 +343,7 @@ int svg_op_conv3x3_gn_f16(svg_ctx* ctx, const uint16_t* x, const float* w_oihw, 
                           int groups, float eps, int silu, int* used_epilogue_stats, void* stream);
 int svg_op_gemm_lnstats_f16(svg_ctx* ctx, const uint16_t* A, const uint16_t* W, const float* bias, const uint16_t* residual,
                             uint16_t* C, int M, int N, int K, int batch, float* rs, float* rm, int* used, void* stream);
+int svg_op_gemm_ex_f16(svg_ctx* ctx, const svg_gemm_desc* desc, int* path, void* stream);
 int svg_op_gemm_cat_f16(svg_ctx* ctx, const uint16_t* A, const uint16_t* A2, const uint16_t* W, const float* bias, uint16_t* C,
                         int M, int N, int K, int k_split, void* stream);
 int svg_op_ff_fused_f16(svg_ctx* ctx, const uint16_t* x, const float* ln_gamma, const float* ln_beta, const float* w1,

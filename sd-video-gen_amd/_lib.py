@@ -29,6 +29,18 @@ class TrainCfg(C.Structure):
                 ("dropout_p", _f), ("seed", C.c_uint64)]
 
 
+class GemmDesc(C.Structure):
+    """struct svg_gemm_desc (include/svg_hip.h): the GEMM launch descriptor of svg_op_gemm_ex."""
+    _fields_ = [("amode", _i), ("H", _i), ("W", _i), ("Cin", _i), ("Ho", _i), ("Wo", _i),
+                ("A", _vp), ("lda", _i), ("Wt", _vp), ("ldb", _i), ("n_valid", _i),
+                ("C", _vp), ("ldc", _i), ("M", _i), ("N", _i), ("K", _i), ("batch", _i),
+                ("sA", _i64), ("sB", _i64), ("sC", _i64),
+                ("alpha", _f), ("bias", _vp), ("bias_row", _i), ("bias_zs", _i64),
+                ("bias_bn", _vp), ("rows_per_batch", _i), ("bias_bn_ld", _i),
+                ("residual", _vp), ("ldr", _i), ("act", _i), ("out_f32", _i),
+                ("ln_rs", _vp), ("ln_rm", _vp), ("ln_s", _vp), ("ln_swapped", _i), ("ln_zstride", _i64),
+                ("vt_out", _vp), ("vt_n0", _i), ("vt_rows", _i), ("vt_ld", _i), ("vt_bs", _i64)]
+
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/svg_hip.h
 SIGNATURES = {
@@ -65,6 +77,7 @@ SIGNATURES = {
     "svg_op_conv3x3_gn": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, C.POINTER(_i), _vp],
     "svg_op_gemm_lnstats": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, C.POINTER(_i), _vp],
     "svg_op_gemm_cat": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "svg_op_gemm_ex": [_vp, C.POINTER(GemmDesc), C.POINTER(_i), _vp],
     "svg_op_ff_fused": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "svg_op_xattn_fused": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp],
     "svg_op_dropout_mask": [_vp, C.c_uint64, _i, _f, _vp, _i64, _vp],
@@ -90,7 +103,7 @@ SIGNATURES = {
     "svg_debug_captures_active": [],
 }
 # fp16-storage twins of the 16-bit operator hooks (svg_op_<name>_f16: same arguments)
-for _n in ("gemm", "conv3x3", "conv3x3_gn", "conv3x3_mx", "gemm_lnstats", "gemm_cat", "ff_fused", "xattn_fused", "quant_mx", "gemm_fp8", "groupnorm", "layernorm",
+for _n in ("gemm", "gemm_ex", "conv3x3", "conv3x3_gn", "conv3x3_mx", "gemm_lnstats", "gemm_cat", "ff_fused", "xattn_fused", "quant_mx", "gemm_fp8", "groupnorm", "layernorm",
            "attention", "conv3x3_f32s", "groupnorm_f32"):
     SIGNATURES["svg_op_%s_f16" % _n] = SIGNATURES["svg_op_" + _n]
 SIGNATURES["svg_model_dtype"] = [_vp, _i]

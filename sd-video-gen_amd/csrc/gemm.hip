@@ -511,6 +511,14 @@ void launch_gemm(svg_ctx* ctx, const GemmArgs& g, hipStream_t s, int prof_kind) 
   if (g.out_f32 == 2)
     SVG_CHECK(g.act == ACT_NONE && !(g.residual && g.residual_f32) && !g.ln_rs && !g.A2, "gemm: the f32 stream takes no activation, LayerNorm fold, "
               "second A source or two residuals");
+  // epilogue operands that no kernel indexes by batch: refused rather than read as batch 0's ("GEMM epilogue contract")
+  if (g.batch > 1) {
+    SVG_CHECK(!g.bias_bn, "gemm: the per-sample bias (bias_bn) is indexed by row, not by batch: fold the batch into M (batch %d)", g.batch);
+    SVG_CHECK(!g.ln_rs || g.ln_swapped, "gemm: the LayerNorm statistics of a normal fold are per row, not per batch (batch %d)", g.batch);
+    SVG_CHECK(!g.ln_rs || g.sA == 0, "gemm: a swapped LayerNorm fold has one row-sum vector: A must be shared by the batch (sA %lld)", (long long)g.sA);
+  }
+  SVG_CHECK(!(g.bias_zs && g.act == ACT_GEGLU), "gemm: the GEGLU epilogue takes one bias for every batch (bias_zs %lld)", (long long)g.bias_zs);
+  if (g.vt_out) SVG_CHECK(g.vt_rows > 0 && g.M % g.vt_rows == 0, "gemm: the V^T write needs whole samples (M %d, vt_rows %d)", g.M, g.vt_rows);
   if (!SVG_LAUNCHING(ctx)) return;
   GemmArgs a = g;
   static const int dbg_env = getenv("SVG_GEMM_DBG") ? atoi(getenv("SVG_GEMM_DBG")) : 0;
@@ -528,9 +536,11 @@ void launch_gemm(svg_ctx* ctx, const GemmArgs& g, hipStream_t s, int prof_kind) 
   }
   // algorithmic bytes: every operand once (a conv reads its image once, not once per tap)
   const double a_elems = g.amode == A_DENSE ? (double)g.M * g.K : (double)(g.M / (g.Ho * g.Wo)) * g.H * g.W * g.Cin;
+  const GemmPath path = gemm_describe(a);
   char tag[160] = "";
   if (ctx->prof_detail) {
-    const char* kern = conv_halo_supported(a) ? "halo" : (gemm_ws_supported(a) ? "ws" : (gemm_pp_supported(a) ? "pp" : "igemm"));
+    static const char* const kern_name[] = {"igemm", "halo", "pp", "ws"};
+    const char* kern = kern_name[path.family];
     if (g.amode == A_DENSE)
       snprintf(tag, sizeof(tag), "M%d_N%d_K%d_b%d_act%d_res%d_ln%d_sk%d_%s", g.M, g.N, g.K, g.batch, g.act, g.residual ? 1 : 0, g.ln_rs ? 1 : 0, a.splitk, kern);
     else
@@ -538,16 +548,16 @@ void launch_gemm(svg_ctx* ctx, const GemmArgs& g, hipStream_t s, int prof_kind) 
   }
   ProfScope ps(ctx, prof_kind, s, 2.0 * g.M * (double)g.N * g.K * g.batch,
                2.0 * (a_elems + (double)g.N * g.K + (double)g.M * g.N) * g.batch, tag);
-  if (conv_halo_supported(a)) {
+  if (path.family == GF_HALO) {
     // 16 x 16 pixel blocks x channel tiles; splitk partitions the 64-channel chunks
-    const int blocks = (a.M / 256) * cdiv(a.N, conv_halo_bn(a));
+    const int blocks = (a.M / 256) * cdiv(a.N, path.bn);
     launch_conv_halo(a, dim3(blocks, 1, a.splitk), s);
-  } else if (gemm_ws_supported(a)) {
+  } else if (path.family == GF_WS) {
     launch_gemm_ws(ctx, a, s);
-  } else if (gemm_pp_supported(a)) {
+  } else if (path.family == GF_PP) {
     launch_gemm_pp(a, s);
   } else {
-    const int bn = pick_bn(a);
+    const int bn = path.bn;
     const int tiles = cdiv(a.M, BM) * cdiv(a.N, bn);
     dim3 grid(tiles, a.batch, a.splitk);
     switch (bn) {
@@ -597,12 +607,24 @@ static int plan_splitk(const GemmArgs& g) {
 
 bool gemm_fused_qkv_supported(const GemmArgs& g) { return g.vt_out != nullptr && gemm_ws_supported(g); }
 
-void gemm_auto(svg_ctx* ctx, GemmArgs g, hipStream_t s, int prof_kind) {
+// the dispatch order of launch_gemm
+GemmPath gemm_describe(const GemmArgs& g) {
+  GemmPath p;
+  p.splitk = std::max(1, g.splitk);
+  if (conv_halo_supported(g)) { p.family = GF_HALO; p.bn = conv_halo_bn(g); }
+  else if (gemm_ws_supported(g)) { p.family = GF_WS; p.bn = g.N / gemm_ws_groups(g); }
+  else if (gemm_pp_supported(g)) { p.family = GF_PP; p.bn = gemm_pp_bn(g); }
+  else { p.family = GF_IGEMM; p.bn = pick_bn(g); }
+  return p;
+}
+
+void gemm_auto(svg_ctx* ctx, GemmArgs g, hipStream_t s, int prof_kind, GemmPath* path) {
   if (g.n_valid <= 0) g.n_valid = g.N;
   SVG_CHECK(!g.vt_out || gemm_ws_supported(g), "gemm: a fused q | k | V^T problem (vt_out) needs the weight-stationary kernel (ask gemm_fused_qkv_supported)");
   g.splitk = 1;
   const int sk = plan_splitk(g);
   g.splitk = sk;
+  if (path) *path = gemm_describe(g);
   if (sk > 1) {
     SVG_CHECK(!g.gn_part, "gemm: GroupNorm statistics cannot be emitted by a split-K launch (ask gemm_emits_gn first)");
     ctx->arena.push();

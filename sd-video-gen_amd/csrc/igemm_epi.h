@@ -122,13 +122,15 @@ __device__ __forceinline__ void ln_fold_tile(const GemmArgs& g, int z, int mr, i
 }
 
 // (the kernels fold LayerNorm into their accumulators with ln_fold_tile before calling this; the split-K reduce with ln_fold)
+// bias of batch z at bias + z * bias_zs, as epi_tile reads it
 __device__ __forceinline__ f32x4 epi_value(const GemmArgs& g, int z, int m, int n, f32x4 v) {
   if (g.bias) {
+    const float* bias_z = g.bias + (int64_t)z * g.bias_zs;
     if (g.bias_row) {
-      float b = g.bias[m];
+      float b = bias_z[m];
       v += b;
     } else {
-      f32x4 b = *(const f32x4*)(g.bias + n);
+      f32x4 b = *(const f32x4*)(bias_z + n);
       v += b;
     }
   }

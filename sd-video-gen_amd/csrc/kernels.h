@@ -128,8 +128,13 @@ void xattn_fused(svg_ctx* ctx, const h16* X, int ldx, const h16* R, int ldr, con
 void pack_ff2_perm(const float* w, h16* out, int N, int K, hipStream_t s);
 void ff_fused(svg_ctx* ctx, const h16* X, int ldx, const h16* W1, const float* b1, const float* s1, const float* rs, const float* rm,
               const h16* W2p, const float* b2, const h16* residual, int ldr, h16* out, int ldo, int M, hipStream_t s);
-// picks split-K from the shape, allocates slabs from the arena, launches
-void gemm_auto(svg_ctx* ctx, GemmArgs g, hipStream_t s, int prof_kind);
+// which kernel a launch of g runs: family, column tile (gemm_ws: columns per group) and split-K.  launch_gemm dispatches on it and
+// tags its profile entries with it; gemm_auto reports it (the test hook svg_op_gemm_ex returns it).  g as launched: splitk planned.
+enum GemmFamily { GF_IGEMM = 0, GF_HALO = 1, GF_PP = 2, GF_WS = 3 };
+struct GemmPath { int family = GF_IGEMM, bn = 0, splitk = 1; };
+GemmPath gemm_describe(const GemmArgs& g);
+// picks split-K from the shape, allocates slabs from the arena, launches; *path (optional): gemm_describe of what was launched
+void gemm_auto(svg_ctx* ctx, GemmArgs g, hipStream_t s, int prof_kind, GemmPath* path = nullptr);
 // a GemmArgs with vt_out set can only be served by the weight-stationary kernel: ask before launching
 bool gemm_fused_qkv_supported(const GemmArgs& g);
 

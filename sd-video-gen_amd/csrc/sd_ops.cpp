@@ -197,6 +197,28 @@ int SVG_OP(svg_op_groupnorm_f32)(svg_ctx* ctx, const float* x, const float* gamm
   API_END(ctx)
 }
 
+// the whole GEMM epilogue contract on caller buffers (svg_hip.h: svg_gemm_desc): the descriptor goes into GemmArgs field by field and
+// through gemm_auto as the models call it; path = {family, column tile, split-K} of what gemm_auto launched.  Test hook.
+int SVG_OP(svg_op_gemm_ex)(svg_ctx* ctx, const svg_gemm_desc* d, int* path, void* stream) {
+  API_BEGIN
+  SVG_CHECK(d != nullptr, "gemm_ex: no descriptor");
+  GemmPath p;
+  run_planned(ctx, [&]() {
+    GemmArgs g;
+    g.amode = d->amode; g.H = d->H; g.W = d->W; g.Cin = d->Cin; g.Ho = d->Ho; g.Wo = d->Wo;
+    g.A = (const h16*)d->A; g.lda = d->lda; g.Wt = (const h16*)d->Wt; g.ldb = d->ldb; g.n_valid = d->n_valid;
+    g.C = d->C; g.ldc = d->ldc; g.M = d->M; g.N = d->N; g.K = d->K; g.batch = d->batch; g.sA = d->sA; g.sB = d->sB; g.sC = d->sC;
+    g.alpha = d->alpha; g.bias = d->bias; g.bias_row = d->bias_row; g.bias_zs = d->bias_zs;
+    g.bias_bn = d->bias_bn; g.rows_per_batch = d->rows_per_batch; g.bias_bn_ld = d->bias_bn_ld;
+    g.residual = (const h16*)d->residual; g.ldr = d->ldr; g.act = d->act; g.out_f32 = d->out_f32;
+    g.ln_rs = d->ln_rs; g.ln_rm = d->ln_rm; g.ln_s = d->ln_s; g.ln_swapped = d->ln_swapped; g.ln_zstride = d->ln_zstride;
+    g.vt_out = (h16*)d->vt_out; g.vt_n0 = d->vt_n0; g.vt_rows = d->vt_rows; g.vt_ld = d->vt_ld; g.vt_bs = d->vt_bs;
+    gemm_auto(ctx, g, (hipStream_t)stream, g.amode == A_DENSE ? PK_GEMM : PK_CONV3, &p);
+  });
+  if (path) { path[0] = p.family; path[1] = p.bn; path[2] = p.splitk; }
+  API_END(ctx)
+}
+
 // C[M,N] = [A | A2][M, K] * W[N,K]^T + bias: dense GEMM whose A operand is the channel concat of two tensors (A: k_split columns)
 int SVG_OP(svg_op_gemm_cat)(svg_ctx* ctx, const uint16_t* A, const uint16_t* A2, const uint16_t* W, const float* bias, uint16_t* C, int M, int N,
                     int K, int k_split, void* stream) {
