@@ -333,6 +333,34 @@ int svg_op_attention(svg_ctx* ctx, const uint16_t* q, const uint16_t* k, const u
                      uint16_t* out, int B, int heads, int Sq, int Skv, int d, int ldq, int ldk,
                      int ldvt, int ldo, int64_t q_bstride, int64_t k_bstride, int64_t vt_bstride,
                      int64_t o_bstride, float scale, void* stream);
+/* svg_op_attention on a full descriptor, optionally forced onto one kernel instantiation (test hook).  Fields as svg_op_attention
+ * (qb / kb / vtb / ob: batch strides in elements; kb = vtb = 0 shares one context between all samples).  d: 8, 16, 32, 40, 64, 80
+ * or 160; strides multiples of 8 elements (ldo: of 4); ldvt >= Skv rounded up to 8.
+ * V^T pad contract: the kernels stage V^T in whole 8-key chunks, so the pad keys Skv .. ceil8(Skv) - 1 of every V^T row are read and
+ * multiplied by P = 0; they must be finite (0 * Inf or NaN is NaN).  Columns from ceil8(Skv) on are never read.  The models write
+ * finite values there: the V^T projection masks the padded token rows of its B operand (n_valid), so they hold the bias.
+ * force = 0: the library's own choice (SVG_ATTN_QB / NST / BC / HV / DMA and Sq >= 512, as svg_op_attention).  force = 1: exactly
+ * {kernel, qblocks, nst, bc, hv}: kernel 0 = attn_kernel<d, qblocks (1, or 2 for d <= 64), nst (LDS stages: 1, or 2 without bc and
+ * d != 160), bc (bias columns: d = 8 or 40, nst 1), hv (V^T read ahead: bc and qblocks 2)>, kernel 1 = attn_dma40_kernel (d = 40,
+ * given as qblocks 2, nst 3, bc 1, hv 1).  A forced variant that is not instantiated for d, an unsupported d, a short ldvt or a
+ * misaligned stride return an error without launching anything.  path (int[6], or NULL) receives what ran: {kernel, d, qblocks,
+ * nst, bc, hv}. */
+typedef struct svg_attn_desc {
+  const uint16_t *q, *k, *vt;
+  uint16_t* out;
+  int B, heads, Sq, Skv, d;
+  int ldq, ldk, ldvt, ldo;
+  int64_t qb, kb, vtb, ob;
+  float scale;
+  int force, kernel, qblocks, nst, bc, hv;
+} svg_attn_desc;
+int svg_op_attention_ex(svg_ctx* ctx, const svg_attn_desc* desc, int* path, void* stream);
+/* The VAE mid block's fused single-head attention (d = C = 512) whatever SVG_VAE_ATTN_FUSED says (test hook): per sample b,
+ * out[b] = softmax(q[b] k[b]^T / sqrt(C)) v[b] over S keys.  q, k: rows of stride ldqk (the model passes one [q | k] buffer,
+ * ldqk = 2C), sample stride qkb; vt (B, C, ldvt) = V transposed, sample stride vtb; out rows of stride ldo, sample stride ob.
+ * S % 64 != 0, C != 512, strides not multiples of 8 (ldo: 4), ldqk < C, ldvt < S or ldo < C return an error. */
+int svg_op_vae_attention(svg_ctx* ctx, const uint16_t* q, const uint16_t* k, int ldqk, int64_t qkb, const uint16_t* vt, int ldvt,
+                         int64_t vtb, uint16_t* out, int ldo, int64_t ob, int B, int S, int C, void* stream);
 /* fp16-storage twins of the hooks above (identical contracts; 16-bit buffers hold IEEE half) */
 int svg_op_gemm_f16(svg_ctx* ctx, const uint16_t* A, const uint16_t* W, const float* bias, const uint16_t* residual, void* C, int M,
                     int N, int K, int act, int out_f32, void* stream);
@@ -370,6 +398,9 @@ int svg_op_layernorm_f16(svg_ctx* ctx, const uint16_t* x, const float* gamma, co
 int svg_op_attention_f16(svg_ctx* ctx, const uint16_t* q, const uint16_t* k, const uint16_t* vt, uint16_t* out, int B, int heads,
                          int Sq, int Skv, int d, int ldq, int ldk, int ldvt, int ldo, int64_t q_bstride, int64_t k_bstride,
                          int64_t vt_bstride, int64_t o_bstride, float scale, void* stream);
+int svg_op_attention_ex_f16(svg_ctx* ctx, const svg_attn_desc* desc, int* path, void* stream);
+int svg_op_vae_attention_f16(svg_ctx* ctx, const uint16_t* q, const uint16_t* k, int ldqk, int64_t qkb, const uint16_t* vt, int ldvt,
+                             int64_t vtb, uint16_t* out, int ldo, int64_t ob, int B, int S, int C, void* stream);
 /* f32 skinny GEMM of the latent Transformer: Y[M,N] = X[M,K] * W[N,K]^T + bias (relu_in: X:=max(X,0)). */
 int svg_op_xf_gemm(svg_ctx* ctx, const float* X, const float* W, const float* bias, float* Y,
                    int M, int N, int K, int relu_in, void* stream);

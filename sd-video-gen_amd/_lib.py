@@ -42,6 +42,15 @@ class GemmDesc(C.Structure):
                 ("vt_out", _vp), ("vt_n0", _i), ("vt_rows", _i), ("vt_ld", _i), ("vt_bs", _i64)]
 
 
+class AttnDesc(C.Structure):
+    """struct svg_attn_desc (include/svg_hip.h): the attention launch descriptor of svg_op_attention_ex."""
+    _fields_ = [("q", _vp), ("k", _vp), ("vt", _vp), ("out", _vp),
+                ("B", _i), ("heads", _i), ("Sq", _i), ("Skv", _i), ("d", _i),
+                ("ldq", _i), ("ldk", _i), ("ldvt", _i), ("ldo", _i),
+                ("qb", _i64), ("kb", _i64), ("vtb", _i64), ("ob", _i64),
+                ("scale", _f), ("force", _i), ("kernel", _i), ("qblocks", _i), ("nst", _i), ("bc", _i), ("hv", _i)]
+
+
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/svg_hip.h
 SIGNATURES = {
     "svg_create": [_i, C.POINTER(_vp)],
@@ -90,6 +99,8 @@ SIGNATURES = {
     "svg_op_groupnorm_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "svg_op_layernorm": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp],
     "svg_op_attention": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _f, _vp],
+    "svg_op_attention_ex": [_vp, C.POINTER(AttnDesc), C.POINTER(_i), _vp],
+    "svg_op_vae_attention": [_vp, _vp, _vp, _i, _i64, _vp, _i, _i64, _vp, _i, _i64, _i, _i, _i, _vp],
     "svg_op_xf_gemm": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "svg_prof_enable": [_vp, _i],
     "svg_prof_reset": [_vp],
@@ -104,7 +115,7 @@ SIGNATURES = {
 }
 # fp16-storage twins of the 16-bit operator hooks (svg_op_<name>_f16: same arguments)
 for _n in ("gemm", "gemm_ex", "conv3x3", "conv3x3_gn", "conv3x3_mx", "gemm_lnstats", "gemm_cat", "ff_fused", "xattn_fused", "quant_mx", "gemm_fp8", "groupnorm", "layernorm",
-           "attention", "conv3x3_f32s", "groupnorm_f32"):
+           "attention", "attention_ex", "vae_attention", "conv3x3_f32s", "groupnorm_f32"):
     SIGNATURES["svg_op_%s_f16" % _n] = SIGNATURES["svg_op_" + _n]
 SIGNATURES["svg_model_dtype"] = [_vp, _i]
 _RESTYPES = {"svg_destroy": None, "svg_env_refresh": None, "svg_model_dtype": C.c_char_p, "svg_last_error": C.c_char_p, "svg_version": C.c_char_p,

@@ -641,57 +641,110 @@ __global__ void __launch_bounds__(256) attn_dma40_kernel(const AttnArgs a) {
   }
 }
 
+// one launch of the instantiation `p` names (attention_describe has checked that it exists for this d)
 template <int D>
-void launch(const AttnArgs& a, hipStream_t s) {
+void launch(const AttnPath& p, const AttnArgs& a, hipStream_t s) {
+  constexpr bool CAN_BC = (D % 16) == 8;        // three spare pad columns in lane-half 1 of the last k-step (d = 8, 40)
+  if constexpr (D == 40) {
+    if (p.kernel == ATTN_DMA40) {
+      hipLaunchKernelGGL(attn_dma40_kernel, dim3(cdiv(a.Sq, 256) * a.heads * a.B), dim3(256), 0, s, a);
+      return;
+    }
+  }
+  if constexpr (D <= 64) {
+    if (p.qb == 2) {
+      const dim3 grid(cdiv(a.Sq, 256) * a.heads * a.B);
+      if constexpr (CAN_BC) {
+        if (p.bc && p.hv) { hipLaunchKernelGGL((attn_kernel<D, 2, 1, true, true>), grid, dim3(256), 0, s, a); return; }
+        if (p.bc) { hipLaunchKernelGGL((attn_kernel<D, 2, 1, true>), grid, dim3(256), 0, s, a); return; }
+      }
+      if (p.nst == 2) hipLaunchKernelGGL((attn_kernel<D, 2, 2, false>), grid, dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((attn_kernel<D, 2, 1, false>), grid, dim3(256), 0, s, a);
+      return;
+    }
+  }
+  const dim3 grid(cdiv(a.Sq, 128) * a.heads * a.B);
+  if constexpr (CAN_BC) {
+    if (p.bc) { hipLaunchKernelGGL((attn_kernel<D, 1, 1, true>), grid, dim3(256), 0, s, a); return; }
+  }
+  if constexpr (D != 160) {   // d = 160 has one LDS stage whatever is asked (attn_kernel's NST)
+    if (p.nst == 2) { hipLaunchKernelGGL((attn_kernel<D, 1, 2, false>), grid, dim3(256), 0, s, a); return; }
+  }
+  hipLaunchKernelGGL((attn_kernel<D, 1, 1, false>), grid, dim3(256), 0, s, a);
+}
+
+// the LDS stages attn_kernel<D, ., NSTW = 2, false> really has: two when they fit the 64 KiB of static LDS (its NST)
+int attn_stages(int d) {
+  const int dk = (d + 15) / 16 * 16, dvt = (d + 31) / 32;
+  const int stage = KVT * (dk * 2 + 16) + dvt * 32 * VROW;
+  return 2 * stage <= 65536 ? 2 : 1;
+}
+
+bool attn_d_supported(int d) {
+  switch (d) { case 8: case 16: case 32: case 40: case 64: case 80: case 160: return true; default: return false; }
+}
+
+// every instantiation attention() can launch for head dim d
+bool attn_path_exists(const AttnPath& p) {
+  const int d = p.d;
+  if (!attn_d_supported(d)) return false;
+  if (p.kernel == ATTN_DMA40) return d == 40 && p.qb == 2 && p.nst == 3 && p.bc == 1 && p.hv == 1;
+  if (p.kernel != ATTN_REG) return false;
+  if (p.qb != 1 && !(p.qb == 2 && d <= 64)) return false;
+  if (p.bc) return (d % 16) == 8 && p.bc == 1 && p.nst == 1 && (p.hv == 0 || (p.hv == 1 && p.qb == 2));
+  return p.hv == 0 && (p.nst == 1 || (p.nst == 2 && attn_stages(d) == 2));
+}
+
+}  // namespace
+
+AttnPath attention_describe(const AttnArgs& a, const AttnPath* force) {
+  SVG_CHECK(attn_d_supported(a.d), "attention: head dim %d unsupported (instantiated: 8, 16, 32, 40, 64, 80, 160)", a.d);
+  if (force) {
+    SVG_CHECK(force->d == a.d && attn_path_exists(*force), "attention: no instantiation {kernel %d, d %d, QB %d, NST %d, BC %d, HV %d} for d = %d",
+              force->kernel, force->d, force->qb, force->nst, force->bc, force->hv, a.d);
+    return *force;
+  }
   // Two query blocks per wave (QB = 2) when the registers allow two waves per SIMD (d <= 64: 222 VGPRs):
   // 0.67 vs 0.73 ms at 16 x 8 x 4096^2 x 40.  SVG_ATTN_QB=1 forces the single-block form.
   static const int nst_env = getenv("SVG_ATTN_NST") ? atoi(getenv("SVG_ATTN_NST")) : 1;   // same-box A/B: one stage + two barriers is 1-2 % faster than two stages + one barrier
   static const int qb_env = getenv("SVG_ATTN_QB") ? atoi(getenv("SVG_ATTN_QB")) : 2;
   static const int bc_env = getenv("SVG_ATTN_BC") ? atoi(getenv("SVG_ATTN_BC")) : 1;
   static const int hv_env = getenv("SVG_ATTN_HV") ? atoi(getenv("SVG_ATTN_HV")) : 1;   // same-box A/B at 28 x 8 x 4096^2 x 40: 1.006 vs 1.026 ms
-  constexpr int QB = (D <= 64) ? 2 : 1;
-  constexpr bool CAN_BC = (D % 16) == 8;        // three spare pad columns in lane-half 1 of the last k-step (d = 8, 40)
   static const int dma_env = getenv("SVG_ATTN_DMA") ? atoi(getenv("SVG_ATTN_DMA")) : 1;
-  if (D == 40 && dma_env && qb_env == 2 && bc_env && a.Sq >= 512) {
-    hipLaunchKernelGGL(attn_dma40_kernel, dim3(cdiv(a.Sq, 256) * a.heads * a.B), dim3(256), 0, s, a);
-    return;
+  const int d = a.d;
+  const bool can_bc = (d % 16) == 8;
+  AttnPath p;
+  p.d = d;
+  if (d == 40 && dma_env && qb_env == 2 && bc_env && a.Sq >= 512) {
+    p.kernel = ATTN_DMA40; p.qb = 2; p.nst = 3; p.bc = 1; p.hv = 1;
+    return p;
   }
-  if (QB == 2 && qb_env == 2 && a.Sq >= 512) {
-    dim3 grid(cdiv(a.Sq, 256) * a.heads * a.B);
-    if (CAN_BC && bc_env && hv_env) hipLaunchKernelGGL((attn_kernel<D, QB, 1, CAN_BC, true>), grid, dim3(256), 0, s, a);
-    else if (CAN_BC && bc_env) hipLaunchKernelGGL((attn_kernel<D, QB, 1, CAN_BC>), grid, dim3(256), 0, s, a);
-    else if (nst_env == 2) hipLaunchKernelGGL((attn_kernel<D, QB, 2, false>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((attn_kernel<D, QB, 1, false>), grid, dim3(256), 0, s, a);
-  } else {
-    dim3 grid(cdiv(a.Sq, 128) * a.heads * a.B);
-    if (CAN_BC && bc_env) hipLaunchKernelGGL((attn_kernel<D, 1, 1, CAN_BC>), grid, dim3(256), 0, s, a);
-    else if (nst_env == 2) hipLaunchKernelGGL((attn_kernel<D, 1, 2, false>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((attn_kernel<D, 1, 1, false>), grid, dim3(256), 0, s, a);
-  }
+  p.qb = (d <= 64 && qb_env == 2 && a.Sq >= 512) ? 2 : 1;
+  if (can_bc && bc_env) { p.bc = 1; p.hv = (p.qb == 2 && hv_env) ? 1 : 0; }
+  else if (nst_env == 2) p.nst = attn_stages(d);
+  return p;
 }
 
-}  // namespace
-
-void attention(svg_ctx* ctx, const AttnArgs& a, hipStream_t s) {
+void attention(svg_ctx* ctx, const AttnArgs& a, hipStream_t s, const AttnPath* force, AttnPath* ran) {
   SVG_CHECK(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldvt % 8 == 0 && a.ldo % 4 == 0, "attention: strides must be 16-byte aligned");
   SVG_CHECK(a.ldvt >= (a.Skv + 7) / 8 * 8, "attention: V^T rows must be padded to a multiple of 8 keys");
   SVG_CHECK(a.Skv > 0 && a.Sq > 0, "attention: empty");
-  if (!SVG_LAUNCHING(ctx)) {
-    switch (a.d) { case 8: case 16: case 32: case 40: case 64: case 80: case 160: return; default: break; }
-    SVG_CHECK(false, "attention: head dim %d unsupported (instantiated: 8, 16, 32, 40, 64, 80, 160)", a.d);
-  }
-  char tag[96];
-  snprintf(tag, sizeof(tag), "B%d_h%d_Sq%d_Skv%d_d%d", a.B, a.heads, a.Sq, a.Skv, a.d);
+  const AttnPath p = attention_describe(a, force);
+  if (ran) *ran = p;
+  if (!SVG_LAUNCHING(ctx)) return;
+  char tag[128];
+  if (p.kernel == ATTN_DMA40) snprintf(tag, sizeof(tag), "B%d_h%d_Sq%d_Skv%d_d%d_dma40", a.B, a.heads, a.Sq, a.Skv, a.d);
+  else snprintf(tag, sizeof(tag), "B%d_h%d_Sq%d_Skv%d_d%d_qb%d_nst%d_bc%d_hv%d", a.B, a.heads, a.Sq, a.Skv, a.d, p.qb, p.nst, p.bc, p.hv);
   ProfScope ps(ctx, PK_ATTN, s, 4.0 * a.B * a.heads * (double)a.Sq * a.Skv * a.d,
                2.0 * a.B * a.heads * ((double)a.Sq * a.d * 2 + (double)a.Skv * a.d * 2), tag);
   switch (a.d) {
-    case 8: launch<8>(a, s); break;
-    case 16: launch<16>(a, s); break;
-    case 32: launch<32>(a, s); break;
-    case 40: launch<40>(a, s); break;
-    case 64: launch<64>(a, s); break;
-    case 80: launch<80>(a, s); break;
-    case 160: launch<160>(a, s); break;
+    case 8: launch<8>(p, a, s); break;
+    case 16: launch<16>(p, a, s); break;
+    case 32: launch<32>(p, a, s); break;
+    case 40: launch<40>(p, a, s); break;
+    case 64: launch<64>(p, a, s); break;
+    case 80: launch<80>(p, a, s); break;
+    case 160: launch<160>(p, a, s); break;
     default: SVG_CHECK(false, "attention: head dim %d unsupported (instantiated: 8, 16, 32, 40, 64, 80, 160)", a.d);
   }
   check_launch("attention");

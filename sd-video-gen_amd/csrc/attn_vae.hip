@@ -200,7 +200,11 @@ bool vae_attention_supported(int S, int C, int ldqk, int ldvt, int ldo) {
   // through LDS, and 272 bytes of scratch per lane (the Q fragments spill).  It removes 7.5 GB of HBM traffic per frame group, but
   // the time is what the frame pays: SVG_VAE_ATTN_FUSED=1 selects it (cached; the tests toggle it and call svg_env_refresh).
   const int on = (int)svg_env_i64("SVG_VAE_ATTN_FUSED", 0);
-  return on && C == VA_D && S % VA_Q == 0 && S >= VA_Q && ldqk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0;
+  return on && vae_attention_shape_ok(S, C, ldqk, ldvt, ldo);
+}
+
+bool vae_attention_shape_ok(int S, int C, int ldqk, int ldvt, int ldo) {
+  return C == VA_D && S % VA_Q == 0 && S >= VA_Q && ldqk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0 && ldqk >= C && ldvt >= S && ldo >= C;
 }
 
 void vae_attn_init_device() {
@@ -210,7 +214,8 @@ void vae_attn_init_device() {
 // q, k: (B, S, ·) rows of stride ldqk (batch stride qkb); vt: (B, C, ·) V transposed, row stride ldvt; out (B, S, C) row stride ldo
 void vae_attention(svg_ctx* ctx, const h16* q, const h16* k, int ldqk, int64_t qkb, const h16* vt, int ldvt, int64_t vtb, h16* out, int ldo,
                    int64_t ob, int B, int S, int C, hipStream_t s) {
-  SVG_CHECK(vae_attention_supported(S, C, ldqk, ldvt, ldo), "vae_attention: S=%d C=%d unsupported", S, C);
+  SVG_CHECK(vae_attention_shape_ok(S, C, ldqk, ldvt, ldo), "vae_attention: S=%d C=%d (ldqk %d, ldvt %d, ldo %d) unsupported", S, C, ldqk,
+            ldvt, ldo);
   if (!SVG_LAUNCHING(ctx)) return;
   char tag[64];
   snprintf(tag, sizeof(tag), "B%d_h1_Sq%d_Skv%d_d%d_fused", B, S, S, C);

@@ -197,9 +197,20 @@ struct AttnArgs {
   int64_t qb, kb, vtb, ob;       // batch strides (elements)
   float scale;
 };
-void attention(svg_ctx* ctx, const AttnArgs& a, hipStream_t s);
-// single-head d = 512 attention of the VAE mid blocks, fused (attn_vae.hip): q, k rows of stride ldqk, vt = V transposed (B, C, ldvt)
+// the instantiation one attention() launch takes: attn_kernel<d, qb, nst, bc, hv> (nst: the LDS stages it really has) or
+// attn_dma40_kernel (reported as {ATTN_DMA40, 40, 2, 3, 1, 1}: two query blocks, a three-stage ring, bias columns, V^T read ahead)
+enum AttnKernel { ATTN_REG = 0, ATTN_DMA40 = 1 };
+struct AttnPath {
+  int kernel = ATTN_REG, d = 0, qb = 1, nst = 1, bc = 0, hv = 0;
+};
+// what attention(a) launches: the SVG_ATTN_QB / NST / BC / HV / DMA choice, or `force` when that names an instantiation that
+// exists for a.d (otherwise an error, as for an unsupported d)
+AttnPath attention_describe(const AttnArgs& a, const AttnPath* force = nullptr);
+void attention(svg_ctx* ctx, const AttnArgs& a, hipStream_t s, const AttnPath* force = nullptr, AttnPath* ran = nullptr);
+// single-head d = 512 attention of the VAE mid blocks, fused (attn_vae.hip): q, k rows of stride ldqk, vt = V transposed (B, C, ldvt).
+// vae_attention_supported: the model's choice (SVG_VAE_ATTN_FUSED=1 and a shape the kernel takes); vae_attention_shape_ok: the shape alone
 bool vae_attention_supported(int S, int C, int ldqk, int ldvt, int ldo);
+bool vae_attention_shape_ok(int S, int C, int ldqk, int ldvt, int ldo);
 void vae_attention(svg_ctx* ctx, const h16* q, const h16* k, int ldqk, int64_t qkb, const h16* vt, int ldvt, int64_t vtb, h16* out, int ldo,
                    int64_t ob, int B, int S, int C, hipStream_t s);
 void vae_attn_init_device();

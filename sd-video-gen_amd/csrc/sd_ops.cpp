@@ -402,4 +402,29 @@ int SVG_OP(svg_op_attention)(svg_ctx* ctx, const uint16_t* q, const uint16_t* k,
   API_END(ctx)
 }
 
+// attention on a full descriptor (svg_hip.h: svg_attn_desc), optionally forced onto one instantiation; path = {kernel, d, QB, NST,
+// BC, HV} of what ran.  Test hook.
+int SVG_OP(svg_op_attention_ex)(svg_ctx* ctx, const svg_attn_desc* d, int* path, void* stream) {
+  API_BEGIN
+  SVG_CHECK(d != nullptr, "attention_ex: no descriptor");
+  AttnArgs a;
+  a.q = (const h16*)d->q; a.k = (const h16*)d->k; a.vt = (const h16*)d->vt; a.out = (h16*)d->out;
+  a.B = d->B; a.heads = d->heads; a.Sq = d->Sq; a.Skv = d->Skv; a.d = d->d;
+  a.ldq = d->ldq; a.ldk = d->ldk; a.ldvt = d->ldvt; a.ldo = d->ldo; a.qb = d->qb; a.kb = d->kb; a.vtb = d->vtb; a.ob = d->ob;
+  a.scale = d->scale;
+  AttnPath f, p;
+  f.kernel = d->kernel; f.d = d->d; f.qb = d->qblocks; f.nst = d->nst; f.bc = d->bc; f.hv = d->hv;
+  attention(ctx, a, (hipStream_t)stream, d->force ? &f : nullptr, &p);
+  if (path) { path[0] = p.kernel; path[1] = p.d; path[2] = p.qb; path[3] = p.nst; path[4] = p.bc; path[5] = p.hv; }
+  API_END(ctx)
+}
+
+// the VAE mid block's fused single-head attention (attn_vae.hip), whatever SVG_VAE_ATTN_FUSED says.  Test hook.
+int SVG_OP(svg_op_vae_attention)(svg_ctx* ctx, const uint16_t* q, const uint16_t* k, int ldqk, int64_t qkb, const uint16_t* vt, int ldvt,
+                                 int64_t vtb, uint16_t* out, int ldo, int64_t ob, int B, int S, int C, void* stream) {
+  API_BEGIN
+  vae_attention(ctx, (const h16*)q, (const h16*)k, ldqk, qkb, (const h16*)vt, ldvt, vtb, (h16*)out, ldo, ob, B, S, C, (hipStream_t)stream);
+  API_END(ctx)
+}
+
 }  // extern "C"
