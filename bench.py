@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — generated frames/sec of the sampling hot path on N MI355X (one process per GPU).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what its headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line.  `--full`
+adds rank 0's optional passes after the headline, each a run of its own: `roofline` (an instrumented pass of one clip group),
+`cpu_baseline` (the CPU oracle) and `extras.fp8_same_box` (the workload again on MX-fp8 convs); none of them changes the headline.
 
 N>1 runs one process per GPU: either the caller launches them (`python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...`, RANK/LOCAL_RANK/WORLD_SIZE in the env) or, when WORLD_SIZE is not set, this script spawns
@@ -81,10 +85,13 @@ def parse():
     p.add_argument("--train", action="store_true",
                    help="SURVEY 8(f1): optimisation steps of the latent Transformer (trainers/trainer.py:141-165) instead of the sampling loop; "
                         "one step = forward in train mode + criterion + backward + Adam on the config's own batch")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-roofline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run rank 0's optional passes (roofline, cpu_baseline, extras.fp8_same_box): off by "
+                        "default, a plain run does only what the headline needs")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    p.add_argument("--no-roofline", action="store_true", help="with --full: skip the instrumented roofline pass")
     p.add_argument("--no-fp8-extra", action="store_true",
-                   help="skip extras.fp8_same_box (one step of the same workload with the MX-fp8 convs, rank 0, after the headline is computed)")
+                   help="with --full: skip extras.fp8_same_box (the same workload with the MX-fp8 convs, rank 0, after the headline is computed)")
     args = p.parse_args()
     if args.steps is None:
         args.steps = 20 if args.train else 2
@@ -103,6 +110,18 @@ def parse():
             setattr(args, k, wl[k])
     args.guidance, args.text = wl["guidance"], wl["text"]
     return args
+
+
+def optional_passes(args):
+    """The passes rank 0 runs after the headline, in this order.  Each takes a run of its own and none is needed for the headline, so
+    a plain run has none; --full turns them on and --no-roofline / --no-cpu-baseline / --no-fp8-extra drop single ones."""
+    if not args.full:
+        return []
+    if args.train:
+        return [] if args.no_cpu_baseline else ["cpu_baseline"]
+    fp8_extra = not args.no_denoise and args.dtype == "fp16" and not args.no_fp8_extra
+    return [name for name, on in (("roofline", not args.no_roofline), ("cpu_baseline", not args.no_cpu_baseline),
+                                  ("fp8_same_box", fp8_extra)) if on]
 
 
 def host_cores():
@@ -484,7 +503,7 @@ def train_bench(args, rank, local_rank, world, dist):
                         "algorithmic_bytes_per_step": step_bytes, "median_ms_per_step": med * 1e3, "mean_ms_per_step": dt / steps * 1e3,
                         "note": "median over per-step wall times (each step synchronises to read its loss); the mean includes this pool's "
                                 "periodic ~75 ms stalls of many-launch sequences (profiles/README.md)"}}
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and "cpu_baseline" in optional_passes(args):
         from oracle import train_oracle as TR
         torch.set_num_threads(host_cores())
         sd = TR.leaf_state({k: v.detach().cpu() for k, v in model.state_dict().items()})
@@ -681,12 +700,13 @@ def main():
                 line.setdefault(into, {})[key] = err
             print("bench.py: optional pass %r failed: %s" % (key, err["error"]), file=sys.stderr)
 
+    passes = optional_passes(args) if rank == 0 else []
     try:
-        if rank == 0 and not args.no_roofline:
+        if "roofline" in passes:
             guarded("roofline", lambda: roofline_pass(args, sd_utils, step, denoise, C, model))
-        if rank == 0 and not args.no_cpu_baseline:
+        if "cpu_baseline" in passes:
             guarded("cpu_baseline", lambda: {"cpu_baseline": cpu_baseline(args.config, args.start_step, denoise, guidance, args.text)})
-        if rank == 0 and denoise and args.dtype == "fp16" and not args.no_fp8_extra:
+        if "fp8_same_box" in passes:
             if os.environ.get("SVG_BENCH_FAIL_EXTRA"):      # test hook (tests/test_host_cpu.py): the failure path of an optional pass
                 guarded("fp8_same_box", lambda: (_ for _ in ()).throw(RuntimeError("SVG_BENCH_FAIL_EXTRA")), into="extras")
             else:

@@ -255,13 +255,13 @@ def test_bench_spawns_its_ranks():
     """`python bench.py --gpus 2` with no launcher: the script starts torch.distributed.run itself (before any GPU call in
     the parent) and rank 0 prints ONE JSON line with n_gpus 2.  Both ranks share the box's single GPU here (gloo + device
     override: the rehearsal knobs), tiny step (1 clip per rank, last DDIM step only).  An optional pass that FAILS on rank 0 after
-    the headline (the $SVG_BENCH_FAIL_EXTRA hook stands in for extras.fp8_same_box raising, as in BENCH_r05) still leaves the
-    line and exit code 0, with the failure recorded under its own key."""
+    the headline under --full (the $SVG_BENCH_FAIL_EXTRA hook stands in for extras.fp8_same_box raising, as in BENCH_r05) still leaves
+    the line and exit code 0, with the failure recorded under its own key."""
     env = dict(os.environ, SVG_DIST_BACKEND="gloo", SVG_DEVICE_OVERRIDE="0", SVG_BENCH_FAIL_EXTRA="1")
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--clips", "1",
-                        "--streams", "1", "--start_step", "49", "--no-cpu-baseline", "--no-roofline"],
+                        "--streams", "1", "--start_step", "49", "--full", "--no-cpu-baseline", "--no-roofline"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -269,6 +269,26 @@ def test_bench_spawns_its_ranks():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["config"]["global_clips"] == 2 and d["value"] > 0 and d["scaling"] == "weak"
     assert "SVG_BENCH_FAIL_EXTRA" in d["extras"]["fp8_same_box"]["error"]
+
+
+def test_plain_bench_runs_no_optional_pass(tmp_path):
+    """Without --full a run does only what its headline needs: the line has the headline's fields and none of the optional passes'
+    (the $SVG_BENCH_FAIL_EXTRA hook would record an error under extras if the fp8 pass were entered), and --dump-outputs still writes the
+    last step's latents."""
+    env = dict(os.environ, SVG_BENCH_FAIL_EXTRA="1")
+    for k in ("WORLD_SIZE", "RANK", "SVG_BENCH_DTYPE"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--clips", "1",
+                        "--streams", "1", "--start_step", "49", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["value"] > 0 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "fp16"
+    assert d["ms_per_step"] > 0 and d["steps"] == 1 and d["warmup"] == 0
+    assert not {"roofline", "families", "cpu_baseline", "extras"} & set(d)
+    assert os.listdir(tmp_path) == ["all_latents.npy"]
 
 
 def test_rccl_gathers_device_tensors_in_a_one_rank_group():

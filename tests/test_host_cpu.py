@@ -312,6 +312,25 @@ def test_bench_refuses_mismatched_world_size():
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
 
 
+def test_bench_optional_passes_only_under_full(monkeypatch):
+    """A plain bench run runs none of rank 0's optional passes; --full runs each that applies, and the --no-* flags drop single ones."""
+    import bench
+    monkeypatch.delenv("SVG_BENCH_DTYPE", raising=False)
+
+    def passes(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + list(argv))
+        return bench.optional_passes(bench.parse())
+    for argv in ((), ("--train",), ("--no-denoise",), ("--dtype", "bf16"), ("--workload", "cfg4"), ("--gpus", "2")):
+        assert passes(*argv) == []
+    assert passes("--full") == ["roofline", "cpu_baseline", "fp8_same_box"]
+    assert passes("--full", "--gpus", "2") == ["roofline", "cpu_baseline", "fp8_same_box"]
+    assert passes("--full", "--no-roofline", "--no-cpu-baseline") == ["fp8_same_box"]
+    assert passes("--full", "--no-fp8-extra") == ["roofline", "cpu_baseline"]
+    assert passes("--full", "--dtype", "bf16") == passes("--full", "--no-denoise") == ["roofline", "cpu_baseline"]
+    assert passes("--full", "--train") == ["cpu_baseline"]
+    assert passes("--full", "--train", "--no-cpu-baseline") == []
+
+
 def test_bench_steps_and_dump_outputs(tmp_path, monkeypatch):
     """--steps is the number of timed steps on every path (--train has its own default, no minimum); --dump-outputs writes float32 /
     float64 .npy files, under 64 MB in all, an output too large for that as the same seeded sample of its elements every time."""
