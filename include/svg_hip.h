@@ -19,6 +19,8 @@
  *   svg_ddim_loop             utils/sd_utils.py:222-267 (gen_i2i_latents: DDIMScheduler(0.00085,
  *                             0.012,'scaled_linear',1000), set_timesteps, add_noise, CFG combine,
  *                             scheduler.step) — the hot loop
+ *   svg_sample_loop           the same loop with a DPM-Solver++(2M) update in place of scheduler.step
+ *                             (an addition: the reference has only DDIM here)
  *   svg_clip_text_forward     utils/sd_utils.py:84,91 (self.text_encoder(input_ids)[0]: transformers CLIPTextModel of
  *                             'openai/clip-vit-large-patch14', last_hidden_state) — tokenisation stays on the host
  *   svg_resize_nearest_u8     prediction/predict.py:158,178 (F.interpolate on uint8, mode nearest)
@@ -202,6 +204,31 @@ int svg_ddim_loop(svg_ctx* ctx, float* z, int N, int h, int w, const float* text
 /* one scheduler step on caller data (x, eps -> prev); t = timestep value, t_prev = t - 1000/num_steps */
 int svg_ddim_step(svg_ctx* ctx, const float* x, const float* eps, float* prev, int64_t n, int t,
                   int t_prev, void* stream);
+
+/* Samplers of svg_sample_loop. */
+#define SVG_SAMPLER_DDIM 0      /* the update of svg_ddim_loop */
+#define SVG_SAMPLER_DPMPP_2M 1  /* DPM-Solver++(2M) */
+/* The img2img loop of svg_ddim_loop under the update rule `sampler`: the same arguments, contract, timesteps
+ * t_i = (num_steps-1-i)*1000/num_steps, add_noise at t_start, CFG combine, history and step graph.
+ * SVG_SAMPLER_DDIM is exactly svg_ddim_loop.  SVG_SAMPLER_DPMPP_2M is the update of diffusers'
+ * DPMSolverMultistepScheduler(algorithm_type="dpmsolver++", solver_order=2, solver_type="midpoint",
+ * lower_order_final=True, thresholding=False) on this timestep set: with abar from the DDIM schedule
+ * (abar = 1 below t = 0), a = sqrt(abar), sig = sqrt(1-abar), lambda = log a - log sig, step s -> s':
+ *   m = (x - sig_s eps) / a_s (no clipping);  h = lambda_s' - lambda_s;
+ *   D = m at the loop's first step, else m + (m - m_prev) / 2r with r = (lambda_s - lambda_prev) / h;
+ *   x' = (sig_s'/sig_s) x + a_s' (1 - e^-h) D, and x' = m at the last step (sig_s' = 0).
+ * Unlike diffusers, a run of fewer than 15 steps does not also fall back to first order at its
+ * second-to-last step.  One extra latent-sized buffer (m_prev) in the workspace.
+ * An unknown sampler returns SVG_ERR_INVALID. */
+int svg_sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, int w, const float* text_emb,
+                    int ctx_len, int num_steps, int start_step, float guidance, const float* noise,
+                    float* hist, void* stream);
+/* One DPM-Solver++(2M) step of svg_sample_loop on caller data (f32, n elements, no CFG combine):
+ * x_out = step(x, eps), m_out = the x0 prediction m (m_out may be NULL).  t -> t_next (t_next < 0:
+ * abar = 1, the final first-order step x_out = m).  m_prev = the previous step's m at timestep t_last
+ * (> t); m_prev NULL: a first-order step, t_last ignored.  x / x_out and m_prev / m_out may alias. */
+int svg_dpmpp_step(svg_ctx* ctx, const float* x, const float* eps, const float* m_prev, float* x_out,
+                   float* m_out, int64_t n, int t, int t_next, int t_last, void* stream);
 
 int svg_resize_nearest_u8(svg_ctx* ctx, const uint8_t* src, int N, int sh, int sw, int C,
                           uint8_t* dst, int dh, int dw, void* stream);

@@ -14,6 +14,14 @@ LIB_PATH = os.environ.get("SVG_LIB") or os.path.join(_HERE, "libsvg_hip.so")   #
 
 SVG_TRANSFORMER, SVG_VAE, SVG_UNET, SVG_CLIP_TEXT, SVG_MINILM, SVG_I3D = 0, 1, 2, 3, 4, 5
 SVG_ERR_RUNTIME, SVG_ERR_INVALID = -1, -2        # enum svg_status
+SAMPLERS = {"ddim": 0, "dpmpp_2m": 1}              # SVG_SAMPLER_DDIM, SVG_SAMPLER_DPMPP_2M
+
+
+def sampler_id(name):
+    """the SVG_SAMPLER_* id of a sampler name ("ddim", "dpmpp_2m"); ValueError for any other"""
+    if name not in SAMPLERS:
+        raise ValueError("unknown sampler %r (one of %s)" % (name, ", ".join(SAMPLERS)))
+    return SAMPLERS[name]
 
 _lib = None
 
@@ -79,6 +87,8 @@ SIGNATURES = {
     "svg_unet_forward": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp],
     "svg_ddim_loop": [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp],
     "svg_ddim_step": [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp],
+    "svg_sample_loop": [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp],
+    "svg_dpmpp_step": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp],
     "svg_resize_bilinear_f32": [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp],
     "svg_resize_nearest_u8": [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
     "svg_op_gemm": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -482,6 +492,31 @@ class Context:
         self.check(self.lib.svg_ddim_loop(self.h, _ptr(z), N, h, w, _ptr(text_emb), text_emb.shape[1], num_steps, start_step,
                                           float(guidance), _ptr(noise), _ptr(hist), _stream()), "svg_ddim_loop")
         return hist if return_hist else z
+
+    def sample_loop(self, z, text_emb, sampler="ddim", num_steps=50, start_step=0, guidance=7.5, noise=None, return_hist=False):
+        """ddim_loop with the update rule `sampler`: "ddim" (the same bits as ddim_loop) or "dpmpp_2m" (DPM-Solver++(2M), svg_sample_loop)"""
+        sid = sampler_id(sampler)
+        N, c, h, w = z.shape
+        z = z.contiguous().float().clone()
+        text_emb = text_emb.contiguous().float()
+        assert text_emb.shape[0] == 2 * N, "text embeddings must be [uncond; cond] (2N rows)"
+        noise = noise.contiguous().float() if noise is not None else None
+        hist = torch.empty(((num_steps - start_step + 1) * N, c, h, w), device=z.device, dtype=torch.float32) if return_hist else None
+        self.check(self.lib.svg_sample_loop(self.h, sid, _ptr(z), N, h, w, _ptr(text_emb), text_emb.shape[1], num_steps, start_step,
+                                            float(guidance), _ptr(noise), _ptr(hist), _stream()), "svg_sample_loop")
+        return hist if return_hist else z
+
+    def dpmpp_step(self, x, eps, t, t_next, m_prev=None, t_last=-1):
+        """one DPM-Solver++(2M) step t -> t_next (< 0: the final step) on caller data: returns (x_next, m), m the x0 prediction;
+        m_prev (the previous step's m, at timestep t_last) None: a first-order step"""
+        x = x.contiguous().float()
+        eps = eps.contiguous().float()
+        m_prev = m_prev.contiguous().float() if m_prev is not None else None
+        out = torch.empty_like(x)
+        m = torch.empty_like(x)
+        self.check(self.lib.svg_dpmpp_step(self.h, _ptr(x), _ptr(eps), _ptr(m_prev), _ptr(out), _ptr(m), x.numel(), int(t), int(t_next),
+                                           int(t_last), _stream()), "svg_dpmpp_step")
+        return out, m
 
     def ddim_step(self, x, eps, t, t_prev):
         x = x.contiguous().float()

@@ -54,6 +54,9 @@ def build_parser():
     p.add_argument("--denoise", type=bool, default=False)
     p.add_argument("--mode", type=str, default="")
     p.add_argument("--denoise_start_step", type=int, default=40)
+    # the denoising loop's sampler and schedule length (num_inference_steps, hard-coded to 50 in the reference's predict loop)
+    p.add_argument("--sampler", type=str, default="ddim", choices=("ddim", "dpmpp_2m"))
+    p.add_argument("--denoise_steps", type=int, default=50)
     return p
 
 

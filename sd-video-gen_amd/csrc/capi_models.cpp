@@ -137,6 +137,29 @@ int svg_ddim_loop(svg_ctx* ctx, float* z, int N, int h, int w, const float* text
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }
+static_assert(SVG_SAMPLER_DDIM == kSamplerDdim && SVG_SAMPLER_DPMPP_2M == kSamplerDpmpp2m, "sampler ids of svg_hip.h and models.h");
+int svg_sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, int w, const float* text_emb, int ctx_len, int num_steps,
+                    int start_step, float guidance, const float* noise, float* hist, void* stream) {
+  try {
+    SVG_CHECK(sampler == SVG_SAMPLER_DDIM || sampler == SVG_SAMPLER_DPMPP_2M, "svg_sample_loop: unknown sampler %d", sampler);
+    SVG_CHECK(ctx && ctx->unet, "unet: model not configured");
+    xf_walk_check(ctx, false);                       // an earlier layer-walking forward that gave up: walk off + logged; raised to the Transformer's caller
+    ctx->unet->sample_loop(ctx, sampler, z, N, h, w, text_emb, ctx_len, num_steps, start_step, guidance, noise, hist, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+int svg_dpmpp_step(svg_ctx* ctx, const float* x, const float* eps, const float* m_prev, float* x_out, float* m_out, int64_t n, int t,
+                   int t_next, int t_last, void* stream) {
+  try {
+    SVG_CHECK(ctx && ctx->unet && ctx->unet->ready, "unet: model not finalized");
+    SVG_CHECK(x && eps && x_out && n >= 0, "svg_dpmpp_step: null tensor or negative size");
+    SVG_CHECK(!m_prev || t_next < 0 || t_last >= 0, "svg_dpmpp_step: a second-order step needs the previous timestep t_last");
+    float row[kDpmRow];
+    ctx->unet->dpmpp_coefs(t, t_next, m_prev ? t_last : -1, row);
+    dpmpp_step(x, eps, nullptr, 0.f, m_prev, x_out, m_out, n, row, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
 int svg_ddim_step(svg_ctx* ctx, const float* x, const float* eps, float* prev, int64_t n, int t, int t_prev, void* stream) {
   try {
     SVG_CHECK(ctx && ctx->unet && ctx->unet->ready, "unet: model not finalized");

@@ -225,9 +225,39 @@ __global__ void ddim_step_tab_kernel(const float* __restrict__ z, const float* _
     zo[i] = sap * x0 + s1ap * e;
   }
 }
-__global__ void ddim_tvec_kernel(float* __restrict__ tvec, int nb, const float* __restrict__ tab, const int* __restrict__ idx) {
+__global__ void ddim_tvec_kernel(float* __restrict__ tvec, int nb, const float* __restrict__ tab, int row, const int* __restrict__ idx) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nb) tvec[i] = tab[5 * idx[0]];
+  if (i < nb) tvec[i] = tab[row * idx[0]];
+}
+// DPM-Solver++(2M) (diffusers DPMSolverMultistepScheduler: dpmsolver++, order 2, midpoint, no thresholding) with the CFG combine in
+// front: m = (x - sig_s e) / a_s;  D = m + k (m - m_prev) (k = 1 / 2r, 0 at first order);  x' = last ? m : cx x + cd D;  m_prev <- m.
+// x / x_out and m_prev / m_out may alias (in-place loop): every element is read before it is written, by the same thread, so those
+// pointers are deliberately not __restrict__.  m_prev is not read at first order (k == 0): it may be null or uninitialised then.
+__device__ __forceinline__ void dpmpp_elem(const float* x, const float* __restrict__ eu, const float* __restrict__ ec, float guidance,
+                                           const float* mp, float* xo, float* mo, int64_t i, float inv_a, float sig, float cx, float cd,
+                                           float k, bool last) {
+  float e = eu[i];
+  if (ec) e = e + guidance * (ec[i] - e);
+  const float xi = x[i];
+  const float m = (xi - sig * e) * inv_a;
+  float d = m;
+  if (k != 0.f) d = m + k * (m - mp[i]);
+  const float out = last ? m : cx * xi + cd * d;
+  if (mo) mo[i] = m;
+  xo[i] = out;
+}
+__global__ void dpmpp_step_kernel(const float* x, const float* __restrict__ eu, const float* __restrict__ ec, float guidance, const float* mp,
+                                  float* xo, float* mo, int64_t n, float inv_a, float sig, float cx, float cd, float k, int last) {
+  GRID_STRIDE(i, n) dpmpp_elem(x, eu, ec, guidance, mp, xo, mo, i, inv_a, sig, cx, cd, k, last != 0);
+}
+// the same step with its row read from a device table through the DDIM loop's step counter: tab[i] = kDpmRow floats
+// {t, 1/a_s, sig_s, sig_s'/sig_s, a_s'(1 - e^-h), 1/2r, last, 0}
+__global__ void dpmpp_step_tab_kernel(const float* x, const float* __restrict__ eu, const float* __restrict__ ec, float guidance, const float* mp,
+                                      float* xo, float* mo, int64_t n, const float* __restrict__ tab, const int* __restrict__ idx) {
+  const float* r = tab + kDpmRow * idx[0];
+  const float inv_a = r[1], sig = r[2], cx = r[3], cd = r[4], k = r[5];
+  const bool last = r[6] != 0.f;
+  GRID_STRIDE(i, n) dpmpp_elem(x, eu, ec, guidance, mp, xo, mo, i, inv_a, sig, cx, cd, k, last);
 }
 __global__ void ddim_bump_kernel(int* __restrict__ idx) { idx[0] += 1; }
 __global__ void add_noise_kernel(const float* __restrict__ x0, const float* __restrict__ nz, float* __restrict__ out, int64_t n, float sa, float s1a) {
@@ -334,9 +364,21 @@ void ddim_step_tab(const float* z, const float* eu, const float* ec, float guida
   hipLaunchKernelGGL(ddim_step_tab_kernel, grid_for(n), dim3(256), 0, s, z, eu, ec, guidance, zo, n, tab, idx);
   check_launch("ddim_step_tab");
 }
-void ddim_tvec(float* tvec, int nb, const float* tab, const int* idx, hipStream_t s) {
-  hipLaunchKernelGGL(ddim_tvec_kernel, dim3((nb + 63) / 64), dim3(64), 0, s, tvec, nb, tab, idx);
+void ddim_tvec(float* tvec, int nb, const float* tab, const int* idx, hipStream_t s, int row) {
+  hipLaunchKernelGGL(ddim_tvec_kernel, dim3((nb + 63) / 64), dim3(64), 0, s, tvec, nb, tab, row, idx);
   check_launch("ddim_tvec");
+}
+void dpmpp_step(const float* x, const float* eu, const float* ec, float guidance, const float* m_prev, float* x_out, float* m_out, int64_t n,
+                const float* row, hipStream_t s) {
+  SVG_CHECK(m_prev || row[5] == 0.f, "dpmpp_step: a second-order step needs m_prev");
+  hipLaunchKernelGGL(dpmpp_step_kernel, grid_for(n), dim3(256), 0, s, x, eu, ec, guidance, m_prev, x_out, m_out, n, row[1], row[2], row[3],
+                     row[4], row[5], row[6] != 0.f ? 1 : 0);
+  check_launch("dpmpp_step");
+}
+void dpmpp_step_tab(const float* x, const float* eu, const float* ec, float guidance, float* m, float* x_out, int64_t n, const float* tab,
+                    const int* idx, hipStream_t s) {
+  hipLaunchKernelGGL(dpmpp_step_tab_kernel, grid_for(n), dim3(256), 0, s, x, eu, ec, guidance, m, x_out, m, n, tab, idx);
+  check_launch("dpmpp_step_tab");
 }
 void ddim_bump(int* idx, hipStream_t s) {
   hipLaunchKernelGGL(ddim_bump_kernel, dim3(1), dim3(1), 0, s, idx);

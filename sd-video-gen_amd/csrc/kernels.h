@@ -254,8 +254,17 @@ void ddim_step(const float* z, const float* eps_u, const float* eps_c, float gui
 // the step with (t, coefficients) read from row idx[0] of a device table of 5-float rows; tvec[i] = tab[idx][0]; idx[0] += 1
 void ddim_step_tab(const float* z, const float* eps_u, const float* eps_c, float guidance, float* z_out, int64_t n, const float* tab,
                    const int* idx, hipStream_t s);
-void ddim_tvec(float* tvec, int nb, const float* tab, const int* idx, hipStream_t s);
+void ddim_tvec(float* tvec, int nb, const float* tab, const int* idx, hipStream_t s, int row = 5);   // row: floats per table row
 void ddim_bump(int* idx, hipStream_t s);
+// DPM-Solver++(2M): one table row of kDpmRow floats {t, 1/a_s, sig_s, sig_s'/sig_s, a_s'(1 - e^-h), 1/2r (0: first order), last, 0}
+constexpr int kDpmRow = 8;
+// x_out <- step(x, eps) with the host row `row`; m_out <- the x0 prediction (may be null); m_prev is read only when row[5] != 0.
+// x / x_out and m_prev / m_out may be the same buffers.
+void dpmpp_step(const float* x, const float* eps_u, const float* eps_c, float guidance, const float* m_prev, float* x_out, float* m_out,
+                int64_t n, const float* row, hipStream_t s);
+// the step with its row read from row idx[0] of a device table (the DDIM loop's counter); m: m_prev in, m out
+void dpmpp_step_tab(const float* x, const float* eps_u, const float* eps_c, float guidance, float* m, float* x_out, int64_t n,
+                    const float* tab, const int* idx, hipStream_t s);
 void add_noise(const float* x0, const float* noise, float* out, int64_t n, float sa, float s1a, hipStream_t s);
 void fill_f32(float* p, int64_t n, float v, hipStream_t s);
 

@@ -135,7 +135,14 @@ struct UnetIface {
   virtual void ddim_loop(svg_ctx* ctx, float* z, int N, int h, int w, const float* text_emb, int ctx_len, int num_steps,
                          int start_step, float guidance, const float* noise, float* hist, hipStream_t s) = 0;
   virtual void ddim_coefs(int t, int t_prev, float* sa, float* s1a, float* sap, float* s1ap) const = 0;
+  // the img2img loop of ddim_loop under another update rule (kSampler*; ddim_loop == sample_loop(kSamplerDdim, ...))
+  virtual void sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, int w, const float* text_emb, int ctx_len, int num_steps,
+                           int start_step, float guidance, const float* noise, float* hist, hipStream_t s) = 0;
+  // one DPM-Solver++(2M) table row (kDpmRow floats) for the step t -> t_next (< 0: alpha_bar = 1); t_last < 0: first order
+  virtual void dpmpp_coefs(int t, int t_next, int t_last, float* row) const = 0;
 };
+// sampler ids of svg_sample_loop (SVG_SAMPLER_* of include/svg_hip.h)
+enum { kSamplerDdim = 0, kSamplerDpmpp2m = 1 };
 VaeIface* new_vae_bf16();
 VaeIface* new_vae_f16();
 UnetIface* new_unet_bf16();
@@ -238,6 +245,9 @@ struct UnetModel : UnetIface {
   void ddim_loop(svg_ctx* ctx, float* z, int N, int h, int w, const float* text_emb, int ctx_len, int num_steps,
                  int start_step, float guidance, const float* noise, float* hist, hipStream_t s) override;
   void ddim_coefs(int t, int t_prev, float* sa, float* s1a, float* sap, float* s1ap) const override;
+  void sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, int w, const float* text_emb, int ctx_len, int num_steps,
+                   int start_step, float guidance, const float* noise, float* hist, hipStream_t s) override;
+  void dpmpp_coefs(int t, int t_next, int t_last, float* row) const override;
 };
 
 // Request for the GroupNorm column sums of an output (GemmArgs::gn_part): the caller provides `buf` (gn_part_floats() floats, at

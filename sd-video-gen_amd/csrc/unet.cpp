@@ -288,6 +288,33 @@ void UnetModel::ddim_coefs(int t, int t_prev, float* sa, float* s1a, float* sap,
   *sa = sqrtf(a_t); *s1a = sqrtf(1.f - a_t); *sap = sqrtf(a_p); *s1ap = sqrtf(1.f - a_p);
 }
 
+// DPM-Solver++(2M) on the DDIM timestep set, in double from the f32 alphas_cumprod: with a = sqrt(abar), sig = sqrt(1 - abar),
+// lambda = log a - log sig and h = lambda_s' - lambda_s:  x' = (sig_s'/sig_s) x + a_s'(1 - e^-h) D,  D = m + (m - m_prev) / 2r,
+// r = (lambda_s - lambda_last) / h (D = m at first order);  sig_s' == 0 (t_next < 0, set_alpha_to_one) is the final step: x' = m.
+void UnetModel::dpmpp_coefs(int t, int t_next, int t_last, float* row) const {
+  SVG_CHECK(t >= 0 && t < 1000 && t_next < t, "dpmpp: timesteps %d -> %d out of range", t, t_next);
+  SVG_CHECK(t_last < 0 || (t_last > t && t_last < 1000), "dpmpp: previous timestep %d is not in (%d, 1000)", t_last, t);
+  auto lam = [](double ab) { return 0.5 * log(ab) - 0.5 * log1p(-ab); };
+  const double ab = alphas_cumprod[t];
+  const double a = sqrt(ab), sig = sqrt(1.0 - ab);
+  for (int j = 0; j < kDpmRow; ++j) row[j] = 0.f;
+  row[0] = (float)t;
+  row[1] = (float)(1.0 / a);
+  row[2] = (float)sig;
+  if (t_next < 0) {                 // lower_order_final: x' = m
+    row[6] = 1.f;
+    return;
+  }
+  const double abn = alphas_cumprod[t_next];
+  const double h = lam(abn) - lam(ab);
+  row[3] = (float)(sqrt(1.0 - abn) / sig);
+  row[4] = (float)(-sqrt(abn) * expm1(-h));
+  if (t_last >= 0) {
+    const double r = (lam(ab) - lam(alphas_cumprod[t_last])) / h;
+    row[5] = (float)(0.5 / r);
+  }
+}
+
 namespace {
 struct UnetRun {
   svg_ctx* ctx; UnetModel* m; hipStream_t s; int N;
@@ -684,7 +711,17 @@ void UnetModel::run(svg_ctx* ctx, const float* x, int N, int h, int w, const flo
 
 void UnetModel::ddim_loop(svg_ctx* ctx, float* z, int N, int h, int w, const float* text_emb, int ctx_len, int num_steps,
                           int start_step, float guidance, const float* noise, float* hist, hipStream_t s) {
+  sample_loop(ctx, kSamplerDdim, z, N, h, w, text_emb, ctx_len, num_steps, start_step, guidance, noise, hist, s);
+}
+
+// The img2img loop of either sampler: the same timesteps, add_noise, CFG combine, K / V^T cache, fp8 placement and step graph; only
+// the update kernel and its table differ.  DPM++(2M) keeps the previous step's x0 prediction in `mprev` (one latent-sized buffer).
+void UnetModel::sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, int w, const float* text_emb, int ctx_len, int num_steps,
+                            int start_step, float guidance, const float* noise, float* hist, hipStream_t s) {
   SVG_CHECK(ready, "unet: svg_finalize has not been called");
+  SVG_CHECK(sampler == kSamplerDdim || sampler == kSamplerDpmpp2m, "sample_loop: unknown sampler %d", sampler);
+  const bool dpm = sampler == kSamplerDpmpp2m;
+  const int row = dpm ? kDpmRow : 5;      // floats per table row
   SVG_CHECK(num_steps >= 1 && num_steps <= 1000 && start_step >= 0 && start_step <= num_steps, "ddim: bad steps %d/%d", start_step, num_steps);
   SVG_CHECK(start_step == 0 || noise, "ddim: start_step > 0 needs the add_noise draws");
   const int ratio = 1000 / num_steps;
@@ -711,8 +748,9 @@ void UnetModel::ddim_loop(svg_ctx* ctx, float* z, int N, int h, int w, const flo
     float* tvec = ctx->arena.get<float>(NB);
     float* zin = cfg ? ctx->arena.get<float>(2 * n) : nullptr;
     float* eps = ctx->arena.get<float>((int64_t)NB * n / N);
-    float* tab = ctx->arena.get<float>((int64_t)5 * num_steps);
+    float* tab = ctx->arena.get<float>((int64_t)row * num_steps);
     int* idx = ctx->arena.get<int>(1);
+    float* mprev = dpm ? ctx->arena.get<float>(n) : nullptr;   // DPM++: the previous step's x0 prediction
     if (SVG_LAUNCHING(ctx)) {
       if (start_step > 0 && start_step < num_steps) {
         const float a = alphas_cumprod[timestep_at(start_step)];
@@ -720,11 +758,15 @@ void UnetModel::ddim_loop(svg_ctx* ctx, float* z, int N, int h, int w, const flo
       }
       if (hist) HIP_OK(hipMemcpyAsync(hist, z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
       if (use_graph) {
-        std::vector<float> h((size_t)5 * num_steps);
+        std::vector<float> h((size_t)row * num_steps);
         for (int i = 0; i < num_steps; ++i) {
           const int t = timestep_at(i);
-          h[5 * i] = (float)t;
-          ddim_coefs(t, t - ratio, &h[5 * i + 1], &h[5 * i + 2], &h[5 * i + 3], &h[5 * i + 4]);
+          if (dpm) {
+            dpmpp_coefs(t, t - ratio, i > start_step ? timestep_at(i - 1) : -1, &h[(size_t)row * i]);
+          } else {
+            h[5 * i] = (float)t;
+            ddim_coefs(t, t - ratio, &h[5 * i + 1], &h[5 * i + 2], &h[5 * i + 3], &h[5 * i + 4]);
+          }
         }
         // pageable host memory: the copy is staged before the call returns
         HIP_OK(hipMemcpyAsync(tab, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice, s));
@@ -737,7 +779,7 @@ void UnetModel::ddim_loop(svg_ctx* ctx, float* z, int N, int h, int w, const flo
       const int t = timestep_at(i);
       ctx->arena.push();
       if (SVG_LAUNCHING(ctx)) {
-        if (tabled) ddim_tvec(tvec, NB, tab, idx, s);
+        if (tabled) ddim_tvec(tvec, NB, tab, idx, s, row);
         else fill_f32(tvec, NB, (float)t, s);
         if (cfg) {
           HIP_OK(hipMemcpyAsync(zin, z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -750,8 +792,15 @@ void UnetModel::ddim_loop(svg_ctx* ctx, float* z, int N, int h, int w, const flo
       run(ctx, cfg ? zin : z, NB, h, w, tvec, text_emb, ctx_len, eps, s, &kv, sites);
       if (SVG_LAUNCHING(ctx)) {
         if (tabled) {
-          ddim_step_tab(z, eps, cfg ? eps + n : nullptr, guidance, z, n, tab, idx, s);
+          if (dpm) dpmpp_step_tab(z, eps, cfg ? eps + n : nullptr, guidance, mprev, z, n, tab, idx, s);
+          else ddim_step_tab(z, eps, cfg ? eps + n : nullptr, guidance, z, n, tab, idx, s);
           ddim_bump(idx, s);
+        } else if (dpm) {
+          float r[kDpmRow];
+          dpmpp_coefs(t, t - ratio, i > start_step ? timestep_at(i - 1) : -1, r);
+          ProfScope ps(ctx, PK_ELT, s, 0, 0);
+          dpmpp_step(z, eps, cfg ? eps + n : nullptr, guidance, mprev, z, mprev, n, r, s);
+          if (hist) HIP_OK(hipMemcpyAsync(hist + (int64_t)(i - start_step + 1) * n, z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
         } else {
           float sa, s1a, sap, s1ap;
           ddim_coefs(t, t - ratio, &sa, &s1a, &sap, &s1ap);

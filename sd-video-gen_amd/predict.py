@@ -9,6 +9,8 @@ import os
 
 import torch
 
+from . import _lib
+
 
 def predict(model, input_sequence, pe_row=None, cls_list=None):
     """prediction/predict.py:16-42 -> (D_lat,) for batch row 0 (or (B,D_lat) rows when ``pe_row`` is given).
@@ -34,7 +36,7 @@ def clip_noise(seeds, shape, device):
 
 def sample_clips(model, sd_utils, clips_u8, pred_frames, denoise=False, start_step=40, seeds=None,
                  text_embeddings=None, num_inference_steps=50, guidance_scale=0.0, return_frames=False, res=512,
-                 cls_list=None, cpu_noise=False, latent_denoise=False, _planning=False):
+                 cls_list=None, cpu_noise=False, latent_denoise=False, sampler="ddim", _planning=False):
     """The per-clip loop of prediction/predict.py:117-197 for C independent clips in lock step, device resident.
 
     clips_u8: (C,T,F,F,3) uint8 conditioning frames on the device (T = 5 in prediction/predict.py; the FVD loop of
@@ -47,6 +49,8 @@ def sample_clips(model, sd_utils, clips_u8, pred_frames, denoise=False, start_st
     prediction/predict_text.py:186-262 (same loop, `predict(model, X, cls_list)`); the names are encoded once.
     ``latent_denoise``: the variant of evaluation/predict_fvd.py:160-178 — the predicted latent itself is resized (bilinear) to the
     512-pixel latent grid and denoised, instead of being decoded, resized as an image and re-encoded first.
+    ``sampler``: the update rule of the denoising loop, "ddim" (the reference's) or "dpmpp_2m" (DPM-Solver++(2M) on the same
+    timesteps: Context.sample_loop).
     ``cpu_noise``: the per-clip generators live on the host (bit-reproducible on a machine without the GPU: the committed
     oracle fixtures of tests/golden/sd_*.pt were drawn that way); default is the device generator, like the reference.
     Workspace: the first call of a given shape signature on a context first runs itself in the library's planning mode (every model
@@ -55,12 +59,13 @@ def sample_clips(model, sd_utils, clips_u8, pred_frames, denoise=False, start_st
     Returns all_latents (C, 4+N, D_lat) f32 [and the decoded frames (C,4+N,F,F,3) uint8].
     """
     ctx = sd_utils.vae.ctx                      # (checked: the context's slots still hold this SDUtils' networks)
+    _lib.sampler_id(sampler)
     if denoise:
         assert sd_utils.unet is not None and sd_utils.unet.ctx is ctx, "sample_clips(denoise=True) needs SDUtils built with --denoise"
     if not _planning:
         plan_workspace(model, sd_utils, clips_u8, pred_frames, denoise=denoise, start_step=start_step, text_embeddings=text_embeddings,
                        num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, return_frames=return_frames, res=res,
-                       cls_list=cls_list, latent_denoise=latent_denoise)
+                       cls_list=cls_list, latent_denoise=latent_denoise, sampler=sampler)
     dev = clips_u8.device
     C, T, F = clips_u8.shape[0], clips_u8.shape[1], clips_u8.shape[2]
     assert 2 <= T <= 31, "conditioning frames: 5 in predict.py:57, 16 in predict_text.py:133 (the library serves sequences up to 32 tokens)"
@@ -95,8 +100,8 @@ def sample_clips(model, sd_utils, clips_u8, pred_frames, denoise=False, start_st
                     e512 = clip_noise(gens, (4, res // 8, res // 8), dev)
                     resized = ctx.vae_encode(noisy_img, H=res, W=res, eps=e512)             # :158 resize + :163-164
                 noise = clip_noise(gens, (4, res // 8, res // 8), dev) if 0 < start_step else None
-                den = ctx.ddim_loop(resized, emb, num_steps=num_inference_steps, start_step=start_step,
-                                    guidance=guidance_scale, noise=noise)                   # :168-170
+                den = ctx.sample_loop(resized, emb, sampler=sampler, num_steps=num_inference_steps, start_step=start_step,
+                                      guidance=guidance_scale, noise=noise)                 # :168-170
                 small = ctx.vae_decode(den, out_hw=(F, F))                                  # :173-179
                 eF = clip_noise(gens, (4, L, L), dev)
                 pred = ctx.vae_encode(small, eps=eF).reshape(C, D)                          # :183-185
@@ -125,13 +130,12 @@ def plan_workspace(model, sd_utils, clips_u8, pred_frames, **kw):
     emb, cl = kw.get("text_embeddings"), kw.get("cls_list")
     key = ("sample_clips", id(model), tuple(clips_u8.shape), int(pred_frames), bool(kw.get("denoise")), int(kw.get("start_step", 40)),
            int(kw.get("num_inference_steps", 50)), float(kw.get("guidance_scale", 0.0)) != 0.0, bool(kw.get("return_frames")), int(kw.get("res", 512)),
-           bool(kw.get("latent_denoise")), None if emb is None else tuple(emb.shape), cl is not None)
+           bool(kw.get("latent_denoise")), None if emb is None else tuple(emb.shape), cl is not None, kw.get("sampler", "ddim"))
     kw = {k: v for k, v in kw.items() if k not in ("seeds", "cpu_noise")}
     seen = ctx.__dict__.setdefault("_planned", set())
     if key in seen:
         return False
     import contextlib
-    from . import _lib
     mctx = getattr(model, "_bound_ctx", None) or _lib.default_context()      # the latent Transformer may live on another context
     with contextlib.ExitStack() as st:
         for c in ([ctx] if mctx is ctx else [ctx, mctx]):
@@ -359,7 +363,7 @@ def main(argv=None):
     n = clips.shape[0]
     lat, frames = run_sharded(clips, lambda c, seeds: sample_clips(
         model, sd_utils, c.to(device), args.pred_frames, denoise=bool(args.denoise), start_step=args.denoise_start_step,
-        seeds=seeds, return_frames=True))                          # ends in the ONE collective of the path
+        num_inference_steps=args.denoise_steps, sampler=args.sampler, seeds=seeds, return_frames=True))                          # ends in the ONE collective of the path
     if rank == 0:
         print("all_latents shape: ", tuple(lat.shape))
         if args.save_output:

@@ -125,7 +125,8 @@ def main(argv=None):
                 real_input = None
             kw = dict(cls_list=cls_list) if cls_list is not None else {}
             lat, frames = sample_clips(model, sd_utils, batch.to(device), args.pred_frames, denoise=bool(args.denoise),
-                                       start_step=args.denoise_start_step, seeds=[ind], return_frames=True, **kw)  # :186-258
+                                       start_step=args.denoise_start_step, num_inference_steps=args.denoise_steps,
+                                       sampler=args.sampler, seeds=[ind], return_frames=True, **kw)                   # :186-258
             if args.save_output:                                                                               # :260-288
                 n_in = batch.shape[1] - 1
                 is_pred = [False] * n_in + [True] * (frames.shape[1] - n_in)

@@ -463,7 +463,9 @@ class SDUtils():
 
     # ---- sd_utils.py:222-267 ---------------------------------------------------------------------------
     def gen_i2i_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5,
-                        latents=None, return_all_latents=False, start_step=10, noise=None):
+                        latents=None, return_all_latents=False, start_step=10, noise=None, sampler="ddim"):
+        """`sampler`: "ddim" (the reference's DDIMScheduler) or "dpmpp_2m" (DPM-Solver++(2M) on the same timesteps)"""
+        _lib.sampler_id(sampler)
         if self.unet is None:
             raise RuntimeError("gen_i2i_latents needs the UNet: construct SDUtils with --denoise")
         if latents is None:
@@ -471,8 +473,8 @@ class SDUtils():
         latents = latents.to(self.device)
         if start_step > 0 and noise is None:
             noise = torch.randn_like(latents)
-        return self.unet.ctx.ddim_loop(latents, text_embeddings.to(self.device), num_steps=num_inference_steps, start_step=start_step,
-                                  guidance=guidance_scale, noise=noise, return_hist=return_all_latents)
+        return self.unet.ctx.sample_loop(latents, text_embeddings.to(self.device), sampler=sampler, num_steps=num_inference_steps,
+                                         start_step=start_step, guidance=guidance_scale, noise=noise, return_hist=return_all_latents)
 
     def perturb_latents(self, latents, scale=0.1):
         noise = torch.randn_like(latents)
@@ -480,12 +482,13 @@ class SDUtils():
         return (new_latents - new_latents.mean()) / new_latents.std()
 
     def img_to_img(self, prompts, height=512, width=512, num_inference_steps=50, guidance_scale=7.5, img=None,
-                   return_all_latents=False, batch_size=2, start_step=10):
+                   return_all_latents=False, batch_size=2, start_step=10, sampler="ddim"):
         if isinstance(prompts, str):
             prompts = [prompts]
         lat = self.encode_img(img)
         emb = self.encode_text(prompts)
-        out = self.gen_i2i_latents(emb, height, width, num_inference_steps, guidance_scale, lat, return_all_latents, start_step)
+        out = self.gen_i2i_latents(emb, height, width, num_inference_steps, guidance_scale, lat, return_all_latents, start_step,
+                                   sampler=sampler)
         imgs = []
         for i in range(0, len(out), batch_size):
             imgs.extend(self.decode_img_latents(out[i:i + batch_size]))
