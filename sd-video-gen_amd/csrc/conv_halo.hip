@@ -24,6 +24,7 @@ namespace {
 #endif
 constexpr int ABL = HALO_ABL;
 constexpr int PW = 18;                 // patch width / height in pixels
+static_assert(PW == HALO_SIDE + 2, "the patch is the tile of output pixels the plan counts (gemm_tiles.h) plus its halo");
 constexpr int PPIX = PW * PW;          // 324
 constexpr int NPD = 6;                 // patch DMA instructions per wave: 8 waves * 64 lanes * 6 = 3072 >= 324 * 8 chunks
 // MFMA (0-based, of the 2 nm in a merged segment) behind which DMA slot o of the merged loop sits (the placement gemm_pp.hip measured best)
@@ -555,35 +556,6 @@ void launch_halo(const GemmArgs& g, dim3 grid, hipStream_t s) {
 
 }  // namespace
 
-int conv_halo_bn(const GemmArgs& g);
-
-// stride-1 3x3 convs on images whose sides are multiples of 16, with enough 16x16-pixel blocks x channel tiles to give
-// every CU a workgroup (below that the 128-row implicit GEMM with its split-K is faster: same-box A/B at 16x16 images)
-bool conv_halo_supported(const GemmArgs& g) {
-  static const int off = getenv("SVG_NO_HALO") ? atoi(getenv("SVG_NO_HALO")) : 0;
-  static const int up_on = getenv("SVG_HALO_UP2") ? atoi(getenv("SVG_HALO_UP2")) : 1;
-  const bool s1 = g.amode == A_CONV_S1 && g.Ho == g.H && g.Wo == g.W;
-  const bool up = up_on && g.amode == A_CONV_UP2 && g.Ho == 2 * g.H && g.Wo == 2 * g.W && !g.A2;
-  if (off || !(s1 || up) || g.Cin % 64 != 0 || g.Ho % 16 != 0 || g.Wo % 16 != 0 || g.batch != 1 || g.out_f32 == 1 ||
-      g.act == ACT_GEGLU || g.N < 128)
-    return false;
-  const int min_wg = (int)svg_env_i64("SVG_HALO_MIN", 192);      // (cached lookup; svg_env_refresh re-reads it: the parity tests force the kernel at batch 1-2)
-  return (int64_t)(g.M / 256) * cdiv(g.N, conv_halo_bn(g)) >= min_wg;
-}
-
-// channel-tile width: fewest serial rounds of workgroups (one per CU) times tile width; ties -> fewer padded columns
-int conv_halo_bn(const GemmArgs& g) {
-  const int64_t pb = g.M / 256;
-  int best = 128;
-  int64_t best_cost = -1, best_pad = 0;
-  for (int bn : {128, 160}) {
-    const int64_t tn = cdiv(g.N, bn);
-    const int64_t cost = ((pb * tn + 255) / 256) * bn, pad = tn * bn - g.N;
-    if (best_cost < 0 || cost < best_cost || (cost == best_cost && pad < best_pad)) { best = bn; best_cost = cost; best_pad = pad; }
-  }
-  return best;
-}
-
 void conv_halo_init_device() {
   HIP_OK(hipFuncSetAttribute((const void*)conv_halo_kernel<128, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PPIX * 128 + 3 * 128 * 128 + 8192));
   HIP_OK(hipFuncSetAttribute((const void*)conv_halo_kernel<128, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PPIX * 128 + 3 * 128 * 128 + 8192));
@@ -595,9 +567,10 @@ void conv_halo_init_device() {
   HIP_OK(hipFuncSetAttribute((const void*)conv_halo_kernel<160, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PPIX * 128 + 3 * 160 * 128 + 8192));
 }
 
-void launch_conv_halo(const GemmArgs& g, dim3 grid, hipStream_t s) {
+// bn: the channel-tile width of the plan (gemm_plan.cpp), 128 or 160
+void launch_conv_halo(const GemmArgs& g, int bn, dim3 grid, hipStream_t s) {
   static const int pp = getenv("SVG_HALO_PP") ? atoi(getenv("SVG_HALO_PP")) : 1;
-  const bool w160 = conv_halo_bn(g) == 160;
+  const bool w160 = bn == 160;
   if (g.out_f32 == 2) {     // f32 residual stream: the merged loop at either width, whatever the A/B switches below say
     GemmArgs gm = g;
     gm.pp_dma_m = std::max(0, std::min(4, (int)svg_env_i64("SVG_HALO_DMA_M", 4)));

@@ -18,14 +18,10 @@
 
 namespace SDNS {
 
-// conv_halo.hip
-void launch_conv_halo(const GemmArgs& g, dim3 grid, hipStream_t s);
-bool gemm_pp_supported(const GemmArgs& g);
-bool gemm_ws_supported(const GemmArgs& g);
-int gemm_ws_groups(const GemmArgs& g);
-void launch_gemm_ws(svg_ctx* ctx, const GemmArgs& g, hipStream_t s);
-int gemm_pp_bn(const GemmArgs& g);
-void launch_gemm_pp(const GemmArgs& g, hipStream_t s);
+// the other families' launchers (conv_halo.hip, gemm_ws.hip, gemm_pp.hip): bn = the plan's column tile
+void launch_conv_halo(const GemmArgs& g, int bn, dim3 grid, hipStream_t s);
+void launch_gemm_ws(svg_ctx* ctx, const GemmArgs& g, int group_cols, hipStream_t s);
+void launch_gemm_pp(const GemmArgs& g, int bn, hipStream_t s);
 
 namespace {
 
@@ -434,65 +430,12 @@ void attr_bn() {
   attr_inst<BN, A_CONV_UP2>(); attr_inst<BN, A_CONV_SMALLC>();
 }
 
-int pick_bn(const GemmArgs& g) {
-  static const int force = getenv("SVG_GEMM_BN") ? atoi(getenv("SVG_GEMM_BN")) : 0;
-  if (force && g.act != ACT_GEGLU && g.N > 64) return force;
-  if (g.act == ACT_GEGLU) return 128;
-  if (g.out_f32 != 2) {                 // (the f32 stream has 128 / 160-column instantiations only)
-    if (g.N <= 32) return 32;
-    if (g.N <= 64) return 64;
-  }
-  // per-CU serial work ~ ceil(blocks / 256) * BN (blocks beyond one per CU share the matrix pipe); ties go to the
-  // width with fewer padded columns, then to the wider tile (the A panel is re-read once per column tile)
-  const int64_t tm = (int64_t)cdiv(g.M, BM) * g.batch;
-  // the 8 x 8 level's convolutions (1792 rows, K = 11520 / 23040): 14 x 8 tiles of 160 columns x split-K 4 = 448 workgroups, two per CU in
-  // one wave of the grid: 0.067 / 0.115 ms against 0.073 / 0.121 for 128 columns x split-K 3 (profiles/r04_kbench_8x8_sweep.txt)
-  if (g.amode != A_DENSE && g.N % 160 == 0 && tm * (g.N / 160) < 192) return 160;
-  int best = 128;
-  int64_t best_cost = -1, best_pad = 0;
-  for (int bn : {128, 160}) {
-    const int64_t tn = cdiv(g.N, bn);
-    const int64_t cost = ((tm * tn + 255) / 256) * bn;
-    const int64_t pad = tn * bn - g.N;
-    if (best_cost < 0 || cost < best_cost || (cost == best_cost && (pad < best_pad || (pad == best_pad && bn > best)))) {
-      best = bn; best_cost = cost; best_pad = pad;
-    }
-  }
-  return best;
-}
-
 }  // namespace
-
-static int plan_splitk(const GemmArgs& g);
-
-int gemm_emits_gn(const GemmArgs& g0) {
-  GemmArgs g = g0;
-  if (g.n_valid <= 0) g.n_valid = g.N;
-  if (g.out_f32 == 1 || g.act == ACT_GEGLU || g.N > g.ldc) return 0;
-  if (g.batch != 1) return 0;
-  if (plan_splitk(g) > 1) return 0;
-  g.splitk = 1;
-  if (conv_halo_supported(g)) return 256;
-  if (gemm_ws_supported(g)) return 128;
-  if (gemm_pp_supported(g)) return 256;
-  return pick_bn(g) >= 32 ? BM : 0;
-}
-
-int gemm_ln_tiles(const GemmArgs& g0) {
-  GemmArgs g = g0;
-  if (g.n_valid <= 0) g.n_valid = g.N;
-  if (g.out_f32 || g.act == ACT_GEGLU || g.N > g.ldc || g.amode != A_DENSE || g.bias_row) return 0;
-  if (plan_splitk(g) > 1) return 0;
-  g.splitk = 1;
-  if (gemm_ws_supported(g)) return gemm_ws_groups(g);      // one partial per row and column group
-  if (gemm_pp_supported(g)) return cdiv(g.N, gemm_pp_bn(g));
-  const int bn = pick_bn(g);
-  return bn >= 128 ? cdiv(g.N, bn) : 0;
-}
 
 void gemm_init_device() { attr_bn<32>(); attr_bn<64>(); attr_bn<128>(); attr_bn<160>(); }
 
-void launch_gemm(svg_ctx* ctx, const GemmArgs& g, hipStream_t s, int prof_kind) {
+// validates g, then launches `plan` (gemm_plan.cpp) as it stands: no decision is taken here; g.slabs holds the split-K workspace
+static void launch_gemm(svg_ctx* ctx, const GemmArgs& g, const GemmPlan& plan, hipStream_t s, int prof_kind) {
   SVG_CHECK(g.N % 4 == 0 && g.K % 8 == 0, "gemm: N (%d) must be a multiple of 4 and K (%d) of 8", g.N, g.K);
   SVG_CHECK(g.M > 0 && g.N > 0 && g.K > 0, "gemm: empty problem %d %d %d", g.M, g.N, g.K);
   if (g.amode != A_DENSE) {
@@ -523,8 +466,7 @@ void launch_gemm(svg_ctx* ctx, const GemmArgs& g, hipStream_t s, int prof_kind) 
   GemmArgs a = g;
   static const int dbg_env = getenv("SVG_GEMM_DBG") ? atoi(getenv("SVG_GEMM_DBG")) : 0;
   a.dbg = dbg_env;
-  if (a.splitk < 1) a.splitk = 1;
-  if (a.n_valid <= 0) a.n_valid = a.N;
+  a.splitk = plan.splitk;
   {
     // Each XCD has its own L2: with the A rows adjacent every XCD streams ALL the weights (8 x N*K*2 bytes per launch),
     // with the weights adjacent every XCD streams all of A.  Pick the cheaper (16 x 16 / 8 x 8 convs: 30 MB of weights
@@ -536,11 +478,10 @@ void launch_gemm(svg_ctx* ctx, const GemmArgs& g, hipStream_t s, int prof_kind) 
   }
   // algorithmic bytes: every operand once (a conv reads its image once, not once per tap)
   const double a_elems = g.amode == A_DENSE ? (double)g.M * g.K : (double)(g.M / (g.Ho * g.Wo)) * g.H * g.W * g.Cin;
-  const GemmPath path = gemm_describe(a);
   char tag[160] = "";
   if (ctx->prof_detail) {
     static const char* const kern_name[] = {"igemm", "halo", "pp", "ws"};
-    const char* kern = kern_name[path.family];
+    const char* kern = kern_name[plan.family];
     if (g.amode == A_DENSE)
       snprintf(tag, sizeof(tag), "M%d_N%d_K%d_b%d_act%d_res%d_ln%d_sk%d_%s", g.M, g.N, g.K, g.batch, g.act, g.residual ? 1 : 0, g.ln_rs ? 1 : 0, a.splitk, kern);
     else
@@ -548,19 +489,18 @@ void launch_gemm(svg_ctx* ctx, const GemmArgs& g, hipStream_t s, int prof_kind) 
   }
   ProfScope ps(ctx, prof_kind, s, 2.0 * g.M * (double)g.N * g.K * g.batch,
                2.0 * (a_elems + (double)g.N * g.K + (double)g.M * g.N) * g.batch, tag);
-  if (path.family == GF_HALO) {
+  if (plan.family == GF_HALO) {
     // 16 x 16 pixel blocks x channel tiles; splitk partitions the 64-channel chunks
-    const int blocks = (a.M / 256) * cdiv(a.N, path.bn);
-    launch_conv_halo(a, dim3(blocks, 1, a.splitk), s);
-  } else if (path.family == GF_WS) {
-    launch_gemm_ws(ctx, a, s);
-  } else if (path.family == GF_PP) {
-    launch_gemm_pp(a, s);
+    const int blocks = (a.M / HALO_ROWS) * cdiv(a.N, plan.bn);
+    launch_conv_halo(a, plan.bn, dim3(blocks, 1, a.splitk), s);
+  } else if (plan.family == GF_WS) {
+    launch_gemm_ws(ctx, a, plan.bn, s);
+  } else if (plan.family == GF_PP) {
+    launch_gemm_pp(a, plan.bn, s);
   } else {
-    const int bn = path.bn;
-    const int tiles = cdiv(a.M, BM) * cdiv(a.N, bn);
+    const int tiles = cdiv(a.M, BM) * cdiv(a.N, plan.bn);
     dim3 grid(tiles, a.batch, a.splitk);
-    switch (bn) {
+    switch (plan.bn) {
       case 32: launch_bn<32>(a, grid, s); break;
       case 64: launch_bn<64>(a, grid, s); break;
       case 128: launch_bn<128>(a, grid, s); break;
@@ -577,63 +517,35 @@ void launch_gemm(svg_ctx* ctx, const GemmArgs& g, hipStream_t s, int prof_kind) 
   }
 }
 
-// split-K factor gemm_auto() uses for g (1 = none)
-static int plan_splitk(const GemmArgs& g) {
-  if (conv_halo_supported(g)) {
-    const int64_t blocks = (int64_t)(g.M / 256) * cdiv(g.N, conv_halo_bn(g));
-    const int CC = g.Cin / 64;
-    static const int tgt = getenv("SVG_HALO_SPLIT_TGT") ? atoi(getenv("SVG_HALO_SPLIT_TGT")) : 320;
-    if (blocks < 192 && CC >= 4) return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((tgt + blocks - 1) / blocks, CC / 2), 8));
-    return 1;
-  }
-  if (gemm_ws_supported(g) || gemm_pp_supported(g)) return 1;
-  const int bn = pick_bn(g);
-  const int64_t blocks = (int64_t)cdiv(g.M, BM) * cdiv(g.N, bn) * g.batch;
-  const int KT = cdiv(g.K, BK);
-  {
-    const int force = (int)svg_env_i64("SVG_IGEMM_SK", 0);     // experiments: split-K of the tiled kernel for launches below 192 tiles
-    if (force > 0 && blocks < 192 && KT >= 8) return std::min(force, KT / 4);
-  }
-  if (blocks < 192 && KT >= 8) {
-    const int tgt = g.amode != A_DENSE ? 448 : 384;
-    const int sk = (int)std::min<int64_t>((tgt + blocks - 1) / blocks, KT / 4);
-    return std::max(1, std::min(sk, 16));
-  }
-  // about one workgroup (4 waves) per CU and a long K: a single wave per SIMD cannot hide its own load phases, so
-  // split in two for two co-resident workgroups (same-box A/B at 16 x 16 x 1280 convs: 0.149 -> 0.122 ms)
-  if (blocks < 300 && KT >= 64) return 2;
-  return 1;
-}
-
-bool gemm_fused_qkv_supported(const GemmArgs& g) { return g.vt_out != nullptr && gemm_ws_supported(g); }
-
-// the dispatch order of launch_gemm
-GemmPath gemm_describe(const GemmArgs& g) {
-  GemmPath p;
-  p.splitk = std::max(1, g.splitk);
-  if (conv_halo_supported(g)) { p.family = GF_HALO; p.bn = conv_halo_bn(g); }
-  else if (gemm_ws_supported(g)) { p.family = GF_WS; p.bn = g.N / gemm_ws_groups(g); }
-  else if (gemm_pp_supported(g)) { p.family = GF_PP; p.bn = gemm_pp_bn(g); }
-  else { p.family = GF_IGEMM; p.bn = pick_bn(g); }
-  return p;
-}
-
-void gemm_auto(svg_ctx* ctx, GemmArgs g, hipStream_t s, int prof_kind, GemmPath* path) {
-  if (g.n_valid <= 0) g.n_valid = g.N;
-  SVG_CHECK(!g.vt_out || gemm_ws_supported(g), "gemm: a fused q | k | V^T problem (vt_out) needs the weight-stationary kernel (ask gemm_fused_qkv_supported)");
-  g.splitk = 1;
-  const int sk = plan_splitk(g);
-  g.splitk = sk;
-  if (path) *path = gemm_describe(g);
-  if (sk > 1) {
-    SVG_CHECK(!g.gn_part, "gemm: GroupNorm statistics cannot be emitted by a split-K launch (ask gemm_emits_gn first)");
+// what the plan promises has to be what g asks for: a caller that set gn_part / ln_part from another plan would read statistics of
+// the wrong tile shape, so that is an error here, before anything is launched
+static void gemm_run(svg_ctx* ctx, GemmArgs& g, const GemmPlan& plan, hipStream_t s, int prof_kind) {
+  SVG_CHECK(!g.vt_out || plan.family == GF_WS, "gemm: a fused q | k | V^T problem (vt_out) needs the weight-stationary kernel (ask gemm_plan: family GF_WS)");
+  SVG_CHECK(!g.gn_part || plan.splitk == 1, "gemm: GroupNorm statistics cannot be emitted by a split-K launch (ask gemm_plan first)");
+  SVG_CHECK(!g.gn_part || plan.gn_rows > 0, "gemm: this launch cannot emit GroupNorm statistics (gemm_plan: gn_rows 0), gn_part is set");
+  SVG_CHECK(!g.ln_part || (plan.ln_tiles > 0 && g.ln_tiles == plan.ln_tiles), "gemm: ln_part is set with %d column tiles, the launch emits %d (gemm_plan: ln_tiles)",
+            g.ln_tiles, plan.ln_tiles);
+  if (plan.splitk > 1) {
     ctx->arena.push();
-    g.slabs = ctx->arena.get<float>((int64_t)sk * g.batch * g.M * g.N);
-    launch_gemm(ctx, g, s, prof_kind);
+    g.slabs = ctx->arena.get<float>((int64_t)plan.splitk * g.batch * g.M * g.N);
+    launch_gemm(ctx, g, plan, s, prof_kind);
     ctx->arena.pop();   // stream order protects the slabs until the reduce has run
   } else {
-    launch_gemm(ctx, g, s, prof_kind);
+    launch_gemm(ctx, g, plan, s, prof_kind);
   }
+}
+
+void gemm_auto(svg_ctx* ctx, GemmArgs g, const GemmPlan& plan, hipStream_t s, int prof_kind) {
+  if (g.n_valid <= 0) g.n_valid = g.N;
+  const GemmPlan now = gemm_plan(g);
+  SVG_CHECK(now == plan, "gemm: the plan handed in (family %d, tile %d, split-K %d, gn_rows %d, ln_tiles %d) is not the plan of these arguments (%d, %d, %d, %d, %d)",
+            plan.family, plan.bn, plan.splitk, plan.gn_rows, plan.ln_tiles, now.family, now.bn, now.splitk, now.gn_rows, now.ln_tiles);
+  gemm_run(ctx, g, plan, s, prof_kind);
+}
+
+void gemm_auto(svg_ctx* ctx, GemmArgs g, hipStream_t s, int prof_kind) {
+  if (g.n_valid <= 0) g.n_valid = g.N;
+  gemm_run(ctx, g, gemm_plan(g), s, prof_kind);
 }
 
 void pack_conv3x3(const float* w, h16* out, int O, int I, int Opad, int Ipad, hipStream_t s) {

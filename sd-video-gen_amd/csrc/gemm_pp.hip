@@ -39,6 +39,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const GemmArgs g) {
   constexpr int NT = BN / 32;            // 16-wide n tiles per wave
   constexpr int MT = 4;                  // 16-high m tiles per wave
   constexpr int BMP = 256;
+  static_assert(BMP == PP_ROWS, "the row tile the plan counts (gemm_tiles.h)");
   constexpr int A_BYTES = BMP * 128, B_BYTES = BN * 128, STAGE = A_BYTES + B_BYTES;
   constexpr int NWS = 3;
   constexpr int NA = 4;                  // A DMA instructions per wave and slab (64 rows each across the 8 waves)
@@ -286,33 +287,8 @@ void gemm_pp_init_device() {
   HIP_OK(hipFuncSetAttribute((const void*)gemm_pp_kernel<160, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (256 * 128 + 160 * 128) + 1024));
 }
 
-int gemm_pp_bn(const GemmArgs& g) {
-  if (g.act == ACT_GEGLU) return 128;
-  // fewest serial rounds of workgroups (one per CU) x tile width; ties -> fewer padded columns
-  const int64_t tm = cdiv(g.M, 256);
-  int best = 128;
-  int64_t best_cost = -1, best_pad = 0;
-  for (int bn : {128, 160}) {
-    const int64_t tn = cdiv(g.N, bn);
-    const int64_t cost = ((tm * tn + 255) / 256) * bn, pad = tn * bn - g.N;
-    if (best_cost < 0 || cost < best_cost || (cost == best_cost && pad < best_pad)) { best = bn; best_cost = cost; best_pad = pad; }
-  }
-  return best;
-}
-
-// dense, unbatched, K a multiple of 64 and long enough, enough 256-row tiles to give every CU a workgroup
-bool gemm_pp_supported(const GemmArgs& g) {
-  static const int on = getenv("SVG_GEMM_PP") ? atoi(getenv("SVG_GEMM_PP")) : 1;
-  static const int min_kt = getenv("SVG_GEMM_PP_MINKT") ? atoi(getenv("SVG_GEMM_PP_MINKT")) : 16;
-  // wide outputs (the GEGLU projection at 32 x 32: N = 5120, K = 640) amortise the tile's unhidden prologue over enough columns at
-  // 10 slabs already: 0.248 against 0.258-0.262 ms on the 128-row kernel, same box; N = 1280 at K = 640 loses (0.081 against 0.073)
-  const int need_kt = g.N >= 2560 ? std::min(min_kt, 10) : min_kt;
-  if (!on || g.amode != A_DENSE || g.batch != 1 || g.splitk > 1 || g.out_f32 || (g.K & 63) != 0 || (g.K >> 6) < need_kt || g.A2) return false;
-  if (g.lda % 8 != 0 || g.ldb % 8 != 0 || g.bias_row) return false;
-  return (int64_t)cdiv(g.M, 256) * cdiv(g.N, gemm_pp_bn(g)) >= 192;
-}
-
-void launch_gemm_pp(const GemmArgs& g0, hipStream_t s) {
+// bn: the column-tile width of the plan (gemm_plan.cpp), 128 or 160
+void launch_gemm_pp(const GemmArgs& g0, int bn, hipStream_t s) {
   static const int gm_env = getenv("SVG_PP_GROUPM") ? atoi(getenv("SVG_PP_GROUPM")) : 4;
   GemmArgs g = g0;
   g.group_m = gm_env;
@@ -320,13 +296,13 @@ void launch_gemm_pp(const GemmArgs& g0, hipStream_t s) {
   // DMA instructions of a slab that ride among the MFMAs (see the merged loop)
   g.pp_dma_m = std::max(0, std::min(7, (int)svg_env_i64("SVG_PP_DMA_M", 6)));
 #ifdef PP_STAMP
-  const int tiles_dbg = cdiv(g.M, 256) * cdiv(g.N, gemm_pp_bn(g));
+  const int tiles_dbg = cdiv(g.M, 256) * cdiv(g.N, bn);
   unsigned long long* dbg = nullptr;
   HIP_OK(hipMalloc(&dbg, (size_t)tiles_dbg * 64 * sizeof(unsigned long long)));
   HIP_OK(hipMemsetAsync(dbg, 0, (size_t)tiles_dbg * 64 * sizeof(unsigned long long), s));
   g.slabs = (float*)dbg;
 #endif
-  if (gemm_pp_bn(g) == 160) launch_pp<160>(g, s);
+  if (bn == 160) launch_pp<160>(g, s);
   else launch_pp<128>(g, s);
 #ifdef PP_STAMP
   {
@@ -340,7 +316,7 @@ void launch_gemm_pp(const GemmArgs& g0, hipStream_t s) {
     for (int grp = 0; grp < 2; ++grp) {
       const double n = sum[grp][7] > 0 ? sum[grp][7] : 1, nw = (double)tiles_dbg * 4;
       fprintf(stderr, "[pp stamps] M%d N%d K%d BN%d dma_m %d grp %d: per slab (cycles) reads + DMA issue %.0f | waits %.0f | barrier in %.0f | MFMA segment %.0f | barrier out %.0f  = %.0f || loop per tile %.0f, slabs %.0f\n",
-              g.M, g.N, g.K, gemm_pp_bn(g), g.pp_dma_m, grp, sum[grp][0] / n, sum[grp][1] / n, sum[grp][2] / n, sum[grp][3] / n, sum[grp][4] / n,
+              g.M, g.N, g.K, bn, g.pp_dma_m, grp, sum[grp][0] / n, sum[grp][1] / n, sum[grp][2] / n, sum[grp][3] / n, sum[grp][4] / n,
               (sum[grp][0] + sum[grp][1] + sum[grp][2] + sum[grp][3] + sum[grp][4]) / n, sum[grp][5] / nw, n / nw);
     }
   }

@@ -32,8 +32,6 @@ namespace SDNS {
 
 namespace {
 
-constexpr int WS_ROWS = 128;
-constexpr int WS_PIECES = 100;                 // (n-tile, k-step) pieces of a column group: 10 x 10 at K = 320, 5 x 20 at K = 640
 constexpr int WS_W_BYTES = WS_PIECES * 1024;
 
 // KS = K / 32; RES: residual present; QKV: the fused q | k | V^T projection (column groups from GemmArgs::vt_n0 on write V^T)
@@ -41,6 +39,7 @@ template <int KS, bool RES, bool QKV = false>
 __global__ void __launch_bounds__(512, 2) gemm_ws_kernel(const GemmArgs g, int n_groups, int n_slices) {
   constexpr int NTG = WS_PIECES / KS;           // n-tiles (16 columns) per column group
   constexpr int GC = NTG * 16;                  // columns per group
+  static_assert(GC == ws_group_cols(KS * 32), "the column group the plan counts (gemm_tiles.h)");
   static_assert(NTG % 2 == 0, "n-tiles are processed in pairs (K = 320: 10 tiles of 16 columns)");
   constexpr int NTP = NTG / 2;                  // n-tile pairs
   // column (inside the group) of operand row r of n-tile j
@@ -251,26 +250,6 @@ int g_ws_cus = 0;       // compute units of the device (persistent grid = one wo
 
 }  // namespace
 
-int gemm_ws_groups(const GemmArgs& g) { return g.N / (WS_PIECES / (g.K / 32) * 16); }
-
-// problems the weight-stationary kernel takes: dense, 16-bit output, K = 320 / 640, whole column groups, unbatched (one W for all
-// rows), no split-K / GEGLU / row bias / per-sample bias / swapped LayerNorm / two-source A
-bool gemm_ws_supported(const GemmArgs& g) {
-  static const int on = getenv("SVG_GEMM_WS") ? atoi(getenv("SVG_GEMM_WS")) : 1;
-  if (!on) return false;
-  if (g.amode != A_DENSE || g.A2 || g.out_f32 || g.act == ACT_GEGLU || g.bias_row || g.bias_bn || g.ln_swapped || g.batch != 1) return false;
-  // K = 640 (80-column groups) builds and is correct but loses: two register sets of 80 A-fragment registers spill, and eight /
-  // sixteen column groups re-read A that often (69 vs 53 us at 28672 x 640 x 640): the tiled kernel keeps those shapes
-  if (g.K != 320) return false;
-  const int gc = WS_PIECES / (g.K / 32) * 16;
-  if (g.N % gc != 0 || g.N > 1280 || (g.n_valid > 0 && g.n_valid < g.N)) return false;
-  if (g.residual && (g.ldr & 7)) return false;            // 16-byte residual loads / stores (8 consecutive columns per lane)
-  if ((g.lda & 7) || (g.ldc & 7) || (g.ldb & 7)) return false;
-  if (g.vt_out && (g.vt_n0 % gc != 0 || g.vt_rows % 16 != 0 || (g.vt_ld & 3) || g.residual || g.gn_part || g.ln_part || g.act != ACT_NONE)) return false;
-  if (g.M < 16384) return false;                        // the tiled kernel's territory: too few 128-row tiles per CU to amortise the W load
-  return true;
-}
-
 void gemm_ws_init_device() {
   const int smem = ws_smem(160);
   HIP_OK(hipFuncSetAttribute((const void*)gemm_ws_kernel<10, false>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
@@ -283,9 +262,9 @@ void gemm_ws_init_device() {
   g_ws_cus = prop.multiProcessorCount;
 }
 
-void launch_gemm_ws(svg_ctx* ctx, const GemmArgs& g, hipStream_t s) {
-  const int ng = gemm_ws_groups(g);
-  const int gc = g.N / ng;
+// gc: the plan's columns per group (gemm_plan.cpp: ws_group_cols(K), whole groups)
+void launch_gemm_ws(svg_ctx* ctx, const GemmArgs& g, int gc, hipStream_t s) {
+  const int ng = g.N / gc;
   const int cus = g_ws_cus > 0 ? g_ws_cus : 256;
   const int tiles = cdiv(g.M, WS_ROWS);
   // row slices: a multiple of 8 (one per XCD position), as many as the CUs allow, not more than the tiles
@@ -296,7 +275,7 @@ void launch_gemm_ws(svg_ctx* ctx, const GemmArgs& g, hipStream_t s) {
   const bool res = g.residual != nullptr;
   if (g.vt_out) {
     hipLaunchKernelGGL((gemm_ws_kernel<10, false, true>), grid, dim3(512), smem, s, g, ng, n_slices);
-  } else {                                               // K = 320 (gemm_ws_supported: the K = 640 form lost to the tiled kernel and is gone)
+  } else {                                               // K = 320 (gemm_plan.cpp: the K = 640 form lost to the tiled kernel and is gone)
     SVG_CHECK(g.K == 320, "gemm_ws: K = %d", g.K);
     if (res) hipLaunchKernelGGL((gemm_ws_kernel<10, true>), grid, dim3(512), smem, s, g, ng, n_slices);
     else hipLaunchKernelGGL((gemm_ws_kernel<10, false>), grid, dim3(512), smem, s, g, ng, n_slices);

@@ -10,9 +10,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr int BM = 128;
-constexpr int BK = 64;
-
 // exact (erf) GELU without erf: gelu(x) = x Phi(x) = max(x, 0) - |x| Phi(-|x|), and the normal tail is smooth in the log domain:
 // log2 Phi(-a) is fitted on [0, 6] by a degree-6 polynomial (weighted for the error of a Phi(-a); |x| > 6 reuses the value at 6,
 // where |x| Phi(-|x|) < 1e-8 |x|).  |gelu - exact| <= 2.7e-7 in f32 (Abramowitz-Stegun 7.1.26, the previous form: 4.7e-7), and

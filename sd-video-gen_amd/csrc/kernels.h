@@ -1,6 +1,7 @@
 // Host-callable launchers of every HIP kernel family (gfx950).
 #pragma once
 #include "common.h"
+#include "gemm_tiles.h"
 
 // Everything down to the latent-Transformer section belongs to the Stable-Diffusion side and lives in namespace SDNS
 // (sd_bf16 or sd_f16, see common.h): these sources are compiled once per storage type.
@@ -62,7 +63,7 @@ struct GemmArgs {
   // GroupNorm statistics of the OUTPUT emitted by the tile epilogue (the consumer is a GroupNorm): per row tile and column
   // the sum and the sum of squares of the stored (bf16-rounded) values, gn_part[(tile_m * N + n) * 2 + {0,1}], written once per
   // tile in a fixed order (deterministic).  Row tile = 128 rows (igemm), 256 rows (gemm_pp) or a 16 x 16 pixel block (halo conv);
-  // only without split-K.  gemm_emits_gn() says whether a problem qualifies and how many rows a tile has.
+  // only without split-K.  gemm_plan()'s gn_rows says whether a problem qualifies and how many rows a tile has.
   float* gn_part = nullptr;
   // LayerNorm row sums of the stored (bf16-rounded) values, one partial per column tile: ln_part[(m * ln_tiles + tile_n) * 2 + {0,1}]
   // = sum, sum of squares of row m over the tile's columns (the consumer's ln_finish turns them into rstd, rstd * mean)
@@ -83,13 +84,21 @@ struct GemmArgs {
   const float* residual_f32 = nullptr;   // [M][ldr] f32 residual (out_f32 == 2 only; exclusive with `residual`; last: the offsets of the fields above stay put)
 };
 
-void launch_gemm(svg_ctx* ctx, const GemmArgs& g, hipStream_t s, int prof_kind);
-// the halo conv (conv_halo.hip) takes g / its channel-tile width
-bool conv_halo_supported(const GemmArgs& g);
-int conv_halo_bn(const GemmArgs& g);
-// rows per row tile of the kernel gemm_auto() would launch for g, or 0 when that launch cannot emit GroupNorm statistics
-// (split-K, batched, f32 / GEGLU output)
-int gemm_emits_gn(const GemmArgs& g);
+// The kernel a launch of g runs, decided once (gemm_plan.cpp): family, column tile (gemm_ws: columns per group), split-K, and what the
+// tile epilogue of that kernel can emit.  A caller that wants GroupNorm / LayerNorm statistics asks gemm_plan(g), fills gn_part /
+// ln_part (+ ln_tiles) from the answer and hands the SAME plan to gemm_auto(); svg_op_gemm_ex reports the first three fields.
+enum GemmFamily { GF_IGEMM = 0, GF_HALO = 1, GF_PP = 2, GF_WS = 3 };
+struct GemmPlan {
+  int family = GF_IGEMM, bn = 0, splitk = 1;
+  int gn_rows = 0;      // rows per GroupNorm row tile (GemmArgs::gn_part); 0: the launch cannot emit (split-K, batched, f32 / GEGLU output)
+  int ln_tiles = 0;     // LayerNorm column tiles (GemmArgs::ln_part); 0: it cannot (split-K, f32 / GEGLU output, conv, row bias ...)
+  bool operator==(const GemmPlan& o) const { return family == o.family && bn == o.bn && splitk == o.splitk && gn_rows == o.gn_rows && ln_tiles == o.ln_tiles; }
+};
+GemmPlan gemm_plan(const GemmArgs& g);
+// launches `plan` (split-K slabs from the arena) without deciding again; an error unless plan == gemm_plan(g) of g as handed in, with
+// gn_part / ln_part set only where the plan emits.  The short form plans and launches a problem that asks for no statistics.
+void gemm_auto(svg_ctx* ctx, GemmArgs g, const GemmPlan& plan, hipStream_t s, int prof_kind);
+void gemm_auto(svg_ctx* ctx, GemmArgs g, hipStream_t s, int prof_kind);
 // per-device kernel attributes (dynamic LDS limits) of every instantiation; called by svg_create after hipSetDevice
 void gemm_init_device();
 void gemm_pp_init_device();
@@ -128,16 +137,6 @@ void xattn_fused(svg_ctx* ctx, const h16* X, int ldx, const h16* R, int ldr, con
 void pack_ff2_perm(const float* w, h16* out, int N, int K, hipStream_t s);
 void ff_fused(svg_ctx* ctx, const h16* X, int ldx, const h16* W1, const float* b1, const float* s1, const float* rs, const float* rm,
               const h16* W2p, const float* b2, const h16* residual, int ldr, h16* out, int ldo, int M, hipStream_t s);
-// which kernel a launch of g runs: family, column tile (gemm_ws: columns per group) and split-K.  launch_gemm dispatches on it and
-// tags its profile entries with it; gemm_auto reports it (the test hook svg_op_gemm_ex returns it).  g as launched: splitk planned.
-enum GemmFamily { GF_IGEMM = 0, GF_HALO = 1, GF_PP = 2, GF_WS = 3 };
-struct GemmPath { int family = GF_IGEMM, bn = 0, splitk = 1; };
-GemmPath gemm_describe(const GemmArgs& g);
-// picks split-K from the shape, allocates slabs from the arena, launches; *path (optional): gemm_describe of what was launched
-void gemm_auto(svg_ctx* ctx, GemmArgs g, hipStream_t s, int prof_kind, GemmPath* path = nullptr);
-// a GemmArgs with vt_out set can only be served by the weight-stationary kernel: ask before launching
-bool gemm_fused_qkv_supported(const GemmArgs& g);
-
 // weight packing (device): f32 OIHW -> bf16 [Opad][ky][kx][Ipad]; f32 [N][K] -> bf16 [Npad][K]
 void pack_conv3x3(const float* w_oihw, h16* out, int O, int I, int Opad, int Ipad, hipStream_t s);
 void pack_linear(const float* w, h16* out, int N, int K, int Npad, hipStream_t s);
@@ -152,8 +151,6 @@ void pack_geglu(const float* w, const float* b, h16* wout, float* bout, int F, i
 // ------------------------------------------------------------------------------------------------
 // normalisation / softmax
 // ------------------------------------------------------------------------------------------------
-// column tiles a dense GEMM launch of g will use when it can emit LayerNorm row partials (0: it cannot — split-K, f32 / GEGLU output ...)
-int gemm_ln_tiles(const GemmArgs& g);
 // rs[m] = rstd, rm[m] = rstd * mean of row m from `tiles` partials per row (GemmArgs::ln_part)
 void ln_finish(svg_ctx* ctx, const float* part, int tiles, float* rs, float* rm, int M, int C, float eps, hipStream_t s);
 // per-row-tile column sums of a tensor, emitted by the epilogue that produced it (GemmArgs::gn_part)

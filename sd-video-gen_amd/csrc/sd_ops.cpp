@@ -198,11 +198,11 @@ int SVG_OP(svg_op_groupnorm_f32)(svg_ctx* ctx, const float* x, const float* gamm
 }
 
 // the whole GEMM epilogue contract on caller buffers (svg_hip.h: svg_gemm_desc): the descriptor goes into GemmArgs field by field and
-// through gemm_auto as the models call it; path = {family, column tile, split-K} of what gemm_auto launched.  Test hook.
+// through gemm_auto as the models call it; path = {family, column tile, split-K} of the plan that was launched.  Test hook.
 int SVG_OP(svg_op_gemm_ex)(svg_ctx* ctx, const svg_gemm_desc* d, int* path, void* stream) {
   API_BEGIN
   SVG_CHECK(d != nullptr, "gemm_ex: no descriptor");
-  GemmPath p;
+  GemmPlan p;
   run_planned(ctx, [&]() {
     GemmArgs g;
     g.amode = d->amode; g.H = d->H; g.W = d->W; g.Cin = d->Cin; g.Ho = d->Ho; g.Wo = d->Wo;
@@ -213,7 +213,8 @@ int SVG_OP(svg_op_gemm_ex)(svg_ctx* ctx, const svg_gemm_desc* d, int* path, void
     g.residual = (const h16*)d->residual; g.ldr = d->ldr; g.act = d->act; g.out_f32 = d->out_f32;
     g.ln_rs = d->ln_rs; g.ln_rm = d->ln_rm; g.ln_s = d->ln_s; g.ln_swapped = d->ln_swapped; g.ln_zstride = d->ln_zstride;
     g.vt_out = (h16*)d->vt_out; g.vt_n0 = d->vt_n0; g.vt_rows = d->vt_rows; g.vt_ld = d->vt_ld; g.vt_bs = d->vt_bs;
-    gemm_auto(ctx, g, (hipStream_t)stream, g.amode == A_DENSE ? PK_GEMM : PK_CONV3, &p);
+    p = gemm_plan(g);
+    gemm_auto(ctx, g, p, (hipStream_t)stream, g.amode == A_DENSE ? PK_GEMM : PK_CONV3);
   });
   if (path) { path[0] = p.family; path[1] = p.bn; path[2] = p.splitk; }
   API_END(ctx)
@@ -245,10 +246,10 @@ int SVG_OP(svg_op_gemm_lnstats)(svg_ctx* ctx, const uint16_t* A, const uint16_t*
     g.residual = (const h16*)residual; g.ldr = N; g.C = C; g.ldc = N;
     if (batch > 1) { g.batch = batch; g.sA = (int64_t)M * K; g.sB = 0; g.sC = (int64_t)M * N; }
     float* part = ctx->arena.get<float>((int64_t)batch * M * 16);
-    tiles = gemm_ln_tiles(g);
-    if (tiles > 8) tiles = 0;
+    const GemmPlan plan = gemm_plan(g);
+    tiles = plan.ln_tiles <= 8 ? plan.ln_tiles : 0;
     if (tiles > 0) { g.ln_part = part; g.ln_tiles = tiles; }
-    gemm_auto(ctx, g, (hipStream_t)stream, PK_GEMM);
+    gemm_auto(ctx, g, plan, (hipStream_t)stream, PK_GEMM);
     if (tiles > 0) ln_finish(ctx, part, tiles, rs, rm, batch * M, N, 1e-5f, (hipStream_t)stream);
     else ln_stats(ctx, (const h16*)C, rs, rm, batch * M, N, 1e-5f, (hipStream_t)stream);
   });

@@ -85,11 +85,11 @@ NormW load_norm(svg_ctx* ctx, WeightStore& ws, const std::string& prefix, int C)
   return n;
 }
 
-// fills emit->st when the launch gemm_auto() picks for g can leave the output's GroupNorm column sums (whole row tiles per sample)
-static void plan_gn_emit(GemmArgs& g, GnEmit* emit, int rows_per_sample) {
+// fills g.gn_part / emit->st when the planned launch of g can leave the output's GroupNorm column sums (whole row tiles per sample)
+static void plan_gn_emit(GemmArgs& g, const GemmPlan& plan, GnEmit* emit, int rows_per_sample) {
   static const int use_epi = getenv("SVG_GN_EPI") ? atoi(getenv("SVG_GN_EPI")) : 1;   // 0: A/B switch, statistics pass as before
   if (!use_epi || !emit || !emit->buf || rows_per_sample < 1024) return;   // small images take the single-launch GroupNorm (one read)
-  const int rows = gemm_emits_gn(g);
+  const int rows = plan.gn_rows;
   if (rows <= 0 || rows_per_sample % rows != 0) return;
   g.gn_part = emit->buf;
   emit->st.part = emit->buf;
@@ -169,13 +169,14 @@ void conv3x3(svg_ctx* ctx, const h16* x, const ConvW& cw, void* out, int B, int 
   g.residual = residual; g.ldr = cw.Opad;
   g.C = out; g.ldc = cw.Opad;
   g.residual_f32 = residual_f32;
-  plan_gn_emit(g, emit, g.Ho * g.Wo);
-  gemm_auto(ctx, g, s, PK_CONV3);
+  const GemmPlan plan = gemm_plan(g);
+  plan_gn_emit(g, plan, emit, g.Ho * g.Wo);
+  gemm_auto(ctx, g, plan, s, PK_CONV3);
 }
 
 int conv3x3_halo_width(const ConvW& cw, int B, int H, int W, int amode, int out_f32) {
-  const GemmArgs g = conv3x3_args(nullptr, cw, B, H, W, amode, out_f32);
-  return conv_halo_supported(g) ? conv_halo_bn(g) : 0;
+  const GemmPlan plan = gemm_plan(conv3x3_args(nullptr, cw, B, H, W, amode, out_f32));
+  return plan.family == GF_HALO ? plan.bn : 0;
 }
 
 void linear(svg_ctx* ctx, const h16* A, int lda, const PackedLinear& pl, void* C, int ldc, int M, int act, const h16* residual,
@@ -217,13 +218,14 @@ void linear(svg_ctx* ctx, const h16* A, int lda, const PackedLinear& pl, void* C
   g.bias = pl.b; g.act = act; g.residual = residual; g.ldr = ldr; g.C = C; g.ldc = ldc; g.out_f32 = out_f32;
   g.A2 = A2; g.lda2 = lda2; g.k_split = k_split;
   g.residual_f32 = residual_f32;
-  plan_gn_emit(g, emit, rows_per_sample);
+  const GemmPlan plan = gemm_plan(g);
+  plan_gn_emit(g, plan, emit, rows_per_sample);
   if (ln && ln->buf) {
     static const int use_ln = getenv("SVG_LN_EPI") ? atoi(getenv("SVG_LN_EPI")) : 1;    // 0: A/B switch, ln_stats pass as before
-    const int tiles = use_ln ? gemm_ln_tiles(g) : 0;
+    const int tiles = use_ln ? plan.ln_tiles : 0;
     if (tiles > 0 && tiles <= 5) { g.ln_part = ln->buf; g.ln_tiles = tiles; ln->tiles = tiles; }   // C = 1280 (8 tiles): the finish costs what the 8 us pass did
   }
-  gemm_auto(ctx, g, s, PK_GEMM);
+  gemm_auto(ctx, g, plan, s, PK_GEMM);
 }
 
 // per-device kernel attributes (dynamic LDS limits) of every kernel instantiation of this namespace

@@ -462,13 +462,14 @@ struct UnetRun {
       g.A = x; g.lda = C; g.Wt = wb; g.ldb = C; g.M = HW; g.N = C; g.K = C; g.n_valid = C;
       g.batch = N; g.sA = (int64_t)HW * C; g.sB = (int64_t)C * C; g.sC = (int64_t)HW * C;
       g.bias = bb; g.bias_zs = C; g.C = h; g.ldc = C;
+      const GemmPlan plan = gemm_plan(g);
       {
         static const int use_ln = getenv("SVG_LN_EPI") ? atoi(getenv("SVG_LN_EPI")) : 1;
-        const int tiles = use_ln ? gemm_ln_tiles(g) : 0;
+        const int tiles = use_ln ? plan.ln_tiles : 0;
         le.tiles = 0;
         if (tiles > 0 && tiles <= 5) { g.ln_part = le.buf; g.ln_tiles = tiles; le.tiles = tiles; }
       }
-      gemm_auto(ctx, g, s, PK_GEMM);
+      gemm_auto(ctx, g, plan, s, PK_GEMM);
       ctx->arena.pop();
     } else {
       h16* n0 = ctx->arena.get<h16>(P * C);
@@ -509,7 +510,8 @@ struct UnetRun {
         vt = ctx->arena.get<h16>((int64_t)N * C * HWp);
         g.vt_out = vt;
         static const int qkv_env = getenv("SVG_QKV_FUSED") ? atoi(getenv("SVG_QKV_FUSED")) : 1;
-        if (qkv_env && gemm_fused_qkv_supported(g)) { gemm_auto(ctx, g, s, PK_GEMM); fused = true; }
+        const GemmPlan plan = gemm_plan(g);      // V^T out of the epilogue: the weight-stationary kernel only
+        if (qkv_env && plan.family == GF_WS) { gemm_auto(ctx, g, plan, s, PK_GEMM); fused = true; }
       }
       if (!fused) {
         linear(ctx, a1, C, b.qk1, qk, 2 * C, M, ACT_NONE, nullptr, 0, 0, s, rs, rm);
