@@ -350,6 +350,66 @@ int svg_op_gemm_fp8(svg_ctx* ctx, const uint16_t* A, const uint16_t* W, const fl
 int svg_op_groupnorm(svg_ctx* ctx, const uint16_t* x, const float* gamma, const float* beta,
                      uint16_t* out, int B, int HW, int C, int groups, float eps, int silu,
                      void* stream);
+/* GroupNorm on a full descriptor, optionally forced onto one kernel path (test hook).  x (B,HW,C1) and x2 (B,HW,C2, or NULL with
+ * C2 = 0): the two sources of a channel concat [x | x2], 16-bit or (f32_in = 1) f32, separately allocated; gamma, beta (C1 + C2) f32
+ * on the device; out (B,HW,C1+C2) 16-bit.  part1 / part2 (optional): producer column sums of each source, [B * tps][C_src][2] =
+ * (sum, sum of squares) per row tile and channel, tps tiles per sample (the GemmArgs::gn_part layout).  C1 + C2 a multiple of 8 and
+ * of groups, C1 a multiple of 8, groups <= 64, C1 + C2 <= 8192.
+ * force = 0: the library's choice.  force = 1: exactly `kind` — 0 small<maxch, vw> (one launch; instantiated <5,8> <10,8> <5,4>
+ * <20,4>; needs channels per group and C1 multiples of vw and HW * cpg / vw <= 256 * maxch), 1 stats+apply (any shape),
+ * 2 finish+apply (needs part1, and part2 when C2 > 0).  A forced path the shape does not admit is an error before any launch.
+ * path (int[8], or NULL) receives {kind, maxch, vw, CV, PL, nchunk, nblk, threads}: CV channel vectors x PL pixel lanes per block
+ * of `threads` threads, the statistics grid (nchunk, B), the apply grid (nblk, B); zero where a path has none.
+ * svg_op_groupnorm_mx: the same inputs (16-bit, force = 0) through the MX fp8 apply pass (kind 3, finish+apply_mx): q (B*HW, Cp)
+ * e4m3 bytes and sc (B*HW, Cp/32) E8M0 bytes, Cp = C rounded up to 128 (padding channels: zero data, scale byte 127), stats
+ * (B,groups,2) = the (mean, rstd) table it used.  *fused = 0 (nothing written, path kind -1) when the pass does not serve the call:
+ * no column sums for a source, C % 32 != 0, or SVG_GN_MX=0 / SVG_GN_EPI=0.
+ * Numerics contract of every GroupNorm path (and of svg_op_gn_finish / svg_op_ln_finish): the variance is the one-pass form
+ * E[x^2] - mean^2 in f32.  With e = 2^-24, L the longest run of sequential f32 additions of the path (small<M,V>: M V + 8, at most 88;
+ * stats+apply: pixels per thread + 2048 / groups + nchunk; finish: column-sum entries per thread + 8) and k = |mean| / sigma of a group,
+ * rstd is within e (3 L + 5) (1 + k^2) / 2 relative of exact arithmetic on the same inputs, and so is the output next to its own
+ * rounding.  That reaches one output ulp (2^-7 bf16, 2^-10 fp16) at k = sqrt(2^18 / (3 L + 5)) in bf16 and sqrt(2^15 / (3 L + 5)) in
+ * fp16: k = 31 and 11 at L = 88; below that the result is the fp64 one to within two output roundings.  A constant group (var = 0) comes
+ * out as beta within |gamma| (L + 1) e |mean| rsqrt(eps).  The bound is a worst case; DESIGN.md lists the errors measured against fp64.
+ * An all-zero 32-channel block of the MX output carries scale byte 127 (svg_op_quant_mx writes 0 there); both decode to zeros. */
+typedef struct svg_gn_desc {
+  const void *x, *x2;
+  int C1, C2, f32_in;
+  const float *gamma, *beta;
+  uint16_t* out;
+  int B, HW, groups;
+  float eps;
+  int silu;
+  const float* part1;
+  int tps1;
+  const float* part2;
+  int tps2;
+  int force, kind, maxch, vw;
+  uint8_t *q, *sc;
+  float* stats;
+} svg_gn_desc;
+int svg_op_groupnorm_ex(svg_ctx* ctx, const svg_gn_desc* desc, int* path, void* stream);
+int svg_op_groupnorm_mx(svg_ctx* ctx, const svg_gn_desc* desc, int* fused, int* path, void* stream);
+/* (mean, rstd) per (sample, group) from producer column sums (layout as part1 / part2 above) -> stats (B,groups,2) (test hook) */
+int svg_op_gn_finish(svg_ctx* ctx, const float* part1, int C1, int tps1, const float* part2, int C2, int tps2, float* stats, int B,
+                     int HW, int groups, float eps, void* stream);
+/* GroupNorm folded into a following 1x1 projection: Wb (B,N,C) 16-bit = W[n][c] gamma[c] rstd[b][g(c)], bb (B,N) = bias[n] (0 when
+ * NULL) + sum_c W[n][c] (beta[c] - mean rstd gamma[c]); W (N,C), stats (B,groups,2) f32 on the device (test hook) */
+int svg_op_gn_fold_weights(svg_ctx* ctx, const float* W, const float* bias, const float* gamma, const float* beta, const float* stats,
+                           uint16_t* Wb, float* bb, int B, int N, int C, int groups, void* stream);
+/* LayerNorm row statistics rs[m] = rstd, rm[m] = rstd * mean of x (M,C) 16-bit (two passes over the row in registers), and the
+ * same from `tiles` (sum, sum of squares) partials per row, part (M,tiles,2) (one pass: E[x^2] - mean^2).  C % 8 == 0, C <= 2048. */
+int svg_op_ln_stats(svg_ctx* ctx, const uint16_t* x, float* rs, float* rm, int M, int C, float eps, void* stream);
+int svg_op_ln_finish(svg_ctx* ctx, const float* part, int tiles, float* rs, float* rm, int M, int C, float eps, void* stream);
+/* rows of f32 scores (row stride ld_in) -> 16-bit softmax(s * scale) (row stride ld_out); output columns cols .. ld_out - 1 are
+ * written as zero, input columns >= cols are never read */
+int svg_op_softmax_rows(svg_ctx* ctx, const float* s_in, uint16_t* p_out, int64_t rows, int cols, int ld_in, int ld_out, float scale,
+                        void* stream);
+/* LayerNorm folding at load time: bias_out[n] = bias_in[n] (0 when NULL) + sum_k w[n][k] beta[k], then w[n][k] *= gamma[k] in place;
+ * and out[n] = sum_k w[n][k] of a 16-bit (N,K) matrix */
+int svg_op_fold_ln(svg_ctx* ctx, float* w, const float* bias_in, const float* gamma, const float* beta, float* bias_out, int N, int K,
+                   void* stream);
+int svg_op_rowsum(svg_ctx* ctx, const uint16_t* w, float* out, int N, int K, void* stream);
 /* LayerNorm over the last dim of (M,C) bf16. */
 int svg_op_layernorm(svg_ctx* ctx, const uint16_t* x, const float* gamma, const float* beta,
                      uint16_t* out, int M, int C, float eps, void* stream);
@@ -428,6 +488,14 @@ int svg_op_attention_f16(svg_ctx* ctx, const uint16_t* q, const uint16_t* k, con
 int svg_op_attention_ex_f16(svg_ctx* ctx, const svg_attn_desc* desc, int* path, void* stream);
 int svg_op_vae_attention_f16(svg_ctx* ctx, const uint16_t* q, const uint16_t* k, int ldqk, int64_t qkb, const uint16_t* vt, int ldvt,
                              int64_t vtb, uint16_t* out, int ldo, int64_t ob, int B, int S, int C, void* stream);
+int svg_op_groupnorm_ex_f16(svg_ctx* ctx, const svg_gn_desc* desc, int* path, void* stream);
+int svg_op_groupnorm_mx_f16(svg_ctx* ctx, const svg_gn_desc* desc, int* fused, int* path, void* stream);
+int svg_op_gn_fold_weights_f16(svg_ctx* ctx, const float* W, const float* bias, const float* gamma, const float* beta, const float* stats,
+                               uint16_t* Wb, float* bb, int B, int N, int C, int groups, void* stream);
+int svg_op_ln_stats_f16(svg_ctx* ctx, const uint16_t* x, float* rs, float* rm, int M, int C, float eps, void* stream);
+int svg_op_softmax_rows_f16(svg_ctx* ctx, const float* s_in, uint16_t* p_out, int64_t rows, int cols, int ld_in, int ld_out, float scale,
+                            void* stream);
+int svg_op_rowsum_f16(svg_ctx* ctx, const uint16_t* w, float* out, int N, int K, void* stream);
 /* f32 skinny GEMM of the latent Transformer: Y[M,N] = X[M,K] * W[N,K]^T + bias (relu_in: X:=max(X,0)). */
 int svg_op_xf_gemm(svg_ctx* ctx, const float* X, const float* W, const float* bias, float* Y,
                    int M, int N, int K, int relu_in, void* stream);

@@ -59,6 +59,14 @@ class AttnDesc(C.Structure):
                 ("scale", _f), ("force", _i), ("kernel", _i), ("qblocks", _i), ("nst", _i), ("bc", _i), ("hv", _i)]
 
 
+class GnDesc(C.Structure):
+    """struct svg_gn_desc (include/svg_hip.h): the GroupNorm launch descriptor of svg_op_groupnorm_ex / svg_op_groupnorm_mx."""
+    _fields_ = [("x", _vp), ("x2", _vp), ("C1", _i), ("C2", _i), ("f32_in", _i), ("gamma", _vp), ("beta", _vp), ("out", _vp),
+                ("B", _i), ("HW", _i), ("groups", _i), ("eps", _f), ("silu", _i),
+                ("part1", _vp), ("tps1", _i), ("part2", _vp), ("tps2", _i),
+                ("force", _i), ("kind", _i), ("maxch", _i), ("vw", _i), ("q", _vp), ("sc", _vp), ("stats", _vp)]
+
+
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/svg_hip.h
 SIGNATURES = {
     "svg_create": [_i, C.POINTER(_vp)],
@@ -107,6 +115,15 @@ SIGNATURES = {
     "svg_op_conv3x3_f32s": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, C.POINTER(_i),
                             C.POINTER(_i), _vp],
     "svg_op_groupnorm_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
+    "svg_op_groupnorm_ex": [_vp, C.POINTER(GnDesc), C.POINTER(_i), _vp],
+    "svg_op_groupnorm_mx": [_vp, C.POINTER(GnDesc), C.POINTER(_i), C.POINTER(_i), _vp],
+    "svg_op_gn_finish": [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _f, _vp],
+    "svg_op_gn_fold_weights": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "svg_op_ln_stats": [_vp, _vp, _vp, _vp, _i, _i, _f, _vp],
+    "svg_op_ln_finish": [_vp, _vp, _i, _vp, _vp, _i, _i, _f, _vp],
+    "svg_op_softmax_rows": [_vp, _vp, _vp, _i64, _i, _i, _i, _f, _vp],
+    "svg_op_fold_ln": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    "svg_op_rowsum": [_vp, _vp, _vp, _i, _i, _vp],
     "svg_op_layernorm": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp],
     "svg_op_attention": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _f, _vp],
     "svg_op_attention_ex": [_vp, C.POINTER(AttnDesc), C.POINTER(_i), _vp],
@@ -125,7 +142,8 @@ SIGNATURES = {
 }
 # fp16-storage twins of the 16-bit operator hooks (svg_op_<name>_f16: same arguments)
 for _n in ("gemm", "gemm_ex", "conv3x3", "conv3x3_gn", "conv3x3_mx", "gemm_lnstats", "gemm_cat", "ff_fused", "xattn_fused", "quant_mx", "gemm_fp8", "groupnorm", "layernorm",
-           "attention", "attention_ex", "vae_attention", "conv3x3_f32s", "groupnorm_f32"):
+           "attention", "attention_ex", "vae_attention", "conv3x3_f32s", "groupnorm_f32", "groupnorm_ex", "groupnorm_mx", "gn_fold_weights", "ln_stats",
+           "softmax_rows", "rowsum"):
     SIGNATURES["svg_op_%s_f16" % _n] = SIGNATURES["svg_op_" + _n]
 SIGNATURES["svg_model_dtype"] = [_vp, _i]
 _RESTYPES = {"svg_destroy": None, "svg_env_refresh": None, "svg_model_dtype": C.c_char_p, "svg_last_error": C.c_char_p, "svg_version": C.c_char_p,

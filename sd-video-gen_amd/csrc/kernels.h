@@ -167,9 +167,34 @@ void groupnorm(svg_ctx* ctx, const h16* x, int C1, const h16* x2, int C2, const 
 // the same on an f32 input (the VAE's f32 residual stream), one source; st: the column sums of the stored f32 values (out_f32 == 2 epilogues)
 void groupnorm_f32(svg_ctx* ctx, const float* x, int C, const float* gamma, const float* beta, h16* out, int B, int HW, int groups, float eps,
                    int silu, hipStream_t s, const GnStats* st = nullptr);
-// the same with an MX fp8 output (norm.hip: gn_apply_mx_kernel) for conv_halo_fp8; false = the caller takes groupnorm() + quant_act_mx()
+// the kernel path one GroupNorm call takes and its launch geometry.  GN_SMALL: gn_small_kernel<maxch, vw> (one launch, grid
+// (groups, B), 256 threads); GN_STATS_APPLY: gn_stats_kernel (grid (nchunk, B)) + gn_apply_kernel (grid (nblk, B)); GN_FINISH_APPLY:
+// gn_finish_kernel on the producers' column sums + gn_apply_kernel; GN_FINISH_APPLY_MX: gn_finish_kernel + gn_apply_mx_kernel (CV counts
+// the padded channel vectors there); GN_NONE: an MX-output call the fused pass does not serve (groupnorm_mx returns false).
+// CV channel vectors x PL pixel lanes = the live threads of a stats / apply block of `threads` threads.
+enum GnKind { GN_NONE = -1, GN_SMALL = 0, GN_STATS_APPLY = 1, GN_FINISH_APPLY = 2, GN_FINISH_APPLY_MX = 3 };
+struct GnPath {
+  int kind = GN_NONE, maxch = 0, vw = 0;
+  int CV = 0, PL = 0, nchunk = 0, nblk = 0, threads = 0;
+};
+struct GnShape {
+  int C1 = 0, C2 = 0, B = 0, HW = 0, groups = 0;
+  bool f32_in = false;       // f32 input (the VAE's f32 residual stream), else 16-bit
+  bool have_stats = false;   // valid producer column sums for every source
+  bool mx_out = false;       // MX fp8 output (groupnorm_mx)
+};
+// the same with an MX fp8 output (norm.hip: gn_apply_mx_kernel) for conv_halo_fp8; false = the caller takes groupnorm() + quant_act_mx().
+// stats_out (optional, B * groups * 2 floats): receives the (mean, rstd) table the apply pass used
 bool groupnorm_mx(svg_ctx* ctx, const h16* x, int C1, const h16* x2, int C2, const float* gamma, const float* beta, uint8_t* q, uint8_t* sc,
-                  int B, int HW, int groups, float eps, int silu, hipStream_t s, const GnStats* st1, const GnStats* st2);
+                  int B, int HW, int groups, float eps, int silu, hipStream_t s, const GnStats* st1, const GnStats* st2,
+                  float* stats_out = nullptr, GnPath* ran = nullptr);
+// what groupnorm / groupnorm_f32 / groupnorm_mx launch for `a`: the SVG_GN_NOSMALL / SMALL_VW8 / EPI / MX choice, or `force`
+// ({kind, maxch, vw}; not for mx_out) when that path is valid for the shape — otherwise an error, as for an unsupported shape
+GnPath groupnorm_describe(const GnShape& a, const GnPath* force = nullptr);
+// groupnorm / groupnorm_f32 with a forced path and a report of what ran (x, x2: h16 or float by f32_in)
+void groupnorm_ex(svg_ctx* ctx, const void* x, int C1, const void* x2, int C2, bool f32_in, const float* gamma, const float* beta, h16* out,
+                  int B, int HW, int groups, float eps, int silu, hipStream_t s, const GnStats* st1, const GnStats* st2, const GnPath* force,
+                  GnPath* ran);
 // (mean, rstd) per (sample, group) from producer column sums -> stats[B][groups][2]
 void gn_finish(svg_ctx* ctx, const GnStats& st1, int C1, const GnStats* st2, int C2, float* stats, int B, int HW, int groups, float eps,
                hipStream_t s);

@@ -538,38 +538,94 @@ void gn_fold_weights(const float* W, const float* bias, const float* gamma, cons
   check_launch("gn_fold_weights");
 }
 
+// ~16 pixels per thread, at least enough blocks to fill the chip
+static int gn_apply_blocks(int B, int HW, int PL) { return std::max(1, std::min(HW / PL, std::max(HW / (PL * 16), (2048 + B - 1) / B))); }
+
+GnPath groupnorm_describe(const GnShape& a, const GnPath* force) {
+  static const int no_small = getenv("SVG_GN_NOSMALL") ? atoi(getenv("SVG_GN_NOSMALL")) : 0;
+  static const int vw8 = getenv("SVG_GN_SMALL_VW8") ? atoi(getenv("SVG_GN_SMALL_VW8")) : 1;
+  static const int use_epi = getenv("SVG_GN_EPI") ? atoi(getenv("SVG_GN_EPI")) : 1;
+  static const int fused_mx = getenv("SVG_GN_MX") ? atoi(getenv("SVG_GN_MX")) : 1;
+  const int C1 = a.C1, C2 = a.C2, C = C1 + C2, B = a.B, HW = a.HW, groups = a.groups;
+  GnPath p;
+  if (a.mx_out) {
+    // MX fp8 output: the fused pass or none (the caller then runs groupnorm() + quant_act_mx()); never an error, never forced
+    if (a.f32_in || !a.have_stats || !fused_mx || !use_epi || B <= 0 || HW <= 0 || groups <= 0) return p;
+    if (C % groups != 0 || C % 32 != 0 || C1 % 8 != 0 || groups > 64) return p;
+    const int CVp = (int)align_up(C, 128) / 8;
+    if (CVp > 1024) return p;
+    p.kind = GN_FINISH_APPLY_MX;
+    p.CV = CVp; p.PL = std::max(1, 256 / CVp);
+    p.threads = std::max((CVp * p.PL + 63) / 64 * 64, 64);
+    p.nblk = gn_apply_blocks(B, HW, p.PL);
+    return p;
+  }
+  SVG_CHECK(B > 0 && HW > 0 && C1 > 0 && C2 >= 0 && groups > 0, "groupnorm: B=%d HW=%d C1=%d C2=%d groups=%d unsupported", B, HW, C1, C2, groups);
+  SVG_CHECK(C % groups == 0 && C % 8 == 0 && C1 % 8 == 0 && groups <= 64, "groupnorm: C=%d groups=%d unsupported", C, groups);
+  const int CV = C / 8, cpg = C / groups;
+  SVG_CHECK(CV <= 1024, "groupnorm: C too large");
+  // gn_small_kernel<maxch, vw>: a (sample, group) of HW x cpg values in vw-channel pieces, at most maxch per thread of a 256-thread block
+  auto small_fits = [&](int maxch, int vw) { return cpg % vw == 0 && C1 % vw == 0 && (int64_t)HW * (cpg / vw) <= 256 * maxch; };
+  if (force) {
+    p.kind = force->kind;
+    if (p.kind == GN_SMALL) {
+      p.maxch = force->maxch; p.vw = force->vw;
+      const bool inst = (p.vw == 8 && (p.maxch == 5 || p.maxch == 10)) || (p.vw == 4 && (p.maxch == 5 || p.maxch == 20));
+      SVG_CHECK(inst, "groupnorm: small<%d,%d> is not instantiated", p.maxch, p.vw);
+      SVG_CHECK(small_fits(p.maxch, p.vw), "groupnorm: small<%d,%d> does not hold HW=%d x %d channels per group (C1=%d)", p.maxch, p.vw, HW, cpg, C1);
+    } else {
+      SVG_CHECK(p.kind == GN_STATS_APPLY || p.kind == GN_FINISH_APPLY, "groupnorm: no path %d", p.kind);
+      SVG_CHECK(p.kind != GN_FINISH_APPLY || a.have_stats, "groupnorm: finish+apply needs the producers' column sums");
+    }
+  } else if (!no_small && HW <= 256 && small_fits(20, 4)) {
+    p.kind = GN_SMALL;
+    if (vw8 && cpg % 8 == 0 && C1 % 8 == 0) { p.vw = 8; p.maxch = small_fits(5, 8) ? 5 : 10; }   // 16-byte pieces
+    else { p.vw = 4; p.maxch = small_fits(5, 4) ? 5 : 20; }
+  } else {
+    p.kind = (use_epi && a.have_stats) ? GN_FINISH_APPLY : GN_STATS_APPLY;
+  }
+  if (p.kind == GN_SMALL) { p.threads = 256; return p; }
+  p.CV = CV; p.PL = std::max(1, 256 / CV);
+  p.threads = std::max((CV * p.PL + 63) / 64 * 64, 64);
+  p.nblk = gn_apply_blocks(B, HW, p.PL);
+  if (p.kind == GN_STATS_APPLY) {
+    int nchunk = std::max(1, std::min(64, HW / (p.PL * 8)));
+    // enough blocks to fill the chip at small batch
+    while (nchunk * 2 <= 64 && (int64_t)nchunk * B < 512 && HW / (nchunk * 2) >= p.PL * 2) nchunk *= 2;
+    p.nchunk = nchunk;
+  }
+  return p;
+}
+
+template <int MAXCH, int VW, typename T>
+static void launch_gn_small(const T* x, int C1, const T* x2, int C2, const float* gamma, const float* beta, h16* out, int B, int HW, int groups,
+                            float eps, int silu, hipStream_t s) {
+  hipLaunchKernelGGL((gn_small_kernel<MAXCH, VW, T>), dim3(groups, B), dim3(256), 0, s, x, C1, x2, C2, gamma, beta, out, HW, groups, eps, silu);
+}
+
 template <typename T>
 static void groupnorm_t(svg_ctx* ctx, const T* x, int C1, const T* x2, int C2, const float* gamma, const float* beta,
-                        h16* out, int B, int HW, int groups, float eps, int silu, hipStream_t s, const GnStats* st1, const GnStats* st2) {
+                        h16* out, int B, int HW, int groups, float eps, int silu, hipStream_t s, const GnStats* st1, const GnStats* st2,
+                        const GnPath* force, GnPath* ran) {
   const int C = C1 + C2;
-  SVG_CHECK(C % groups == 0 && C % 8 == 0 && C1 % 8 == 0 && groups <= 64, "groupnorm: C=%d groups=%d unsupported", C, groups);
-  const int CV = C / 8;
-  SVG_CHECK(CV <= 1024, "groupnorm: C too large");
-  {
-    const int cpg = C / groups;
-    static const int no_small = getenv("SVG_GN_NOSMALL") ? atoi(getenv("SVG_GN_NOSMALL")) : 0;
-    if (!no_small && HW <= 256 && cpg % 4 == 0 && C1 % 4 == 0 && (int64_t)HW * (cpg / 4) <= 256 * 20) {
-      if (!SVG_LAUNCHING(ctx)) return;
-      char tag[96];
-      snprintf(tag, sizeof(tag), "small_B%d_HW%d_C%d", B, HW, C);
-      ProfScope ps(ctx, PK_GNORM, s, 0, (double)B * HW * C * (sizeof(T) + 2), tag);
-      static const int vw8 = getenv("SVG_GN_SMALL_VW8") ? atoi(getenv("SVG_GN_SMALL_VW8")) : 1;
-      if (vw8 && cpg % 8 == 0 && C1 % 8 == 0) {             // 16-byte pieces
-        if ((int64_t)HW * (cpg / 8) <= 256 * 5)
-          hipLaunchKernelGGL((gn_small_kernel<5, 8, T>), dim3(groups, B), dim3(256), 0, s, x, C1, x2, C2, gamma, beta, out, HW, groups, eps, silu);
-        else
-          hipLaunchKernelGGL((gn_small_kernel<10, 8, T>), dim3(groups, B), dim3(256), 0, s, x, C1, x2, C2, gamma, beta, out, HW, groups, eps, silu);
-      } else if ((int64_t)HW * (cpg / 4) <= 256 * 5)
-        hipLaunchKernelGGL((gn_small_kernel<5, 4, T>), dim3(groups, B), dim3(256), 0, s, x, C1, x2, C2, gamma, beta, out, HW, groups, eps, silu);
-      else
-        hipLaunchKernelGGL((gn_small_kernel<20, 4, T>), dim3(groups, B), dim3(256), 0, s, x, C1, x2, C2, gamma, beta, out, HW, groups, eps, silu);
-      check_launch("gn_small");
-      return;
-    }
+  GnShape sh;
+  sh.C1 = C1; sh.C2 = C2; sh.B = B; sh.HW = HW; sh.groups = groups; sh.f32_in = sizeof(T) == 4;
+  sh.have_stats = st1 && st1->valid() && (C2 == 0 || (st2 && st2->valid()));
+  const GnPath p = groupnorm_describe(sh, force);
+  if (ran) *ran = p;
+  if (p.kind == GN_SMALL) {
+    if (!SVG_LAUNCHING(ctx)) return;
+    char tag[96];
+    snprintf(tag, sizeof(tag), "small_B%d_HW%d_C%d", B, HW, C);
+    ProfScope ps(ctx, PK_GNORM, s, 0, (double)B * HW * C * (sizeof(T) + 2), tag);
+    if (p.vw == 8 && p.maxch == 5) launch_gn_small<5, 8, T>(x, C1, x2, C2, gamma, beta, out, B, HW, groups, eps, silu, s);
+    else if (p.vw == 8) launch_gn_small<10, 8, T>(x, C1, x2, C2, gamma, beta, out, B, HW, groups, eps, silu, s);
+    else if (p.maxch == 5) launch_gn_small<5, 4, T>(x, C1, x2, C2, gamma, beta, out, B, HW, groups, eps, silu, s);
+    else launch_gn_small<20, 4, T>(x, C1, x2, C2, gamma, beta, out, B, HW, groups, eps, silu, s);
+    check_launch("gn_small");
+    return;
   }
-  const int PL = std::max(1, 256 / CV);
-  static const int use_epi = getenv("SVG_GN_EPI") ? atoi(getenv("SVG_GN_EPI")) : 1;
-  if (use_epi && st1 && st1->valid() && (C2 == 0 || (st2 && st2->valid()))) {
+  if (p.kind == GN_FINISH_APPLY) {
     // the producers' epilogues left per-tile column sums: no statistics pass over the tensor, one apply pass
     ctx->arena.push();
     float* stats = ctx->arena.get<float>((int64_t)B * groups * 2);
@@ -578,40 +634,31 @@ static void groupnorm_t(svg_ctx* ctx, const T* x, int C1, const T* x2, int C2, c
       char tag[96];
       snprintf(tag, sizeof(tag), "apply_B%d_HW%d_C%d", B, HW, C);
       ProfScope ps(ctx, PK_GNORM, s, 0, (double)B * HW * C * (sizeof(T) + 2), tag);
-      const int threads = std::max((CV * PL + 63) / 64 * 64, 64);
-      int nblk = std::max(1, std::min(HW / PL, std::max(HW / (PL * 16), (2048 + B - 1) / B)));
-      hipLaunchKernelGGL(gn_apply_kernel<T>, dim3(nblk, B), dim3(threads), 0, s, x, C1, x2, C2, stats, gamma, beta, out, HW, groups, 0, eps,
-                         silu, CV, PL);
+      hipLaunchKernelGGL(gn_apply_kernel<T>, dim3(p.nblk, B), dim3(p.threads), 0, s, x, C1, x2, C2, stats, gamma, beta, out, HW, groups, 0, eps,
+                         silu, p.CV, p.PL);
       check_launch("gn_apply");
     }
     ctx->arena.pop();
     return;
   }
-  int nchunk = std::max(1, std::min(64, HW / (PL * 8)));
-  // enough blocks to fill the chip at small batch
-  while (nchunk * 2 <= 64 && (int64_t)nchunk * B < 512 && HW / (nchunk * 2) >= PL * 2) nchunk *= 2;
   ctx->arena.push();
-  float* partial = ctx->arena.get<float>((int64_t)B * nchunk * groups * 2);
+  float* partial = ctx->arena.get<float>((int64_t)B * p.nchunk * groups * 2);
   if (SVG_LAUNCHING(ctx)) {
     const double bytes = (double)B * HW * C * sizeof(T);
     char tag[96];
     snprintf(tag, sizeof(tag), "stats_B%d_HW%d_C%d", B, HW, C);
     {
       ProfScope ps(ctx, PK_GNORM, s, 0, bytes, tag);
-      const int threads = (CV * PL + 63) / 64 * 64;
-      const size_t sh = (size_t)PL * C * 2 * sizeof(float);
-      hipLaunchKernelGGL(gn_stats_kernel<T>, dim3(nchunk, B), dim3(std::max(threads, 64)), sh, s, x, C1, x2, C2, partial, HW,
-                         groups, nchunk, CV, PL);
+      const size_t sh = (size_t)p.PL * C * 2 * sizeof(float);
+      hipLaunchKernelGGL(gn_stats_kernel<T>, dim3(p.nchunk, B), dim3(p.threads), sh, s, x, C1, x2, C2, partial, HW,
+                         groups, p.nchunk, p.CV, p.PL);
       check_launch("gn_stats");
     }
     {
       tag[0] = 'a'; tag[1] = 'p'; tag[2] = 'p'; tag[3] = 'l'; tag[4] = 'y';
       ProfScope ps(ctx, PK_GNORM, s, 0, 2 * bytes, tag);
-      const int threads = std::max((CV * PL + 63) / 64 * 64, 64);
-      // ~16 pixels per thread, at least enough blocks to fill the chip
-      int nblk = std::max(1, std::min(HW / PL, std::max(HW / (PL * 16), (2048 + B - 1) / B)));
-      hipLaunchKernelGGL(gn_apply_kernel<T>, dim3(nblk, B), dim3(threads), 0, s, x, C1, x2, C2, partial, gamma, beta, out, HW,
-                         groups, nchunk, eps, silu, CV, PL);
+      hipLaunchKernelGGL(gn_apply_kernel<T>, dim3(p.nblk, B), dim3(p.threads), 0, s, x, C1, x2, C2, partial, gamma, beta, out, HW,
+                         groups, p.nchunk, eps, silu, p.CV, p.PL);
       check_launch("gn_apply");
     }
   }
@@ -620,36 +667,41 @@ static void groupnorm_t(svg_ctx* ctx, const T* x, int C1, const T* x2, int C2, c
 
 void groupnorm(svg_ctx* ctx, const h16* x, int C1, const h16* x2, int C2, const float* gamma, const float* beta,
                h16* out, int B, int HW, int groups, float eps, int silu, hipStream_t s, const GnStats* st1, const GnStats* st2) {
-  groupnorm_t<h16>(ctx, x, C1, x2, C2, gamma, beta, out, B, HW, groups, eps, silu, s, st1, st2);
+  groupnorm_t<h16>(ctx, x, C1, x2, C2, gamma, beta, out, B, HW, groups, eps, silu, s, st1, st2, nullptr, nullptr);
 }
 void groupnorm_f32(svg_ctx* ctx, const float* x, int C, const float* gamma, const float* beta, h16* out, int B, int HW, int groups, float eps,
                    int silu, hipStream_t s, const GnStats* st) {
-  groupnorm_t<float>(ctx, x, C, nullptr, 0, gamma, beta, out, B, HW, groups, eps, silu, s, st, nullptr);
+  groupnorm_t<float>(ctx, x, C, nullptr, 0, gamma, beta, out, B, HW, groups, eps, silu, s, st, nullptr, nullptr, nullptr);
+}
+void groupnorm_ex(svg_ctx* ctx, const void* x, int C1, const void* x2, int C2, bool f32_in, const float* gamma, const float* beta, h16* out,
+                  int B, int HW, int groups, float eps, int silu, hipStream_t s, const GnStats* st1, const GnStats* st2, const GnPath* force,
+                  GnPath* ran) {
+  if (f32_in) groupnorm_t<float>(ctx, (const float*)x, C1, (const float*)x2, C2, gamma, beta, out, B, HW, groups, eps, silu, s, st1, st2, force, ran);
+  else groupnorm_t<h16>(ctx, (const h16*)x, C1, (const h16*)x2, C2, gamma, beta, out, B, HW, groups, eps, silu, s, st1, st2, force, ran);
 }
 
 // GroupNorm (+SiLU) whose output is MX fp8 (e4m3 [B*HW][Cp] + E8M0 [B*HW][Cp/32], Cp = C rounded up to 128): the statistics must
 // come from the producers' epilogues (st1 / st2 valid); returns false when they do not, or the shape does not fit the apply kernel —
-// the caller then runs groupnorm() and quant_act_mx().  tmp_stats: B * groups * 2 floats of workspace.
+// the caller then runs groupnorm() and quant_act_mx().  stats_out: B * groups * 2 floats for the (mean, rstd) table, else workspace.
 bool groupnorm_mx(svg_ctx* ctx, const h16* x, int C1, const h16* x2, int C2, const float* gamma, const float* beta, uint8_t* q, uint8_t* sc,
-                  int B, int HW, int groups, float eps, int silu, hipStream_t s, const GnStats* st1, const GnStats* st2) {
+                  int B, int HW, int groups, float eps, int silu, hipStream_t s, const GnStats* st1, const GnStats* st2, float* stats_out,
+                  GnPath* ran) {
   const int C = C1 + C2;
-  static const int use_epi = getenv("SVG_GN_EPI") ? atoi(getenv("SVG_GN_EPI")) : 1;
-  static const int fused = getenv("SVG_GN_MX") ? atoi(getenv("SVG_GN_MX")) : 1;
-  if (!fused || !use_epi || !st1 || !st1->valid() || (C2 != 0 && !(st2 && st2->valid()))) return false;
-  if (C % groups != 0 || C % 32 != 0 || C1 % 8 != 0 || groups > 64) return false;
-  const int Cp = (int)align_up(C, 128), CVp = Cp / 8;
-  if (CVp > 1024) return false;
-  const int PL = std::max(1, 256 / CVp);
+  GnShape sh;
+  sh.C1 = C1; sh.C2 = C2; sh.B = B; sh.HW = HW; sh.groups = groups; sh.mx_out = true;
+  sh.have_stats = st1 && st1->valid() && (C2 == 0 || (st2 && st2->valid()));
+  const GnPath p = groupnorm_describe(sh);
+  if (ran) *ran = p;
+  if (p.kind != GN_FINISH_APPLY_MX) return false;
+  const int Cp = p.CV * 8;
   ctx->arena.push();
-  float* stats = ctx->arena.get<float>((int64_t)B * groups * 2);
+  float* stats = stats_out ? stats_out : ctx->arena.get<float>((int64_t)B * groups * 2);
   gn_finish(ctx, *st1, C1, C2 ? st2 : nullptr, C2, stats, B, HW, groups, eps, s);
   if (SVG_LAUNCHING(ctx)) {
     char tag[96];
     snprintf(tag, sizeof(tag), "apply_mx_B%d_HW%d_C%d", B, HW, C);
     ProfScope ps(ctx, PK_GNORM, s, 0, (double)B * HW * (2.0 * C + Cp + Cp / 32), tag);
-    const int threads = std::max((CVp * PL + 63) / 64 * 64, 64);
-    int nblk = std::max(1, std::min(HW / PL, std::max(HW / (PL * 16), (2048 + B - 1) / B)));
-    hipLaunchKernelGGL(gn_apply_mx_kernel, dim3(nblk, B), dim3(threads), 0, s, x, C1, x2, C2, stats, gamma, beta, q, sc, HW, groups, silu, CVp, PL);
+    hipLaunchKernelGGL(gn_apply_mx_kernel, dim3(p.nblk, B), dim3(p.threads), 0, s, x, C1, x2, C2, stats, gamma, beta, q, sc, HW, groups, silu, p.CV, p.PL);
     check_launch("gn_apply_mx");
   }
   ctx->arena.pop();

@@ -384,6 +384,105 @@ int SVG_OP(svg_op_groupnorm)(svg_ctx* ctx, const uint16_t* x, const float* gamma
   API_END(ctx)
 }
 
+// GroupNorm on a full descriptor (svg_hip.h: svg_gn_desc): two sources, f32 input, caller-supplied producer column sums and a forced
+// kernel path; path = {kind, maxch, vw, CV, PL, nchunk, nblk, threads} of what ran.  Test hook.
+static void gn_desc_stats(const svg_gn_desc* d, GnStats& s1, GnStats& s2) {
+  s1.part = d->part1; s1.tiles_per_sample = d->tps1;
+  s2.part = d->part2; s2.tiles_per_sample = d->tps2;
+}
+static void gn_path_out(const GnPath& p, int* path) {
+  if (!path) return;
+  path[0] = p.kind; path[1] = p.maxch; path[2] = p.vw; path[3] = p.CV; path[4] = p.PL; path[5] = p.nchunk; path[6] = p.nblk; path[7] = p.threads;
+}
+int SVG_OP(svg_op_groupnorm_ex)(svg_ctx* ctx, const svg_gn_desc* d, int* path, void* stream) {
+  API_BEGIN
+  SVG_CHECK(d != nullptr, "groupnorm_ex: no descriptor");
+  SVG_CHECK(d->x && d->gamma && d->beta && d->out && (d->C2 == 0 || d->x2), "groupnorm_ex: x, gamma, beta, out (and x2 when C2 > 0) are required");
+  GnStats s1, s2;
+  gn_desc_stats(d, s1, s2);
+  GnPath f, p;
+  f.kind = d->kind; f.maxch = d->maxch; f.vw = d->vw;
+  run_planned(ctx, [&]() {
+    groupnorm_ex(ctx, d->x, d->C1, d->x2, d->C2, d->f32_in != 0, d->gamma, d->beta, (h16*)d->out, d->B, d->HW, d->groups, d->eps, d->silu,
+                 (hipStream_t)stream, &s1, &s2, d->force ? &f : nullptr, &p);
+  });
+  gn_path_out(p, path);
+  API_END(ctx)
+}
+
+// GroupNorm with MX fp8 output on the same descriptor (16-bit input, the statistics from part1 / part2): q (B*HW, Cp) e4m3 bytes, sc
+// (B*HW, Cp/32) E8M0 bytes, stats (B, groups, 2) the (mean, rstd) table it used; *fused = 0 when groupnorm_mx declines (nothing is written).
+int SVG_OP(svg_op_groupnorm_mx)(svg_ctx* ctx, const svg_gn_desc* d, int* fused, int* path, void* stream) {
+  API_BEGIN
+  SVG_CHECK(d != nullptr, "groupnorm_mx: no descriptor");
+  SVG_CHECK(!d->f32_in && !d->force, "groupnorm_mx: 16-bit input, no forced path");
+  SVG_CHECK(d->x && d->gamma && d->beta && d->q && d->sc && d->stats && (d->C2 == 0 || d->x2), "groupnorm_mx: x, gamma, beta, q, sc, stats (and x2 when C2 > 0) are required");
+  GnStats s1, s2;
+  gn_desc_stats(d, s1, s2);
+  GnPath p;
+  bool ok = false;
+  run_planned(ctx, [&]() {
+    ok = groupnorm_mx(ctx, (const h16*)d->x, d->C1, (const h16*)d->x2, d->C2, d->gamma, d->beta, d->q, d->sc, d->B, d->HW, d->groups, d->eps,
+                      d->silu, (hipStream_t)stream, &s1, &s2, d->stats, &p);
+  });
+  if (fused) *fused = ok ? 1 : 0;
+  gn_path_out(p, path);
+  API_END(ctx)
+}
+
+// gn_fold_weights on caller buffers (device): Wb (B,N,C) 16-bit, bb (B,N).  Test hook.
+int SVG_OP(svg_op_gn_fold_weights)(svg_ctx* ctx, const float* W, const float* bias, const float* gamma, const float* beta, const float* stats,
+                                   uint16_t* Wb, float* bb, int B, int N, int C, int groups, void* stream) {
+  API_BEGIN
+  SVG_CHECK(groups > 0 && C % groups == 0 && B > 0 && N > 0, "gn_fold_weights: C=%d groups=%d unsupported", C, groups);
+  gn_fold_weights(W, bias, gamma, beta, stats, (h16*)Wb, bb, B, N, C, groups, (hipStream_t)stream);
+  API_END(ctx)
+}
+
+// ln_stats, softmax_rows and rowsum_h16 on caller buffers.  Test hooks.
+int SVG_OP(svg_op_ln_stats)(svg_ctx* ctx, const uint16_t* x, float* rs, float* rm, int M, int C, float eps, void* stream) {
+  API_BEGIN
+  ln_stats(ctx, (const h16*)x, rs, rm, M, C, eps, (hipStream_t)stream);
+  API_END(ctx)
+}
+int SVG_OP(svg_op_softmax_rows)(svg_ctx* ctx, const float* s_in, uint16_t* p_out, int64_t rows, int cols, int ld_in, int ld_out, float scale,
+                                void* stream) {
+  API_BEGIN
+  SVG_CHECK(rows > 0 && cols > 0 && ld_in >= cols && ld_out >= cols, "softmax_rows: rows=%lld cols=%d ld_in=%d ld_out=%d unsupported", (long long)rows,
+            cols, ld_in, ld_out);
+  softmax_rows(ctx, s_in, (h16*)p_out, rows, cols, ld_in, ld_out, scale, (hipStream_t)stream);
+  API_END(ctx)
+}
+int SVG_OP(svg_op_rowsum)(svg_ctx* ctx, const uint16_t* w, float* out, int N, int K, void* stream) {
+  API_BEGIN
+  rowsum_h16((const h16*)w, out, N, K, (hipStream_t)stream);
+  API_END(ctx)
+}
+
+#if !SD_F16
+// the f32-only kernels of norm.hip on caller buffers (one export: no 16-bit storage is involved).  Test hooks.
+int svg_op_gn_finish(svg_ctx* ctx, const float* part1, int C1, int tps1, const float* part2, int C2, int tps2, float* stats, int B, int HW,
+                     int groups, float eps, void* stream) {
+  API_BEGIN
+  const int C = C1 + C2;
+  SVG_CHECK(groups > 0 && C % groups == 0 && part1 && tps1 > 0 && (C2 == 0 || (part2 && tps2 > 0)), "gn_finish: C=%d groups=%d or partials unsupported", C, groups);
+  GnStats s1, s2;
+  s1.part = part1; s1.tiles_per_sample = tps1; s2.part = part2; s2.tiles_per_sample = tps2;
+  gn_finish(ctx, s1, C1, C2 ? &s2 : nullptr, C2, stats, B, HW, groups, eps, (hipStream_t)stream);
+  API_END(ctx)
+}
+int svg_op_ln_finish(svg_ctx* ctx, const float* part, int tiles, float* rs, float* rm, int M, int C, float eps, void* stream) {
+  API_BEGIN
+  ln_finish(ctx, part, tiles, rs, rm, M, C, eps, (hipStream_t)stream);
+  API_END(ctx)
+}
+int svg_op_fold_ln(svg_ctx* ctx, float* w, const float* bias_in, const float* gamma, const float* beta, float* bias_out, int N, int K, void* stream) {
+  API_BEGIN
+  fold_ln_weights(w, bias_in, gamma, beta, bias_out, N, K, (hipStream_t)stream);
+  API_END(ctx)
+}
+#endif
+
 int SVG_OP(svg_op_layernorm)(svg_ctx* ctx, const uint16_t* x, const float* gamma, const float* beta, uint16_t* out, int M, int C,
                      float eps, void* stream) {
   API_BEGIN
