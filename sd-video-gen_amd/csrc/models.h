@@ -211,12 +211,12 @@ struct XfBlockW {   // SpatialTransformer with one BasicTransformerBlock
   h16* xo = nullptr;             // attn2.to_out.0 [320][384] with the padded / permuted contraction order of that kernel
   int C = 0;
 };
-// cross-attention K / V^T of a constant context, computed on the first DDIM step and reused by the others
+// cross-attention K / V^T of a constant context, computed on the first DDIM step and reused by the others; one slot per transformer
+// block and tensor, allocated outside the arena (it survives the call)
 struct KvCache {
-  std::vector<h16*> k, vt;
-  std::vector<int64_t> k_cap, vt_cap;
-  std::vector<h16*> kp, vp;            // per-head packed copies for the fused cross-attention kernel
-  std::vector<int64_t> kvp_cap;
+  struct Slot { h16* p = nullptr; int64_t cap = 0; };
+  std::vector<Slot> k, vt;
+  std::vector<Slot> kp, vp;            // per-head packed copies for the fused cross-attention kernel
   bool valid = false;
 };
 
@@ -265,6 +265,11 @@ struct LnEmit {
 };
 static inline int64_t gn_part_floats(int64_t B, int64_t HW, int64_t N) { return B * (HW / 128 + 1) * N * 2; }
 
+// a GnEmit with its arena buffer for an (N, hw, Cout) output; none below 1024 rows per sample (the single-launch GroupNorm takes those)
+GnEmit emit_for(svg_ctx* ctx, int N, int64_t hw, int Cout);
+// hands ln->buf to a planned dense GEMM when its launch emits few enough column tiles ($SVG_LN_EPI=0: never); ln->tiles says whether
+void plan_ln_emit(GemmArgs& g, const GemmPlan& plan, LnEmit* ln);
+
 // shared graph pieces (sdnet.cpp)
 // fp8: additionally keep the MX fp8 copy of the weights (ConvW::w8) when the conv qualifies (Cin % 64 == 0)
 ConvW load_conv3x3(svg_ctx* ctx, WeightStore& ws, const std::string& prefix, int Cin, int Cout, hipStream_t s, bool fp8 = false);
@@ -275,24 +280,43 @@ NormW load_norm(svg_ctx* ctx, WeightStore& ws, const std::string& prefix, int C)
 // adds the MX fp8 copy of a packed linear when it qualifies (see PackedLinear::w8)
 void add_fp8_copy(svg_ctx* ctx, PackedLinear& pl, hipStream_t s);
 float* keep_f32(svg_ctx* ctx, WeightStore& ws, const std::string& name, int64_t numel);
-// out (B,Ho,Wo,Cout) = conv3x3(x) + bias [+ per-sample bias] [+ residual]
+// output image of a 3x3 conv in mode `amode` (A_CONV_*) on an H x W input: the one place that maps the mode to a geometry
+struct ConvDims { int Ho, Wo; };
+ConvDims conv_out_dims(int amode, int H, int W);
+// the implicit-GEMM problem of a 3x3 conv (no epilogue operands, no output pointer)
+GemmArgs conv3x3_args(const h16* x, const ConvW& cw, int B, int H, int W, int amode, int out_f32);
 // output channel tile of the halo kernel conv3x3() would launch for this problem (128 / 160), 0 when it takes the implicit GEMM
 int conv3x3_halo_width(const ConvW& cw, int B, int H, int W, int amode, int out_f32);
-// out_f32: 0 16-bit, 1 f32, 2 the VAE's f32 residual stream (GemmArgs::out_f32); residual_f32: an f32 residual instead of `residual` (2 only)
-void conv3x3(svg_ctx* ctx, const h16* x, const ConvW& cw, void* out, int B, int H, int W, int amode, const float* bias_bn,
-             int bias_bn_ld, const h16* residual, int out_f32, hipStream_t s, GnEmit* emit = nullptr, const float* residual_f32 = nullptr);
-// the same stride-1 conv on MX fp8 operands (conv_halo_fp8.hip): x8 / xs = the quantised input of quant_act_mx (or of the quantising
-// GroupNorm apply pass); the caller asks conv3x3_fp8_ok() first
-// up2: nearest-2x upsample fused in front (the UNet's upsamplers): x8 is the H x W source, the output is 2H x 2W
+// The optional operands of a conv: out (B,Ho,Wo,Cout) = conv3x3(x) + bias [+ per-sample bias] [+ residual]
+struct ConvOpts {
+  const float* bias_bn = nullptr; int bias_bn_ld = 0;   // [B][bias_bn_ld] per-sample column bias (the time embedding); ld 0 = Opad
+  const h16* residual = nullptr;                         // (B,Ho,Wo,Opad)
+  const float* residual_f32 = nullptr;                   // an f32 residual instead of `residual` (out_f32 == 2 only)
+  int out_f32 = 0;                                       // 0 16-bit, 1 f32, 2 the VAE's f32 residual stream (GemmArgs::out_f32)
+  GnEmit* emit = nullptr;                                // GroupNorm column sums of the output
+};
+void conv3x3(svg_ctx* ctx, const h16* x, const ConvW& cw, void* out, int B, int H, int W, int amode, hipStream_t s, const ConvOpts& o = {});
+// the same conv on MX fp8 operands (conv_halo_fp8.hip), 16-bit output only: x8 / xs = the quantised input of quant_act_mx (or of the
+// quantising GroupNorm apply pass); the caller asks conv3x3_fp8_ok() first.  amode: A_CONV_S1, or A_CONV_UP2 (up2) = nearest-2x
+// upsample fused in front (the UNet's upsamplers): x8 is the H x W source, the output is 2H x 2W
 bool conv3x3_fp8_ok(const ConvW& cw, int B, int H, int W, bool up2 = false);
-void conv3x3_fp8(svg_ctx* ctx, const uint8_t* x8, const uint8_t* xs, const ConvW& cw, h16* out, int B, int H, int W, const float* bias_bn,
-                 int bias_bn_ld, const h16* residual, hipStream_t s, GnEmit* emit = nullptr, bool up2 = false);
-// C[M,N] = act(A[M,K] W^T + b) [+ residual]
-// emit / rows_per_sample: GroupNorm column sums of the output (M = samples x rows_per_sample).  A2 / k_split: the A operand is the
-// channel concat [A | A2] of two tensors (columns >= k_split come from A2, row stride lda2) without materialising it.
-void linear(svg_ctx* ctx, const h16* A, int lda, const PackedLinear& pl, void* C, int ldc, int M, int act, const h16* residual,
-            int ldr, int out_f32, hipStream_t s, const float* ln_rs = nullptr, const float* ln_rm = nullptr, GnEmit* emit = nullptr,
-            int rows_per_sample = 0, const h16* A2 = nullptr, int lda2 = 0, int k_split = 0, LnEmit* ln = nullptr,
-            const float* residual_f32 = nullptr);
+void conv3x3_fp8(svg_ctx* ctx, const uint8_t* x8, const uint8_t* xs, const ConvW& cw, h16* out, int B, int H, int W, int amode, hipStream_t s,
+                 const ConvOpts& o = {});
+// The optional operands of a linear: C[M,N] = act(A[M,K] W^T + b) [+ residual]
+struct LinearOpts {
+  int act = ACT_NONE;
+  const h16* residual = nullptr; int ldr = 0;                // [M][ldr]
+  const float* residual_f32 = nullptr;                       // an f32 residual (same ldr) instead of `residual` (out_f32 == 2 only)
+  int out_f32 = 0;                                           // as ConvOpts::out_f32
+  const float *ln_rs = nullptr, *ln_rm = nullptr;            // row statistics of A: with (and only with) LayerNorm-folded weights (pl.ln_s)
+  GnEmit* emit = nullptr; int rows_per_sample = 0;           // GroupNorm column sums of the output (M = samples x rows_per_sample)
+  const h16* A2 = nullptr; int lda2 = 0, k_split = 0;        // A = channel concat [A | A2], never materialised: columns >= k_split from A2
+  LnEmit* ln = nullptr;                                      // LayerNorm row partials of the output
+};
+void linear(svg_ctx* ctx, const h16* A, int lda, const PackedLinear& pl, void* C, int ldc, int M, hipStream_t s, const LinearOpts& o = {});
+// V^T[b] (wv.N x rows_pad) = Wv * src_b^T (+ bv per row, when wv has a bias) for B samples of `rows` tokens; ln_rs / ln_rm: the token
+// statistics of LayerNorm-folded weights
+void vt_proj_into(svg_ctx* ctx, const PackedLinear& wv, const h16* src, int B, int rows, int rows_pad, int K, h16* vt, hipStream_t s,
+                  const float* ln_rs = nullptr, const float* ln_rm = nullptr);
 
 }  // namespace SDNS

@@ -17,6 +17,30 @@
 
 using namespace SDNS;
 
+// The temporary ConvW of a conv hook: the caller's OIHW f32 weights (+ optional bias) staged in the arena and packed there, as 16-bit
+// weights or (mx) as the MX fp8 copy alone.  Arena order: [w |] f32 staging | bias [| w8 | w8s]
+static ConvW stage_conv(svg_ctx* ctx, const float* w_oihw, const float* bias, int Cin, int Cout, bool mx, hipStream_t s) {
+  ConvW cw;
+  cw.Cin = Cin; cw.Cout = Cout; cw.Opad = (int)align_up(Cout, 4);
+  const int64_t nw = (int64_t)Cout * Cin * 9;
+  if (!mx) cw.w = ctx->arena.get<h16>((int64_t)cw.Opad * 9 * Cin);
+  float* wdev = ctx->arena.get<float>(nw);
+  cw.b = ctx->arena.get<float>(cw.Opad);
+  if (mx) {
+    cw.Cp = (int)align_up(Cin, 128);
+    cw.w8 = ctx->arena.get<uint8_t>((int64_t)cw.Opad * 9 * cw.Cp);
+    cw.w8s = ctx->arena.get<uint8_t>((int64_t)9 * (cw.Cp / 128) * cw.Opad * 4);
+  }
+  if (SVG_LAUNCHING(ctx)) {
+    HIP_OK(hipMemcpyAsync(wdev, w_oihw, (size_t)nw * sizeof(float), hipMemcpyDefault, s));
+    HIP_OK(hipMemsetAsync(cw.b, 0, cw.Opad * sizeof(float), s));
+    if (bias) HIP_OK(hipMemcpyAsync(cw.b, bias, Cout * sizeof(float), hipMemcpyDefault, s));
+    if (mx) pack_conv3x3_mx(wdev, cw.w8, cw.w8s, Cout, Cin, cw.Opad, cw.Cp, s);
+    else pack_conv3x3(wdev, cw.w, Cout, Cin, cw.Opad, Cin, s);
+  }
+  return cw;
+}
+
 extern "C" {
 
 int SVG_OP(svg_op_gemm)(svg_ctx* ctx, const uint16_t* A, const uint16_t* W, const float* bias, const uint16_t* residual, void* C,
@@ -52,28 +76,11 @@ int SVG_OP(svg_op_conv3x3)(svg_ctx* ctx, const uint16_t* x, const float* w_oihw,
   API_BEGIN
   hipStream_t s = (hipStream_t)stream;
   run_planned(ctx, [&]() {
-    const int Opad = (int)align_up(Cout, 4);
-    h16* wp = ctx->arena.get<h16>((int64_t)Opad * 9 * Cin);
-    float* wdev = ctx->arena.get<float>((int64_t)Cout * Cin * 9);
-    float* bdev = ctx->arena.get<float>(Opad);
-    if (SVG_LAUNCHING(ctx)) {
-      HIP_OK(hipMemcpyAsync(wdev, w_oihw, (size_t)Cout * Cin * 9 * sizeof(float), hipMemcpyDefault, s));
-      HIP_OK(hipMemsetAsync(bdev, 0, Opad * sizeof(float), s));
-      if (bias) HIP_OK(hipMemcpyAsync(bdev, bias, Cout * sizeof(float), hipMemcpyDefault, s));
-      pack_conv3x3(wdev, wp, Cout, Cin, Opad, Cin, s);
-    }
-    GemmArgs g;
-    g.A = (const h16*)x;
-    g.H = H; g.W = W; g.Cin = Cin;
-    switch (mode) {
-      case 0: g.amode = (Cin == 8) ? A_CONV_SMALLC : A_CONV_S1; g.Ho = H; g.Wo = W; break;
-      case 1: g.amode = A_CONV_S2P1; g.Ho = H / 2; g.Wo = W / 2; break;
-      case 2: g.amode = A_CONV_S2ASYM; g.Ho = H / 2; g.Wo = W / 2; break;
-      case 3: g.amode = A_CONV_UP2; g.Ho = 2 * H; g.Wo = 2 * W; break;
-      default: throw SvgError("conv3x3: bad mode");
-    }
-    g.Wt = wp; g.ldb = 9 * Cin; g.K = 9 * Cin; g.M = B * g.Ho * g.Wo; g.N = Opad; g.n_valid = Opad;
-    g.bias = bdev; g.C = out; g.ldc = Cout;
+    SVG_CHECK(mode >= 0 && mode <= 3, "conv3x3: bad mode");
+    const int amodes[4] = {A_CONV_S1, A_CONV_S2P1, A_CONV_S2ASYM, A_CONV_UP2};
+    const ConvW cw = stage_conv(ctx, w_oihw, bias, Cin, Cout, false, s);
+    GemmArgs g = conv3x3_args((const h16*)x, cw, B, H, W, amodes[mode], 0);
+    g.C = out; g.ldc = Cout;
     SVG_CHECK(Cout % 4 == 0, "conv3x3 op: Cout must be a multiple of 4");
     gemm_auto(ctx, g, s, PK_CONV3);
   });
@@ -92,23 +99,13 @@ int SVG_OP(svg_op_conv3x3_mx)(svg_ctx* ctx, const uint16_t* x, const float* w_oi
   SVG_CHECK(mode == 0 || mode == 3, "conv3x3_mx op: mode 0 (stride 1) or 3 (nearest-2x upsample in front)");
   const bool up2 = mode == 3;
   run_planned(ctx, [&]() {
-    ConvW cw;
-    cw.Cin = Cin; cw.Cout = Cout; cw.Opad = Cout; cw.Cp = (int)align_up(Cin, 128);
+    const ConvW cw = stage_conv(ctx, w_oihw, bias, Cin, Cout, true, s);
     const int64_t P = (int64_t)B * H * W;
-    float* wdev = ctx->arena.get<float>((int64_t)Cout * Cin * 9);
-    cw.b = ctx->arena.get<float>(Cout);
-    cw.w8 = ctx->arena.get<uint8_t>((int64_t)Cout * 9 * cw.Cp);
-    cw.w8s = ctx->arena.get<uint8_t>((int64_t)9 * (cw.Cp / 128) * Cout * 4);
     uint8_t* q = ctx->arena.get<uint8_t>(P * cw.Cp);
     uint8_t* qs = ctx->arena.get<uint8_t>(P * (cw.Cp / 32));
-    if (SVG_LAUNCHING(ctx)) {
-      HIP_OK(hipMemcpyAsync(wdev, w_oihw, (size_t)Cout * Cin * 9 * sizeof(float), hipMemcpyDefault, s));
-      HIP_OK(hipMemsetAsync(cw.b, 0, Cout * sizeof(float), s));
-      if (bias) HIP_OK(hipMemcpyAsync(cw.b, bias, Cout * sizeof(float), hipMemcpyDefault, s));
-      pack_conv3x3_mx(wdev, cw.w8, cw.w8s, Cout, Cin, Cout, cw.Cp, s);
-    }
     quant_act_mx(ctx, (const h16*)x, Cin, q, qs, P, s);
-    conv3x3_fp8(ctx, q, qs, cw, (h16*)out, B, H, W, nullptr, 0, (const h16*)residual, s, nullptr, up2);
+    ConvOpts o; o.residual = (const h16*)residual;
+    conv3x3_fp8(ctx, q, qs, cw, (h16*)out, B, H, W, up2 ? A_CONV_UP2 : A_CONV_S1, s, o);
     if (SVG_LAUNCHING(ctx)) {
       if (q_out) HIP_OK(hipMemcpyAsync(q_out, q, (size_t)P * cw.Cp, hipMemcpyDeviceToDevice, s));
       if (s_out) HIP_OK(hipMemcpyAsync(s_out, qs, (size_t)P * (cw.Cp / 32), hipMemcpyDeviceToDevice, s));
@@ -126,24 +123,17 @@ int SVG_OP(svg_op_conv3x3_gn)(svg_ctx* ctx, const uint16_t* x, const float* w_oi
   SVG_CHECK(Cout % 4 == 0 && Cin % 64 == 0, "conv3x3_gn op: Cout %% 4 and Cin %% 64 must be 0");
   int used = 0;
   run_planned(ctx, [&]() {
-    ConvW cw;
-    cw.Cin = Cin; cw.Cout = Cout; cw.Opad = Cout;
-    cw.w = ctx->arena.get<h16>((int64_t)Cout * 9 * Cin);
-    float* wdev = ctx->arena.get<float>((int64_t)Cout * Cin * 9);
-    cw.b = ctx->arena.get<float>(Cout);
+    const ConvW cw = stage_conv(ctx, w_oihw, bias, Cin, Cout, false, s);
     float* gdev = ctx->arena.get<float>(Cout);
     float* bdev = ctx->arena.get<float>(Cout);
     if (SVG_LAUNCHING(ctx)) {
-      HIP_OK(hipMemcpyAsync(wdev, w_oihw, (size_t)Cout * Cin * 9 * sizeof(float), hipMemcpyDefault, s));
-      HIP_OK(hipMemsetAsync(cw.b, 0, Cout * sizeof(float), s));
-      if (bias) HIP_OK(hipMemcpyAsync(cw.b, bias, Cout * sizeof(float), hipMemcpyDefault, s));
       HIP_OK(hipMemcpyAsync(gdev, gamma, Cout * sizeof(float), hipMemcpyDefault, s));
       HIP_OK(hipMemcpyAsync(bdev, beta, Cout * sizeof(float), hipMemcpyDefault, s));
-      pack_conv3x3(wdev, cw.w, Cout, Cin, Cout, Cin, s);
     }
     GnEmit e;
     e.buf = ctx->arena.get<float>(gn_part_floats(B, (int64_t)H * W, Cout));
-    conv3x3(ctx, (const h16*)x, cw, conv_out, B, H, W, A_CONV_S1, nullptr, 0, nullptr, 0, s, &e);
+    ConvOpts o; o.emit = &e;
+    conv3x3(ctx, (const h16*)x, cw, conv_out, B, H, W, A_CONV_S1, s, o);
     used = e.st.valid() ? 1 : 0;
     groupnorm(ctx, (const h16*)conv_out, Cout, nullptr, 0, gdev, bdev, (h16*)gn_out, B, H * W, groups, eps, silu, s, &e.st, nullptr);
   });
@@ -163,26 +153,17 @@ int SVG_OP(svg_op_conv3x3_f32s)(svg_ctx* ctx, const uint16_t* x, const float* w_
   SVG_CHECK(!(residual && residual_f32), "conv3x3_f32s op: one residual");
   SVG_CHECK(!gn_out || (gamma && beta), "conv3x3_f32s op: the GroupNorm needs gamma and beta");
   const int amode = mode == 0 ? A_CONV_S1 : (mode == 2 ? A_CONV_S2ASYM : A_CONV_UP2);
-  const int Ho = mode == 0 ? H : (mode == 2 ? H / 2 : 2 * H), Wo = mode == 0 ? W : (mode == 2 ? W / 2 : 2 * W);
+  const ConvDims d = conv_out_dims(amode, H, W);
   int used = 0, hw = 0;
   run_planned(ctx, [&]() {
-    ConvW cw;
-    cw.Cin = Cin; cw.Cout = Cout; cw.Opad = Cout;
-    cw.w = ctx->arena.get<h16>((int64_t)Cout * 9 * Cin);
-    float* wdev = ctx->arena.get<float>((int64_t)Cout * Cin * 9);
-    cw.b = ctx->arena.get<float>(Cout);
-    if (SVG_LAUNCHING(ctx)) {
-      HIP_OK(hipMemcpyAsync(wdev, w_oihw, (size_t)Cout * Cin * 9 * sizeof(float), hipMemcpyDefault, s));
-      HIP_OK(hipMemsetAsync(cw.b, 0, Cout * sizeof(float), s));
-      if (bias) HIP_OK(hipMemcpyAsync(cw.b, bias, Cout * sizeof(float), hipMemcpyDefault, s));
-      pack_conv3x3(wdev, cw.w, Cout, Cin, Cout, Cin, s);
-    }
+    const ConvW cw = stage_conv(ctx, w_oihw, bias, Cin, Cout, false, s);
     hw = conv3x3_halo_width(cw, B, H, W, amode, 2);
     GnEmit e;
-    e.buf = ctx->arena.get<float>(gn_part_floats(B, (int64_t)Ho * Wo, Cout));
-    conv3x3(ctx, (const h16*)x, cw, out, B, H, W, amode, nullptr, 0, (const h16*)residual, 2, s, gn_out ? &e : nullptr, residual_f32);
+    e.buf = ctx->arena.get<float>(gn_part_floats(B, (int64_t)d.Ho * d.Wo, Cout));
+    ConvOpts o; o.residual = (const h16*)residual; o.residual_f32 = residual_f32; o.out_f32 = 2; o.emit = gn_out ? &e : nullptr;
+    conv3x3(ctx, (const h16*)x, cw, out, B, H, W, amode, s, o);
     used = e.st.valid() ? 1 : 0;
-    if (gn_out) groupnorm_f32(ctx, out, Cout, gamma, beta, (h16*)gn_out, B, Ho * Wo, groups, eps, silu, s, &e.st);
+    if (gn_out) groupnorm_f32(ctx, out, Cout, gamma, beta, (h16*)gn_out, B, d.Ho * d.Wo, groups, eps, silu, s, &e.st);
   });
   if (halo_width) *halo_width = hw;
   if (used_epilogue_stats) *used_epilogue_stats = used;

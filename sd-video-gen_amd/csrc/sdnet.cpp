@@ -85,54 +85,67 @@ NormW load_norm(svg_ctx* ctx, WeightStore& ws, const std::string& prefix, int C)
   return n;
 }
 
-// fills g.gn_part / emit->st when the planned launch of g can leave the output's GroupNorm column sums (whole row tiles per sample)
-static void plan_gn_emit(GemmArgs& g, const GemmPlan& plan, GnEmit* emit, int rows_per_sample) {
+GnEmit emit_for(svg_ctx* ctx, int N, int64_t hw, int Cout) {
+  GnEmit e;
+  if (hw >= 1024) e.buf = ctx->arena.get<float>(gn_part_floats(N, hw, Cout));
+  return e;
+}
+
+// fills g.gn_part / emit->st when the launch of g leaves the output's GroupNorm column sums per `rows` output rows (gemm_plan()'s
+// gn_rows, or the 16 x 16 pixel block of the fp8 halo conv) and a sample is whole row tiles
+static void attach_gn_emit(GemmArgs& g, GnEmit* emit, int rows_per_sample, int rows) {
   static const int use_epi = getenv("SVG_GN_EPI") ? atoi(getenv("SVG_GN_EPI")) : 1;   // 0: A/B switch, statistics pass as before
   if (!use_epi || !emit || !emit->buf || rows_per_sample < 1024) return;   // small images take the single-launch GroupNorm (one read)
-  const int rows = plan.gn_rows;
   if (rows <= 0 || rows_per_sample % rows != 0) return;
   g.gn_part = emit->buf;
   emit->st.part = emit->buf;
   emit->st.tiles_per_sample = rows_per_sample / rows;
 }
 
+void plan_ln_emit(GemmArgs& g, const GemmPlan& plan, LnEmit* ln) {
+  if (ln) ln->tiles = 0;
+  if (!ln || !ln->buf) return;
+  static const int use_ln = getenv("SVG_LN_EPI") ? atoi(getenv("SVG_LN_EPI")) : 1;    // 0: A/B switch, ln_stats pass as before
+  const int tiles = use_ln ? plan.ln_tiles : 0;
+  if (tiles > 0 && tiles <= 5) { g.ln_part = ln->buf; g.ln_tiles = tiles; ln->tiles = tiles; }   // C = 1280 (8 tiles): the finish costs what the 8 us pass did
+}
+
+ConvDims conv_out_dims(int amode, int H, int W) {
+  switch (amode) {
+    case A_CONV_S1: return {H, W};
+    case A_CONV_S2P1: case A_CONV_S2ASYM: return {H / 2, W / 2};
+    case A_CONV_UP2: return {2 * H, 2 * W};
+    default: throw SvgError("conv3x3: bad mode");
+  }
+}
+
 bool conv3x3_fp8_ok(const ConvW& cw, int B, int H, int W, bool up2) {
   return cw.w8 != nullptr && conv_halo_fp8_supported(B, up2 ? 2 * H : H, up2 ? 2 * W : W, cw.Cin, cw.Opad);
 }
 
-void conv3x3_fp8(svg_ctx* ctx, const uint8_t* x8, const uint8_t* xs, const ConvW& cw, h16* out, int B, int H, int W, const float* bias_bn,
-                 int bias_bn_ld, const h16* residual, hipStream_t s, GnEmit* emit, bool up2) {
-  SVG_CHECK(conv3x3_fp8_ok(cw, B, H, W, up2), "conv3x3_fp8: %d x %dx%d x %d -> %d does not qualify", B, H, W, cw.Cin, cw.Opad);
+void conv3x3_fp8(svg_ctx* ctx, const uint8_t* x8, const uint8_t* xs, const ConvW& cw, h16* out, int B, int H, int W, int amode, hipStream_t s,
+                 const ConvOpts& o) {
+  SVG_CHECK((amode == A_CONV_S1 || amode == A_CONV_UP2) && !o.out_f32 && !o.residual_f32, "conv3x3_fp8: stride 1 (mode %d), 16-bit output and residual only", amode);
+  SVG_CHECK(conv3x3_fp8_ok(cw, B, H, W, amode == A_CONV_UP2), "conv3x3_fp8: %d x %dx%d x %d -> %d does not qualify", B, H, W, cw.Cin, cw.Opad);
+  const ConvDims d = conv_out_dims(amode, H, W);
   GemmArgs g;
-  g.H = H; g.W = W; g.Cin = cw.Cin; g.amode = up2 ? A_CONV_UP2 : A_CONV_S1; g.Ho = up2 ? 2 * H : H; g.Wo = up2 ? 2 * W : W;
-  H = g.Ho; W = g.Wo;                       // the output image from here on
-  g.K = 9 * cw.Cin; g.M = B * H * W; g.N = cw.Opad; g.n_valid = cw.Opad;
+  g.H = H; g.W = W; g.Cin = cw.Cin; g.amode = amode; g.Ho = d.Ho; g.Wo = d.Wo;
+  g.K = 9 * cw.Cin; g.M = B * d.Ho * d.Wo; g.N = cw.Opad; g.n_valid = cw.Opad;
   g.bias = cw.b;
-  g.bias_bn = bias_bn; g.bias_bn_ld = bias_bn_ld; g.rows_per_batch = H * W;
-  g.residual = residual; g.ldr = cw.Opad;
+  g.bias_bn = o.bias_bn; g.bias_bn_ld = o.bias_bn_ld; g.rows_per_batch = d.Ho * d.Wo;
+  g.residual = o.residual; g.ldr = cw.Opad;
   g.C = out; g.ldc = cw.Opad;
-  // GroupNorm column sums of the output: one partial per 16 x 16 pixel block, like the fp16 halo conv
-  static const int use_epi = getenv("SVG_GN_EPI") ? atoi(getenv("SVG_GN_EPI")) : 1;
-  if (use_epi && emit && emit->buf && H * W >= 1024 && (H * W) % 256 == 0) {
-    g.gn_part = emit->buf;
-    emit->st.part = emit->buf;
-    emit->st.tiles_per_sample = H * W / 256;
-  }
+  attach_gn_emit(g, o.emit, d.Ho * d.Wo, 256);   // one partial per 16 x 16 pixel block, like the fp16 halo conv
   conv_halo_fp8(ctx, x8, xs, cw.w8, cw.w8s, cw.Opad, g, s);
 }
 
-// the implicit-GEMM problem of a 3x3 conv (no epilogue operands)
-static GemmArgs conv3x3_args(const h16* x, const ConvW& cw, int B, int H, int W, int amode, int out_f32) {
+GemmArgs conv3x3_args(const h16* x, const ConvW& cw, int B, int H, int W, int amode, int out_f32) {
   GemmArgs g;
   g.A = x; g.H = H; g.W = W; g.Cin = cw.Cin;
   g.amode = (cw.Cin == 8) ? A_CONV_SMALLC : amode;
   SVG_CHECK(cw.Cin != 8 || amode == A_CONV_S1, "small-Cin conv supports stride 1 only");
-  switch (amode) {
-    case A_CONV_S1: g.Ho = H; g.Wo = W; break;
-    case A_CONV_S2P1: case A_CONV_S2ASYM: g.Ho = H / 2; g.Wo = W / 2; break;
-    case A_CONV_UP2: g.Ho = 2 * H; g.Wo = 2 * W; break;
-    default: throw SvgError("conv3x3: bad mode");
-  }
+  const ConvDims d = conv_out_dims(amode, H, W);
+  g.Ho = d.Ho; g.Wo = d.Wo;
   g.Wt = cw.w; g.ldb = 9 * cw.Cin; g.K = 9 * cw.Cin;
   g.M = B * g.Ho * g.Wo; g.N = cw.Opad; g.n_valid = cw.Opad;
   g.bias = cw.b;
@@ -140,9 +153,8 @@ static GemmArgs conv3x3_args(const h16* x, const ConvW& cw, int B, int H, int W,
   return g;
 }
 
-void conv3x3(svg_ctx* ctx, const h16* x, const ConvW& cw, void* out, int B, int H, int W, int amode, const float* bias_bn,
-             int bias_bn_ld, const h16* residual, int out_f32, hipStream_t s, GnEmit* emit, const float* residual_f32) {
-  SVG_CHECK(!residual_f32 || (out_f32 == 2 && !residual), "conv3x3: an f32 residual needs the f32-stream output and no 16-bit residual");
+void conv3x3(svg_ctx* ctx, const h16* x, const ConvW& cw, void* out, int B, int H, int W, int amode, hipStream_t s, const ConvOpts& o) {
+  SVG_CHECK(!o.residual_f32 || (o.out_f32 == 2 && !o.residual), "conv3x3: an f32 residual needs the f32-stream output and no 16-bit residual");
   // the kernels address an operand with 32-bit byte offsets: an input or output of 2^31 elements or more (the 512 x 512
   // VAE levels beyond ~30 images) is processed in batch chunks
   {
@@ -151,26 +163,27 @@ void conv3x3(svg_ctx* ctx, const h16* x, const ConvW& cw, void* out, int B, int 
     const int64_t lim = chunk_limit();
     if ((int64_t)B * per_img > lim && B > 1) {
       const int chunk = (int)std::max<int64_t>(1, lim / per_img);
-      const int Ho = amode == A_CONV_UP2 ? 2 * H : ((amode == A_CONV_S2P1 || amode == A_CONV_S2ASYM) ? H / 2 : H);
-      const int Wo = amode == A_CONV_UP2 ? 2 * W : ((amode == A_CONV_S2P1 || amode == A_CONV_S2ASYM) ? W / 2 : W);
-      const int cin = cw.Cin;
+      const ConvDims d = conv_out_dims(amode, H, W);
+      ConvOpts c = o;               // per chunk: its slice of every operand; no statistics
+      c.emit = nullptr;
       for (int b0 = 0; b0 < B; b0 += chunk) {
-        const int nb = std::min(chunk, B - b0);
-        const int64_t o = (int64_t)b0 * Ho * Wo * cw.Opad;
-        conv3x3(ctx, x + (int64_t)b0 * H * W * cin, cw, out_f32 ? (void*)((float*)out + o) : (void*)((h16*)out + o), nb, H, W, amode,
-                bias_bn ? bias_bn + (int64_t)b0 * (bias_bn_ld ? bias_bn_ld : cw.Opad) : nullptr, bias_bn_ld,
-                residual ? residual + o : nullptr, out_f32, s, nullptr, residual_f32 ? residual_f32 + o : nullptr);
+        const int64_t off = (int64_t)b0 * d.Ho * d.Wo * cw.Opad;
+        if (o.bias_bn) c.bias_bn = o.bias_bn + (int64_t)b0 * (o.bias_bn_ld ? o.bias_bn_ld : cw.Opad);
+        if (o.residual) c.residual = o.residual + off;
+        if (o.residual_f32) c.residual_f32 = o.residual_f32 + off;
+        conv3x3(ctx, x + (int64_t)b0 * H * W * cw.Cin, cw, o.out_f32 ? (void*)((float*)out + off) : (void*)((h16*)out + off), std::min(chunk, B - b0),
+                H, W, amode, s, c);
       }
       return;
     }
   }
-  GemmArgs g = conv3x3_args(x, cw, B, H, W, amode, out_f32);
-  g.bias_bn = bias_bn; g.bias_bn_ld = bias_bn_ld; g.rows_per_batch = g.Ho * g.Wo;
-  g.residual = residual; g.ldr = cw.Opad;
+  GemmArgs g = conv3x3_args(x, cw, B, H, W, amode, o.out_f32);
+  g.bias_bn = o.bias_bn; g.bias_bn_ld = o.bias_bn_ld; g.rows_per_batch = g.Ho * g.Wo;
+  g.residual = o.residual; g.ldr = cw.Opad;
   g.C = out; g.ldc = cw.Opad;
-  g.residual_f32 = residual_f32;
+  g.residual_f32 = o.residual_f32;
   const GemmPlan plan = gemm_plan(g);
-  plan_gn_emit(g, plan, emit, g.Ho * g.Wo);
+  attach_gn_emit(g, o.emit, g.Ho * g.Wo, plan.gn_rows);
   gemm_auto(ctx, g, plan, s, PK_CONV3);
 }
 
@@ -179,53 +192,67 @@ int conv3x3_halo_width(const ConvW& cw, int B, int H, int W, int amode, int out_
   return plan.family == GF_HALO ? plan.bn : 0;
 }
 
-void linear(svg_ctx* ctx, const h16* A, int lda, const PackedLinear& pl, void* C, int ldc, int M, int act, const h16* residual,
-            int ldr, int out_f32, hipStream_t s, const float* ln_rs, const float* ln_rm, GnEmit* emit, int rows_per_sample,
-            const h16* A2, int lda2, int k_split, LnEmit* ln, const float* residual_f32) {
-  if (ln) ln->tiles = 0;
-  SVG_CHECK(!residual_f32 || (out_f32 == 2 && !residual), "linear: an f32 residual needs the f32-stream output and no 16-bit residual");
-  SVG_CHECK((pl.ln_s != nullptr) == (ln_rs != nullptr), "linear: LayerNorm-folded weights need the row statistics (and only they)");
+void linear(svg_ctx* ctx, const h16* A, int lda, const PackedLinear& pl, void* C, int ldc, int M, hipStream_t s, const LinearOpts& o) {
+  if (o.ln) o.ln->tiles = 0;
+  SVG_CHECK(!o.residual_f32 || (o.out_f32 == 2 && !o.residual), "linear: an f32 residual needs the f32-stream output and no 16-bit residual");
+  SVG_CHECK((pl.ln_s != nullptr) == (o.ln_rs != nullptr), "linear: LayerNorm-folded weights need the row statistics (and only they)");
   {   // 32-bit operand offsets in the kernels: split very tall problems (1 x 1 convs on the 512 x 512 VAE levels) by rows
     const int64_t lim = chunk_limit();
-    const int64_t per_row = std::max<int64_t>(lda, std::max(ldc, ldr));
+    const int64_t per_row = std::max<int64_t>(lda, std::max(ldc, o.ldr));
     if ((int64_t)M * per_row > lim && M > 1) {
-      SVG_CHECK(!A2, "linear: a two-source A operand is not split by rows");
+      SVG_CHECK(!o.A2, "linear: a two-source A operand is not split by rows");
       const int chunk = (int)(lim / per_row) & ~255;
       SVG_CHECK(chunk >= 256, "linear: a %lld-element operand limit is below one 256-row slab of %lld-wide rows", (long long)lim, (long long)per_row);
-      const int csz = out_f32 ? 4 : 2;
-      for (int m0 = 0; m0 < M; m0 += chunk)
-        linear(ctx, A + (int64_t)m0 * lda, lda, pl, (char*)C + (int64_t)m0 * ldc * csz, ldc, std::min(chunk, M - m0), act,
-               residual ? residual + (int64_t)m0 * ldr : nullptr, ldr, out_f32, s, ln_rs ? ln_rs + m0 : nullptr, ln_rm ? ln_rm + m0 : nullptr,
-               nullptr, 0, nullptr, 0, 0, nullptr, residual_f32 ? residual_f32 + (int64_t)m0 * ldr : nullptr);
+      const int csz = o.out_f32 ? 4 : 2;
+      LinearOpts c = o;             // per chunk: its rows of every operand; no statistics
+      c.emit = nullptr; c.rows_per_sample = 0; c.ln = nullptr;
+      for (int m0 = 0; m0 < M; m0 += chunk) {
+        if (o.residual) c.residual = o.residual + (int64_t)m0 * o.ldr;
+        if (o.residual_f32) c.residual_f32 = o.residual_f32 + (int64_t)m0 * o.ldr;
+        if (o.ln_rs) c.ln_rs = o.ln_rs + m0;
+        if (o.ln_rm) c.ln_rm = o.ln_rm + m0;
+        linear(ctx, A + (int64_t)m0 * lda, lda, pl, (char*)C + (int64_t)m0 * ldc * csz, ldc, std::min(chunk, M - m0), s, c);
+      }
       return;
     }
   }
-  if (pl.w8 && !A2 && !ln_rs && act != ACT_GEGLU && out_f32 != 2 && M >= 1024 && lda == pl.K && gemm_fp8_supported(M, pl.N, pl.K)) {
+  if (pl.w8 && !o.A2 && !o.ln_rs && o.act != ACT_GEGLU && o.out_f32 != 2 && M >= 1024 && lda == pl.K && gemm_fp8_supported(M, pl.N, pl.K)) {
     // MX fp8: the activations are quantised per 32-element block on the way in (one extra pass over A), f32 accumulate
     ctx->arena.push();
     uint8_t* aq = ctx->arena.get<uint8_t>((int64_t)M * pl.K);
     uint8_t* as = ctx->arena.get<uint8_t>((int64_t)M * (pl.K / 32));
     quant_mx_h16(ctx, A, lda, aq, as, M, pl.K, s);
     GemmArgs g8;
-    g8.M = M; g8.N = pl.N; g8.K = pl.K; g8.bias = pl.b; g8.act = act; g8.residual = residual; g8.ldr = ldr; g8.C = C; g8.ldc = ldc; g8.out_f32 = out_f32;
+    g8.M = M; g8.N = pl.N; g8.K = pl.K; g8.bias = pl.b; g8.act = o.act; g8.residual = o.residual; g8.ldr = o.ldr; g8.C = C; g8.ldc = ldc; g8.out_f32 = o.out_f32;
     gemm_fp8(ctx, aq, as, pl.w8, pl.w8s, g8, s);
     ctx->arena.pop();
     return;
   }
   GemmArgs g;
-  g.ln_rs = ln_rs; g.ln_rm = ln_rm; g.ln_s = pl.ln_s;
+  g.ln_rs = o.ln_rs; g.ln_rm = o.ln_rm; g.ln_s = pl.ln_s;
   g.A = A; g.lda = lda; g.Wt = pl.w; g.ldb = pl.K; g.M = M; g.N = pl.N; g.K = pl.K; g.n_valid = pl.N;
-  g.bias = pl.b; g.act = act; g.residual = residual; g.ldr = ldr; g.C = C; g.ldc = ldc; g.out_f32 = out_f32;
-  g.A2 = A2; g.lda2 = lda2; g.k_split = k_split;
-  g.residual_f32 = residual_f32;
+  g.bias = pl.b; g.act = o.act; g.residual = o.residual; g.ldr = o.ldr; g.C = C; g.ldc = ldc; g.out_f32 = o.out_f32;
+  g.A2 = o.A2; g.lda2 = o.lda2; g.k_split = o.k_split;
+  g.residual_f32 = o.residual_f32;
   const GemmPlan plan = gemm_plan(g);
-  plan_gn_emit(g, plan, emit, rows_per_sample);
-  if (ln && ln->buf) {
-    static const int use_ln = getenv("SVG_LN_EPI") ? atoi(getenv("SVG_LN_EPI")) : 1;    // 0: A/B switch, ln_stats pass as before
-    const int tiles = use_ln ? plan.ln_tiles : 0;
-    if (tiles > 0 && tiles <= 5) { g.ln_part = ln->buf; g.ln_tiles = tiles; ln->tiles = tiles; }   // C = 1280 (8 tiles): the finish costs what the 8 us pass did
-  }
+  attach_gn_emit(g, o.emit, o.rows_per_sample, plan.gn_rows);
+  plan_ln_emit(g, plan, o.ln);
   gemm_auto(ctx, g, plan, s, PK_GEMM);
+}
+
+void vt_proj_into(svg_ctx* ctx, const PackedLinear& wv, const h16* src, int B, int rows, int rows_pad, int K, h16* vt, hipStream_t s,
+                  const float* ln_rs, const float* ln_rm) {
+  const int C = wv.N;
+  GemmArgs g;
+  g.A = wv.w; g.lda = K; g.Wt = src; g.ldb = K; g.M = C; g.N = rows_pad; g.n_valid = rows; g.K = K;
+  g.batch = B; g.sA = 0; g.sB = (int64_t)rows * K; g.sC = (int64_t)C * rows_pad;
+  g.C = vt; g.ldc = rows_pad;
+  SVG_CHECK((wv.ln_s != nullptr) == (ln_rs != nullptr), "vt_proj: LayerNorm-folded weights need the token statistics");
+  if (wv.b) { g.bias = wv.b; g.bias_row = 1; }   // the output rows are the projection's columns
+  if (ln_rs) {   // the normalised tokens are the B operand here: statistics per column, sums per row
+    g.ln_rs = ln_rs; g.ln_rm = ln_rm; g.ln_s = wv.ln_s; g.ln_swapped = 1; g.ln_zstride = rows;
+  }
+  gemm_auto(ctx, g, s, PK_GEMM);
 }
 
 // per-device kernel attributes (dynamic LDS limits) of every kernel instantiation of this namespace

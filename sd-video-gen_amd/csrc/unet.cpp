@@ -331,11 +331,6 @@ struct UnetRun {
     int C = 0;
     GnStats st;
   };
-  GnEmit emit_for(int64_t hw, int Cout) {
-    GnEmit e;
-    if (hw >= 1024) e.buf = ctx->arena.get<float>(gn_part_floats(N, hw, Cout));
-    return e;
-  }
 
   // ResnetBlock2D; `skip` (up path): the input is torch.cat([x, skip], dim=1) — never materialised when both tensors carry
   // their column sums: GroupNorm reads the two sources, the 1x1 shortcut takes a two-source A operand
@@ -346,7 +341,7 @@ struct UnetRun {
     Act out;
     out.C = r.c2.Cout;
     h16* outp = ctx->arena.get<h16>(P * r.c2.Opad);
-    GnEmit eo = emit_for(HW, r.c2.Opad);
+    GnEmit eo = emit_for(ctx, N, HW, r.c2.Opad);
     ctx->arena.push();
     const bool virt = skip && x.st.valid() && skip->st.valid() && Cx % 64 == 0 && r.has_sc;   // virtual concat
     const h16* xin = x.p;
@@ -356,12 +351,12 @@ struct UnetRun {
       xin = cat;
     }
     h16* t1 = ctx->arena.get<h16>(P * r.c1.Opad);
-    GnEmit e1 = emit_for(HW, r.c1.Opad);
+    GnEmit e1 = emit_for(ctx, N, HW, r.c1.Opad);
     // GroupNorm + SiLU -> conv.  fp8=1 (MX fp8 convs, conv_halo_fp8.hip): the normalised tensor is written as e4m3 + one E8M0 scale per 32
     // channels by the apply pass itself (gn_apply_mx) — or, where the statistics do not come from an epilogue, by a quantising pass over
     // the 16-bit tensor — and the conv runs on v_mfma_scale_f32_16x16x128_f8f6f4 at twice the 16-bit matrix rate.
     auto norm_conv = [&](const h16* a, int Ca, const h16* a2, int Ca2, const NormW& nw, const GnStats* s1, const GnStats* s2, const ConvW& cw, h16* o,
-                         const float* bbn, int bbn_ld, const h16* resid, GnEmit* e, int conv_bit) {
+                         const ConvOpts& co, int conv_bit) {
       const int Cn = Ca + Ca2;
       ctx->arena.push();
       const bool site_on = ((sites >> r.site) & 1) && ((sites >> conv_bit) & 1);      // this call's placement mask
@@ -374,24 +369,27 @@ struct UnetRun {
           groupnorm(ctx, a, Ca, a2, Ca2, nw.g, nw.b, t, N, HW, m->groups, 1e-5f, 1, s, s1, s2);
           quant_act_mx(ctx, t, Cn, q, qs, P, s);
         }
-        conv3x3_fp8(ctx, q, qs, cw, o, N, H, W, bbn, bbn_ld, resid, s, e);
+        conv3x3_fp8(ctx, q, qs, cw, o, N, H, W, A_CONV_S1, s, co);
       } else {
         h16* t = ctx->arena.get<h16>(P * Cn);
         groupnorm(ctx, a, Ca, a2, Ca2, nw.g, nw.b, t, N, HW, m->groups, 1e-5f, 1, s, s1, s2);
-        conv3x3(ctx, t, cw, o, N, H, W, A_CONV_S1, bbn, bbn_ld, resid, 0, s, e);
+        conv3x3(ctx, t, cw, o, N, H, W, A_CONV_S1, s, co);
       }
       ctx->arena.pop();
     };
-    if (virt) norm_conv(x.p, Cx, skip->p, Cs, r.n1, &x.st, &skip->st, r.c1, t1, temb + r.temb_off, temb_ld, nullptr, &e1, 10);
-    else norm_conv(xin, Cin, nullptr, 0, r.n1, skip ? nullptr : &x.st, nullptr, r.c1, t1, temb + r.temb_off, temb_ld, nullptr, &e1, 10);
-    const h16* res = xin;
+    ConvOpts c1, c2;      // conv1 adds this resnet's time_emb_proj row of every sample, conv2 the (shortcut of the) input
+    c1.bias_bn = temb + r.temb_off; c1.bias_bn_ld = temb_ld; c1.emit = &e1;
+    if (virt) norm_conv(x.p, Cx, skip->p, Cs, r.n1, &x.st, &skip->st, r.c1, t1, c1, 10);
+    else norm_conv(xin, Cin, nullptr, 0, r.n1, skip ? nullptr : &x.st, nullptr, r.c1, t1, c1, 10);
+    c2.residual = xin; c2.emit = &eo;
     if (r.has_sc) {
       h16* sc = ctx->arena.get<h16>(P * r.sc.N);
-      if (virt) linear(ctx, x.p, Cx, r.sc, sc, r.sc.N, (int)P, ACT_NONE, nullptr, 0, 0, s, nullptr, nullptr, nullptr, 0, skip->p, Cs, Cx);
-      else linear(ctx, xin, Cin, r.sc, sc, r.sc.N, (int)P, ACT_NONE, nullptr, 0, 0, s);
-      res = sc;
+      LinearOpts cat;      // virtual concat: the shortcut reads [x | skip] as a two-source A operand
+      if (virt) { cat.A2 = skip->p; cat.lda2 = Cs; cat.k_split = Cx; }
+      linear(ctx, virt ? x.p : xin, virt ? Cx : Cin, r.sc, sc, r.sc.N, (int)P, s, cat);
+      c2.residual = sc;
     }
-    norm_conv(t1, r.n2.C, nullptr, 0, r.n2, &e1.st, nullptr, r.c2, outp, nullptr, 0, res, &eo, 11);
+    norm_conv(t1, r.n2.C, nullptr, 0, r.n2, &e1.st, nullptr, r.c2, outp, c2, 11);
     ctx->arena.pop();
     out.p = outp;
     out.st = eo.st;
@@ -409,35 +407,13 @@ struct UnetRun {
     attention(ctx, a, s);
   }
 
-  // V^T[b] (C x SkvPad) = Wv * src_b^T
-  void vt_proj_into(const PackedLinear& wv, const h16* src, int rows, int rows_pad, int K, h16* vt,
-                    const float* ln_rs = nullptr, const float* ln_rm = nullptr) {
-    const int C = wv.N;
-    GemmArgs g;
-    g.A = wv.w; g.lda = K; g.Wt = src; g.ldb = K; g.M = C; g.N = rows_pad; g.n_valid = rows; g.K = K;
-    g.batch = N; g.sA = 0; g.sB = (int64_t)rows * K; g.sC = (int64_t)C * rows_pad;
-    g.C = vt; g.ldc = rows_pad;
-    SVG_CHECK((wv.ln_s != nullptr) == (ln_rs != nullptr), "vt_proj: LayerNorm-folded weights need the token statistics");
-    if (ln_rs) {   // the normalised tokens are the B operand here: statistics per column, sums / bias per row
-      g.ln_rs = ln_rs; g.ln_rm = ln_rm; g.ln_s = wv.ln_s; g.ln_swapped = 1; g.ln_zstride = rows;
-      g.bias = wv.b; g.bias_row = 1;
-    }
-    gemm_auto(ctx, g, s, PK_GEMM);
-  }
-  h16* vt_proj(const PackedLinear& wv, const h16* src, int rows, int rows_pad, int K, const float* ln_rs = nullptr,
-                const float* ln_rm = nullptr) {
-    h16* vt = ctx->arena.get<h16>((int64_t)N * wv.N * rows_pad);
-    vt_proj_into(wv, src, rows, rows_pad, K, vt, ln_rs, ln_rm);
-    return vt;
-  }
-
   Act spatial_transformer(const Act& xa, const XfBlockW& b, int H, int W) {
     const h16* x = xa.p;
     const int HW = H * W, C = b.C;
     const int64_t P = (int64_t)N * HW;
     const int M = (int)P;
     h16* out = ctx->arena.get<h16>(P * C);
-    GnEmit eo = emit_for(HW, C);
+    GnEmit eo = emit_for(ctx, N, HW, C);
     ctx->arena.push();
     h16* h = ctx->arena.get<h16>(P * C);
     // LayerNorm row partials: the three LayerNorm inputs of the block (proj_in output, the two attention residual sums) are written by
@@ -463,24 +439,21 @@ struct UnetRun {
       g.batch = N; g.sA = (int64_t)HW * C; g.sB = (int64_t)C * C; g.sC = (int64_t)HW * C;
       g.bias = bb; g.bias_zs = C; g.C = h; g.ldc = C;
       const GemmPlan plan = gemm_plan(g);
-      {
-        static const int use_ln = getenv("SVG_LN_EPI") ? atoi(getenv("SVG_LN_EPI")) : 1;
-        const int tiles = use_ln ? plan.ln_tiles : 0;
-        le.tiles = 0;
-        if (tiles > 0 && tiles <= 5) { g.ln_part = le.buf; g.ln_tiles = tiles; le.tiles = tiles; }
-      }
+      plan_ln_emit(g, plan, &le);
       gemm_auto(ctx, g, plan, s, PK_GEMM);
       ctx->arena.pop();
     } else {
       h16* n0 = ctx->arena.get<h16>(P * C);
       groupnorm(ctx, x, C, nullptr, 0, b.gn.g, b.gn.b, n0, N, HW, m->groups, 1e-6f, 0, s, &xa.st, nullptr);
-      linear(ctx, n0, C, b.proj_in, h, C, M, ACT_NONE, nullptr, 0, 0, s, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, &le);
+      LinearOpts o; o.ln = &le;
+      linear(ctx, n0, C, b.proj_in, h, C, M, s, o);
     }
     // LayerNorms: folded into the consuming projections (row statistics only) unless SVG_LN_FOLD=0
     const bool fold = b.qk1.ln_s != nullptr;
     h16* ln = fold ? nullptr : ctx->arena.get<h16>(P * C);
     float* rs = fold ? ctx->arena.get<float>(M + 8) : nullptr;
     float* rm = fold ? ctx->arena.get<float>(M + 8) : nullptr;
+    LinearOpts stat; stat.ln_rs = rs; stat.ln_rm = rm;       // a LayerNorm-folded projection: the current row statistics
     auto norm = [&](const h16* src, const NormW& n) -> const h16* {
       if (fold) {
         if (le.tiles > 0) ln_finish(ctx, le.buf, le.tiles, rs, rm, M, C, 1e-5f, s);   // src's producer left its row partials
@@ -514,8 +487,9 @@ struct UnetRun {
         if (qkv_env && plan.family == GF_WS) { gemm_auto(ctx, g, plan, s, PK_GEMM); fused = true; }
       }
       if (!fused) {
-        linear(ctx, a1, C, b.qk1, qk, 2 * C, M, ACT_NONE, nullptr, 0, 0, s, rs, rm);
-        vt = vt_proj(b.v1, a1, HW, HWp, C, rs, rm);
+        linear(ctx, a1, C, b.qk1, qk, 2 * C, M, s, stat);
+        vt = ctx->arena.get<h16>((int64_t)N * C * HWp);
+        vt_proj_into(ctx, b.v1, a1, N, HW, HWp, C, vt, s, rs, rm);
       }
       attn_core(qk, 2 * C, qk + C, 2 * C, (int64_t)HW * 2 * C, vt, HWp, (int64_t)C * HWp, ao, C, HW, HW);
       ctx->arena.pop();
@@ -525,53 +499,39 @@ struct UnetRun {
     const bool xa_one = fold && b.xq && xattn_fused_supported(C, m->heads, M, HW, L);
     // ... and, CHAIN form, the self-attention's output projection + residual in front of it: h1 is never written
     const bool xa_chain = xa_one && xattn_chain_enabled() && b.o1.K == C && b.o1.N == C;
-    if (!xa_chain) linear(ctx, ao, C, b.o1, h1, C, M, ACT_NONE, h, C, 0, s, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, xa_one ? nullptr : &le);
+    LinearOpts o1, o2;     // the attention output projections: + residual, leaving the row partials of the next LayerNorm
+    o1.residual = h; o1.ldr = C; o1.ln = xa_one ? nullptr : &le;
+    if (!xa_chain) linear(ctx, ao, C, b.o1, h1, C, M, s, o1);
     h16* h2 = ctx->arena.get<h16>(P * C);
     // ---- cross-attention
     const h16* a2 = xa_one ? h1 : norm(h1, b.ln2);
     {
       ctx->arena.push();
       h16* q = xa_one ? nullptr : ctx->arena.get<h16>(P * C);
-      if (!xa_one) linear(ctx, a2, C, b.q2, q, C, M, ACT_NONE, nullptr, 0, 0, s, rs, rm);
+      if (!xa_one) linear(ctx, a2, C, b.q2, q, C, M, s, stat);
       const int idx = xf_idx++;
       const int64_t kn = (int64_t)N * L * C, vn = (int64_t)N * C * Lp;
-      h16 *k, *vt;
-      h16* const unset = (h16*)(uintptr_t)0x1000;     // dry pass before the cache exists: never dereferenced (nothing is launched)
       // the cache lives outside the arena (it survives the call); plan mode sizes it too, so the first real step allocates nothing
       const bool grow_cache = cache && (SVG_LAUNCHING(ctx) || ctx->plan_only);
-      if (cache) {
+      // slot idx of one cached tensor with room for n elements (a growth invalidates the cache), or n arena elements without a cache
+      auto kv_buf = [&](std::vector<KvCache::Slot> KvCache::*which, int64_t n) -> h16* {
+        if (!cache) return ctx->arena.get<h16>(n);
+        std::vector<KvCache::Slot>& v = cache->*which;
         if (grow_cache) {
-          if ((int)cache->k.size() <= idx) { cache->k.resize(idx + 1, nullptr); cache->vt.resize(idx + 1, nullptr); cache->k_cap.resize(idx + 1, 0); cache->vt_cap.resize(idx + 1, 0); }
-          if (cache->k_cap[idx] < kn) { cache->k[idx] = (h16*)ctx->dalloc(kn * sizeof(h16)); cache->k_cap[idx] = kn; cache->valid = false; }
-          if (cache->vt_cap[idx] < vn) { cache->vt[idx] = (h16*)ctx->dalloc(vn * sizeof(h16)); cache->vt_cap[idx] = vn; cache->valid = false; }
+          if ((int)v.size() <= idx) v.resize(idx + 1);
+          if (v[idx].cap < n) { v[idx].p = (h16*)ctx->dalloc(n * sizeof(h16)); v[idx].cap = n; cache->valid = false; }
         }
-        const bool have = idx < (int)cache->k.size() && cache->k[idx];
-        k = have ? cache->k[idx] : unset; vt = have ? cache->vt[idx] : unset;
-      } else {
-        k = ctx->arena.get<h16>(kn);
-        vt = ctx->arena.get<h16>(vn);
-      }
-      h16 *kp = nullptr, *vp = nullptr;
-      if (xa_one) {
-        const int64_t pn = xattn_kv_pack_elems(N);
-        if (cache) {
-          if (grow_cache) {
-            if ((int)cache->kp.size() <= idx) { cache->kp.resize(idx + 1, nullptr); cache->vp.resize(idx + 1, nullptr); cache->kvp_cap.resize(idx + 1, 0); }
-            if (cache->kvp_cap[idx] < pn) {
-              cache->kp[idx] = (h16*)ctx->dalloc(pn * sizeof(h16)); cache->vp[idx] = (h16*)ctx->dalloc(pn * sizeof(h16));
-              cache->kvp_cap[idx] = pn; cache->valid = false;
-            }
-          }
-          const bool have = idx < (int)cache->kp.size() && cache->kp[idx];
-          kp = have ? cache->kp[idx] : unset; vp = have ? cache->vp[idx] : unset;
-        } else {
-          kp = ctx->arena.get<h16>(pn);
-          vp = ctx->arena.get<h16>(pn);
-        }
-      }
+        if (idx < (int)v.size() && v[idx].p) return v[idx].p;
+        return (h16*)(uintptr_t)0x1000;     // dry pass before the cache exists: never dereferenced (nothing is launched)
+      };
+      h16* k = kv_buf(&KvCache::k, kn);
+      h16* vt = kv_buf(&KvCache::vt, vn);
+      const int64_t pn = xattn_kv_pack_elems(N);
+      h16* kp = xa_one ? kv_buf(&KvCache::kp, pn) : nullptr;
+      h16* vp = xa_one ? kv_buf(&KvCache::vp, pn) : nullptr;
       if (!(cache && cache->valid && SVG_LAUNCHING(ctx))) {
-        linear(ctx, ctxb, m->ctx_dim, b.k2, k, C, N * L, ACT_NONE, nullptr, 0, 0, s);
-        vt_proj_into(b.v2, ctxb, L, Lp, m->ctx_dim, vt);
+        linear(ctx, ctxb, m->ctx_dim, b.k2, k, C, N * L, s);
+        vt_proj_into(ctx, b.v2, ctxb, N, L, Lp, m->ctx_dim, vt, s);
         if (xa_one && SVG_LAUNCHING(ctx)) xattn_pack_kv(k, C, (int64_t)L * C, vt, Lp, (int64_t)C * Lp, kp, vp, N, L, s);
       }
       if (xa_chain) xattn_fused(ctx, ao, C, h, C, b.o1.w, b.o1.b, nullptr, nullptr, b.xqp, b.xq_s, b.xq_b, kp, vp, b.xo, b.o2.b, h2, C, M, HW, L, s);
@@ -579,7 +539,8 @@ struct UnetRun {
       else attn_core(q, C, k, C, (int64_t)L * C, vt, Lp, (int64_t)C * Lp, ao, C, HW, L);
       ctx->arena.pop();
     }
-    if (!xa_one) linear(ctx, ao, C, b.o2, h2, C, M, ACT_NONE, h1, C, 0, s, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, &le);
+    o2.residual = h1; o2.ldr = C; o2.ln = &le;
+    if (!xa_one) linear(ctx, ao, C, b.o2, h2, C, M, s, o2);
     // ---- GEGLU feed-forward
     const bool ff_one = fold && b.ff2p && ff_fused_supported(C, M);
     const h16* a3 = ff_one ? h2 : norm(h2, b.ln3);     // the fused feed-forward takes its LayerNorm statistics from the rows it holds
@@ -596,13 +557,17 @@ struct UnetRun {
       h16* g = ctx->arena.get<h16>((int64_t)std::min(rows, M) * 4 * C);
       for (int m0 = 0; m0 < M; m0 += rows) {
         const int mc = std::min(rows, M - m0);
-        linear(ctx, a3 + (int64_t)m0 * C, C, b.ff1, g, 4 * C, mc, ACT_GEGLU, nullptr, 0, 0, s, rs ? rs + m0 : nullptr, rm ? rm + m0 : nullptr);
-        linear(ctx, g, 4 * C, b.ff2, h + (int64_t)m0 * C, C, mc, ACT_NONE, h2 + (int64_t)m0 * C, C, 0, s);   // h is free again: reuse as h3
+        LinearOpts f1, f2;
+        f1.act = ACT_GEGLU; f1.ln_rs = rs ? rs + m0 : nullptr; f1.ln_rm = rm ? rm + m0 : nullptr;
+        f2.residual = h2 + (int64_t)m0 * C; f2.ldr = C;
+        linear(ctx, a3 + (int64_t)m0 * C, C, b.ff1, g, 4 * C, mc, s, f1);
+        linear(ctx, g, 4 * C, b.ff2, h + (int64_t)m0 * C, C, mc, s, f2);   // h is free again: reuse as h3
       }
       ctx->arena.pop();
       }
     }
-    linear(ctx, h, C, b.proj_out, out, C, M, ACT_NONE, x, C, 0, s, nullptr, nullptr, &eo, HW);
+    LinearOpts po; po.residual = x; po.ldr = C; po.emit = &eo; po.rows_per_sample = HW;
+    linear(ctx, h, C, b.proj_out, out, C, M, s, po);
     ctx->arena.pop();
     Act o;
     o.p = out; o.C = C; o.st = eo.st;
@@ -639,23 +604,26 @@ void UnetModel::run(svg_ctx* ctx, const float* x, int N, int h, int w, const flo
   h16* te0 = ctx->arena.get<h16>((int64_t)N * c0);
   if (SVG_LAUNCHING(ctx)) { ProfScope ps(ctx, PK_ELT, s, 0, 0); timestep_embed(timesteps, te0, N, c0, s); }
   h16* te1 = ctx->arena.get<h16>((int64_t)N * temb_dim);
-  linear(ctx, te0, c0, time1, te1, temb_dim, N, ACT_SILU, nullptr, 0, 0, s);
+  LinearOpts silu, f32o; silu.act = ACT_SILU; f32o.out_f32 = 1;
+  linear(ctx, te0, c0, time1, te1, temb_dim, N, s, silu);
   h16* te2 = ctx->arena.get<h16>((int64_t)N * temb_dim);
-  linear(ctx, te1, temb_dim, time2, te2, temb_dim, N, ACT_SILU, nullptr, 0, 0, s);   // SiLU(temb), shared by all resnets
+  linear(ctx, te1, temb_dim, time2, te2, temb_dim, N, s, silu);   // SiLU(temb), shared by all resnets
   float* tall = ctx->arena.get<float>((int64_t)N * temb_all.N);
-  linear(ctx, te2, temb_dim, temb_all, tall, temb_all.N, N, ACT_NONE, nullptr, 0, 1, s);
+  linear(ctx, te2, temb_dim, temb_all, tall, temb_all.N, N, s, f32o);
   r.temb = tall; r.temb_ld = temb_all.N;
 
   // ---- conv_in
   typedef UnetRun::Act Act;
+  ConvOpts co;      // the plain convs between the blocks: the GroupNorm column sums of the output, nothing else
   h16* x0 = ctx->arena.get<h16>((int64_t)N * h * w * 8);
   if (SVG_LAUNCHING(ctx)) { ProfScope ps(ctx, PK_ELT, s, 0, 0); nchw_to_act(x, x0, N, in_ch, h, w, 8, 1.f, s); }
   int H = h, W = w;
   Act cur;
   {
     h16* y = ctx->arena.get<h16>((int64_t)N * H * W * conv_in.Opad);
-    GnEmit e = r.emit_for((int64_t)H * W, conv_in.Opad);
-    conv3x3(ctx, x0, conv_in, y, N, H, W, A_CONV_S1, nullptr, 0, nullptr, 0, s, &e);
+    GnEmit e = emit_for(ctx, N, (int64_t)H * W, conv_in.Opad);
+    co.emit = &e;
+    conv3x3(ctx, x0, conv_in, y, N, H, W, A_CONV_S1, s, co);
     cur.p = y; cur.C = c0; cur.st = e.st;
   }
   std::vector<Act> skips{cur};
@@ -668,8 +636,9 @@ void UnetModel::run(svg_ctx* ctx, const float* x, int N, int h, int w, const flo
     }
     if (i < nb - 1) {
       h16* y = ctx->arena.get<h16>((int64_t)N * (H / 2) * (W / 2) * down_s[i].Opad);
-      GnEmit e = r.emit_for((int64_t)(H / 2) * (W / 2), down_s[i].Opad);
-      conv3x3(ctx, cur.p, down_s[i], y, N, H, W, A_CONV_S2P1, nullptr, 0, nullptr, 0, s, &e);
+      GnEmit e = emit_for(ctx, N, (int64_t)(H / 2) * (W / 2), down_s[i].Opad);
+      co.emit = &e;
+      conv3x3(ctx, cur.p, down_s[i], y, N, H, W, A_CONV_S2P1, s, co);
       cur.p = y; cur.st = e.st; H /= 2; W /= 2;
       skips.push_back(cur);
     }
@@ -688,17 +657,18 @@ void UnetModel::run(svg_ctx* ctx, const float* x, int N, int h, int w, const flo
     }
     if (i < nb - 1) {
       h16* y = ctx->arena.get<h16>((int64_t)N * (2 * H) * (2 * W) * up_s[i].Opad);
-      GnEmit e = r.emit_for((int64_t)4 * H * W, up_s[i].Opad);
+      GnEmit e = emit_for(ctx, N, (int64_t)4 * H * W, up_s[i].Opad);
+      co.emit = &e;
       if (((fp8_sites >> 9) & 1) && conv3x3_fp8_ok(up_s[i], N, H, W, true)) {      // fp8=1: quantise the (small) source image, conv on the MX fp8 path
         ctx->arena.push();
         const int64_t Ps = (int64_t)N * H * W, Cp = align_up(up_s[i].Cin, 128);
         uint8_t* q = ctx->arena.get<uint8_t>(Ps * Cp);
         uint8_t* qs = ctx->arena.get<uint8_t>(Ps * (Cp / 32));
         quant_act_mx(ctx, cur.p, up_s[i].Cin, q, qs, Ps, s);
-        conv3x3_fp8(ctx, q, qs, up_s[i], y, N, H, W, nullptr, 0, nullptr, s, &e, true);
+        conv3x3_fp8(ctx, q, qs, up_s[i], y, N, H, W, A_CONV_UP2, s, co);
         ctx->arena.pop();
       } else
-      conv3x3(ctx, cur.p, up_s[i], y, N, H, W, A_CONV_UP2, nullptr, 0, nullptr, 0, s, &e);
+      conv3x3(ctx, cur.p, up_s[i], y, N, H, W, A_CONV_UP2, s, co);
       cur.p = y; cur.st = e.st; H *= 2; W *= 2;
     }
   }
@@ -706,7 +676,8 @@ void UnetModel::run(svg_ctx* ctx, const float* x, int N, int h, int w, const flo
   h16* t = ctx->arena.get<h16>((int64_t)N * H * W * c0);
   groupnorm(ctx, cur.p, c0, nullptr, 0, norm_out.g, norm_out.b, t, N, H * W, groups, 1e-5f, 1, s, &cur.st, nullptr);
   float* o = ctx->arena.get<float>((int64_t)N * H * W * conv_out.Opad);
-  conv3x3(ctx, t, conv_out, o, N, H, W, A_CONV_S1, nullptr, 0, nullptr, 1, s);
+  ConvOpts of32; of32.out_f32 = 1;
+  conv3x3(ctx, t, conv_out, o, N, H, W, A_CONV_S1, s, of32);
   if (SVG_LAUNCHING(ctx)) { ProfScope ps(ctx, PK_ELT, s, 0, 0); actf32_to_nchw(o, conv_out.Opad, eps_out, N, out_ch, H, W, s); }
   if (cache && SVG_LAUNCHING(ctx)) cache->valid = true;   // every block's K / V^T of this context is now stored
 }

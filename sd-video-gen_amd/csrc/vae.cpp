@@ -129,19 +129,15 @@ struct VaeRun {
     if (x.f) groupnorm_f32(ctx, x.f, nw.C, nw.g, nw.b, out, N, HW, m->groups, EPS, silu, s, &x.st);
     else groupnorm(ctx, x.p, nw.C, nullptr, 0, nw.g, nw.b, out, N, HW, m->groups, EPS, silu, s, &x.st, nullptr);
   }
-  GnEmit emit_for(int64_t hw, int Cout) {
-    GnEmit e;
-    if (hw >= 1024) e.buf = ctx->arena.get<float>(gn_part_floats(N, hw, Cout));
-    return e;
-  }
   // the input: a 16-bit tensor, or a stream tensor (read through its 16-bit copy)
   Act conv(const Act& xa, const ConvW& cw, int H, int W, int amode) {
-    const int Ho = amode == A_CONV_UP2 ? 2 * H : (amode == A_CONV_S2ASYM ? H / 2 : H), Wo = amode == A_CONV_UP2 ? 2 * W : (amode == A_CONV_S2ASYM ? W / 2 : W);
-    Act y = alloc_act((int64_t)N * Ho * Wo, cw.Opad);
-    GnEmit e = emit_for((int64_t)Ho * Wo, cw.Opad);
+    const ConvDims d = conv_out_dims(amode, H, W);
+    Act y = alloc_act((int64_t)N * d.Ho * d.Wo, cw.Opad);
+    GnEmit e = emit_for(ctx, N, (int64_t)d.Ho * d.Wo, cw.Opad);
     ctx->arena.push();
     const h16* x = as_h16(xa, (int64_t)N * H * W * cw.Cin);
-    conv3x3(ctx, x, cw, ptr(y), N, H, W, amode, nullptr, 0, nullptr, out_mode(), s, &e);
+    ConvOpts o; o.out_f32 = out_mode(); o.emit = &e;
+    conv3x3(ctx, x, cw, ptr(y), N, H, W, amode, s, o);
     ctx->arena.pop();
     y.st = e.st;
     return y;
@@ -152,23 +148,23 @@ struct VaeRun {
   Act resnet(const Act& x, const ResW& r, int H, int W) {
     const int64_t P = (int64_t)N * H * W;
     Act out = alloc_act(P, r.c2.Opad);
-    GnEmit eo = emit_for((int64_t)H * W, r.c2.Opad);
+    GnEmit eo = emit_for(ctx, N, (int64_t)H * W, r.c2.Opad);
     ctx->arena.push();
     h16* t0 = ctx->arena.get<h16>(P * r.n1.C);
     norm(x, r.n1, t0, H * W, 1);
     h16* t1 = ctx->arena.get<h16>(P * r.c1.Opad);
-    GnEmit e1 = emit_for((int64_t)H * W, r.c1.Opad);
-    conv3x3(ctx, t0, r.c1, t1, N, H, W, A_CONV_S1, nullptr, 0, nullptr, 0, s, &e1);
+    GnEmit e1 = emit_for(ctx, N, (int64_t)H * W, r.c1.Opad);
+    ConvOpts c1, c2; c1.emit = &e1;
+    conv3x3(ctx, t0, r.c1, t1, N, H, W, A_CONV_S1, s, c1);
     h16* t2 = ctx->arena.get<h16>(P * r.n2.C);
     groupnorm(ctx, t1, r.n2.C, nullptr, 0, r.n2.g, r.n2.b, t2, N, H * W, m->groups, EPS, 1, s, &e1.st, nullptr);
-    const h16* res = x.p;
-    const float* res_f = x.f;
+    c2.residual = x.p; c2.residual_f32 = x.f; c2.out_f32 = out_mode(); c2.emit = &eo;
     if (r.has_sc) {
       h16* sc = ctx->arena.get<h16>(P * r.sc.N);
-      linear(ctx, as_h16(x, P * r.n1.C), r.n1.C, r.sc, sc, r.sc.N, (int)P, ACT_NONE, nullptr, 0, 0, s);
-      res = sc; res_f = nullptr;
+      linear(ctx, as_h16(x, P * r.n1.C), r.n1.C, r.sc, sc, r.sc.N, (int)P, s);
+      c2.residual = sc; c2.residual_f32 = nullptr;
     }
-    conv3x3(ctx, t2, r.c2, ptr(out), N, H, W, A_CONV_S1, nullptr, 0, res, out_mode(), s, &eo, res_f);
+    conv3x3(ctx, t2, r.c2, ptr(out), N, H, W, A_CONV_S1, s, c2);
     ctx->arena.pop();
     out.st = eo.st;
     return out;
@@ -180,21 +176,15 @@ struct VaeRun {
     const int64_t P = (int64_t)N * HW;
     const int HWp = (int)align_up(HW, 8);
     Act y = alloc_act(P, C);
-    GnEmit eo = emit_for(HW, C);
+    GnEmit eo = emit_for(ctx, N, HW, C);
     ctx->arena.push();
     h16* n = ctx->arena.get<h16>(P * C);
     norm(xa, a.gn, n, HW, 0);
     h16* qk = ctx->arena.get<h16>(P * 2 * C);
-    linear(ctx, n, C, a.qk, qk, 2 * C, (int)P, ACT_NONE, nullptr, 0, 0, s);
+    linear(ctx, n, C, a.qk, qk, 2 * C, (int)P, s);
     // V^T[b] = Wv * n_b^T + bv (per row)
     h16* vt = ctx->arena.get<h16>((int64_t)N * C * HWp);
-    {
-      GemmArgs g;
-      g.A = a.v.w; g.lda = C; g.Wt = n; g.ldb = C; g.M = C; g.N = HWp; g.n_valid = HW; g.K = C;
-      g.batch = N; g.sA = 0; g.sB = (int64_t)HW * C; g.sC = (int64_t)C * HWp;
-      g.bias = a.v.b; g.bias_row = 1; g.C = vt; g.ldc = HWp;
-      gemm_auto(ctx, g, s, PK_GEMM);
-    }
+    vt_proj_into(ctx, a.v, n, N, HW, HWp, C, vt, s);
     h16* o = ctx->arena.get<h16>(P * C);
     if (vae_attention_supported(HW, C, 2 * C, HWp, C)) {
       // flash-style, the head dimension split over the waves of a workgroup (attn_vae.hip): no S x S matrix in HBM
@@ -218,7 +208,8 @@ struct VaeRun {
         gemm_auto(ctx, g, s, PK_GEMM);
       }
     }
-    linear(ctx, o, C, a.proj, ptr(y), C, (int)P, ACT_NONE, xa.p, C, out_mode(), s, nullptr, nullptr, &eo, HW, nullptr, 0, 0, nullptr, xa.f);
+    LinearOpts po; po.residual = xa.p; po.residual_f32 = xa.f; po.ldr = C; po.out_f32 = out_mode(); po.emit = &eo; po.rows_per_sample = HW;
+    linear(ctx, o, C, a.proj, ptr(y), C, (int)P, s, po);
     ctx->arena.pop();
     y.st = eo.st;
     return y;
@@ -257,7 +248,8 @@ void VaeModel::encode(svg_ctx* ctx, const uint8_t* img, int N, int srcH, int src
     h16* t = r.norm_act(x, e_norm_out, h, w);
     const int64_t P = (int64_t)N * h * w;
     float* mom0 = ctx->arena.get<float>(P * 8);
-    conv3x3(ctx, t, e_conv_out, mom0, N, h, w, A_CONV_S1, nullptr, 0, nullptr, 1, s);
+    ConvOpts of32; of32.out_f32 = 1;
+    conv3x3(ctx, t, e_conv_out, mom0, N, h, w, A_CONV_S1, s, of32);
     float* mom = ctx->arena.get<float>(P * 8);
     if (SVG_LAUNCHING(ctx)) {
       ProfScope ps(ctx, PK_ELT, s, 0, 0);
@@ -299,7 +291,8 @@ void VaeModel::decode(svg_ctx* ctx, const float* z, int N, int h, int w, uint8_t
     }
     h16* t = r.norm_act(x, d_norm_out, H, W);
     float* o = ctx->arena.get<float>((int64_t)N * H * W * 4);
-    conv3x3(ctx, t, d_conv_out, o, N, H, W, A_CONV_S1, nullptr, 0, nullptr, 1, s);
+    ConvOpts of32; of32.out_f32 = 1;
+    conv3x3(ctx, t, d_conv_out, o, N, H, W, A_CONV_S1, s, of32);
     if (SVG_LAUNCHING(ctx)) {
       ProfScope ps(ctx, PK_ELT, s, 0, 0);
       act_to_img(o, 4, img_out, float_out, N, H, W, img_out ? outH : H, img_out ? outW : W, s);

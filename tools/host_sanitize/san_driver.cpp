@@ -88,9 +88,11 @@ static void transformer(int text_dim, int dm = 32, int d_lat = 64, int ffn = 204
   EXPECT_ERR(svg_transformer_tensor(ctx, SVG_TENSOR_PARAM, "no.such.weight", w.data(), 1, nullptr));
 }
 
-static void vae(int f16) {
+static void vae(int f16, int stream_f32 = 0) {
   const int V = SVG_VAE;
-  OK(svg_model_configure(ctx, V, f16 ? "block_out=64,128;layers=1;groups=32;latent=4;f16=1" : "block_out=64,128;layers=1;groups=32;latent=4"));
+  char kv[128];
+  snprintf(kv, sizeof(kv), "block_out=64,128;layers=1;groups=32;latent=4;f16=%d;stream_f32=%d", f16, stream_f32);
+  OK(svg_model_configure(ctx, V, kv));
   auto attn = [&](const std::string& p, int c) {
     load_norm(V, p + ".group_norm", c);
     for (const char* n : {"query", "key", "value", "proj_attn"}) load_lin(V, p + "." + n, c, c);
@@ -238,6 +240,21 @@ static void ops() {
   int used = 0;
   OK(svg_op_conv3x3_gn(ctx, x.data(), w.data(), b2.data(), g.data(), be.data(), y.data(), y2.data(), 2, 32, 32, 64, 64, 32, 1e-5f, 1, &used, nullptr));
   OK(svg_op_groupnorm_f16(ctx, x.data(), g.data(), be.data(), y.data(), 2, 1024, 64, 32, 1e-5f, 1, nullptr));
+  // the conv hooks: every mode (the outputs are sized for the 2x upsample), the small-Cin conv, the f32 residual stream
+  std::vector<uint16_t> yb((size_t)2 * 64 * 64 * 128), gb = yb;
+  auto w2 = buf((size_t)128 * 64 * 9), yf = buf(yb.size()), rf = buf(yb.size(), 0.f), g2 = buf(128, 1.f), be2 = buf(128, 0.f);
+  for (int mode = 0; mode < 4; ++mode) OK(svg_op_conv3x3(ctx, x.data(), w.data(), b2.data(), yb.data(), 2, 32, 32, 64, 64, mode, nullptr));
+  OK(svg_op_conv3x3_f16(ctx, x.data(), w.data(), nullptr, yb.data(), 2, 32, 32, 8, 64, 0, nullptr));
+  EXPECT_ERR(svg_op_conv3x3(ctx, x.data(), w.data(), b2.data(), yb.data(), 2, 32, 32, 64, 64, 4, nullptr));          // no such mode
+  int halo = 0;
+  for (int mode : {0, 2, 3}) {
+    OK(svg_op_conv3x3_f32s(ctx, x.data(), w2.data(), b2.data(), nullptr, mode == 0 ? rf.data() : nullptr, yf.data(), g2.data(), be2.data(), gb.data(), 2, 32,
+                           32, 64, 128, mode, 32, 1e-6f, 1, &halo, &used, nullptr));
+  }
+  OK(svg_op_conv3x3_f32s(ctx, x.data(), w2.data(), b2.data(), x.data(), nullptr, yf.data(), nullptr, nullptr, nullptr, 2, 32, 32, 64, 128, 0, 32, 1e-6f, 0,
+                         &halo, &used, nullptr));
+  // MX fp8: this size qualifies only under SVG_HALO_MIN=1 (else the hook reports that it does not: either way no sanitizer finding)
+  for (int mode : {0, 3}) (void)svg_op_conv3x3_mx(ctx, x.data(), w2.data(), b2.data(), nullptr, yb.data(), nullptr, nullptr, 2, 32, 32, 64, 128, mode, nullptr);
 }
 
 int main() {
@@ -249,6 +266,7 @@ int main() {
   transformer(384, 128, 128, 256);
   transformer(0, 256, 256, 256);                   // d = K = 256: one clip (6 rows) takes the small-row walk (xf_forward_walk_small: whole-K stage table)
   vae(0); vae(1);
+  vae(0, 1);                                       // the f32 residual stream (f32 conv / linear outputs and residuals)
   unet(0, 0); unet(1, 0); unet(0, 1);
   text_towers();
   i3d_and_fvd();
