@@ -20,7 +20,10 @@
  *                             0.012,'scaled_linear',1000), set_timesteps, add_noise, CFG combine,
  *                             scheduler.step) — the hot loop
  *   svg_sample_loop           the same loop with a DPM-Solver++(2M) update in place of scheduler.step
- *                             (an addition: the reference has only DDIM here)
+ *                             (an addition: the reference has only DDIM here), or, with SVG_SAMPLER_LMS,
+ *                             utils/sd_utils.py:97-126 (denoise_img_latents: LMSDiscreteScheduler(0.00085, 0.012,
+ *                             'scaled_linear', 1000), set_timesteps, sigma scaling, CFG combine, scheduler.step)
+ *   svg_lms_coefs / _step     that scheduler's timesteps, sigmas and coefficients (host only) / one update on caller data
  *   svg_clip_text_forward     utils/sd_utils.py:84,91 (self.text_encoder(input_ids)[0]: transformers CLIPTextModel of
  *                             'openai/clip-vit-large-patch14', last_hidden_state) — tokenisation stays on the host
  *   svg_resize_nearest_u8     prediction/predict.py:158,178 (F.interpolate on uint8, mode nearest)
@@ -208,6 +211,7 @@ int svg_ddim_step(svg_ctx* ctx, const float* x, const float* eps, float* prev, i
 /* Samplers of svg_sample_loop. */
 #define SVG_SAMPLER_DDIM 0      /* the update of svg_ddim_loop */
 #define SVG_SAMPLER_DPMPP_2M 1  /* DPM-Solver++(2M) */
+#define SVG_SAMPLER_LMS 2       /* linear multistep, order <= 4: the reference's text-to-image sampler (below) */
 /* The img2img loop of svg_ddim_loop under the update rule `sampler`: the same arguments, contract, timesteps
  * t_i = (num_steps-1-i)*1000/num_steps, add_noise at t_start, CFG combine, history and step graph.
  * SVG_SAMPLER_DDIM is exactly svg_ddim_loop.  SVG_SAMPLER_DPMPP_2M is the update of diffusers'
@@ -229,6 +233,33 @@ int svg_sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, int w, co
  * (> t); m_prev NULL: a first-order step, t_last ignored.  x / x_out and m_prev / m_out may alias. */
 int svg_dpmpp_step(svg_ctx* ctx, const float* x, const float* eps, const float* m_prev, float* x_out,
                    float* m_out, int64_t n, int t, int t_next, int t_last, void* stream);
+
+/* SVG_SAMPLER_LMS runs diffusers 0.2.3's LMSDiscreteScheduler(beta_start=0.00085, beta_end=0.012, 'scaled_linear', 1000) inside
+ * svg_sample_loop.  Its contract differs from the other two samplers:
+ *   - z holds unit-normal draws on entry; the loop scales them by sigma_0 (14.6146 at any step count) before the first step;
+ *   - start_step must be 0 (SVG_ERR_INVALID otherwise: the reference has no LMS img2img, and the rule is not well defined when
+ *     the history is shorter than the order); noise is ignored;
+ *   - the timesteps are t_i = linspace(999, 0, num_steps)[i], fractional, handed to the UNet as f32.
+ * With abar the f32 alphas_cumprod of the schedule and everything after it in double: sigma_i interpolates the train sigmas
+ * sqrt((1 - abar) / abar) linearly between floor(t_i) and ceil(t_i), sigma_num_steps = 0.  Step i: the UNet input is
+ * x / sqrt(sigma_i^2 + 1); d_i = eps_i after the CFG combine (the reference computes (x - (x - sigma_i eps_i)) / sigma_i, the same
+ * number up to f32 rounding); order = min(i + 1, 4);
+ *   c_k = integral over [sigma_i, sigma_{i+1}] of prod_{j != k} (tau - sigma_{i-j}) / (sigma_{i-k} - sigma_{i-j}),  k, j < order
+ * (a polynomial of degree <= 3, integrated exactly: no quadrature);  x <- x + sum_k c_k d_{i-k}.
+ * As for the other samplers, guidance == 0 runs the uncond half only, hist (num_steps + 1 latents, the first one the scaled
+ * draws) is filled on the direct-launch path, and the second step is captured and replayed.  Workspace: one table and a ring of
+ * four latent-sized derivative buffers.
+ *
+ * svg_lms_coefs: step i of a num_steps schedule, on the host (no context, no device): the timestep, sigma_i, sigma_{i+1}, the
+ * order and coefs[4] (zero beyond the order); any output pointer may be NULL.  SVG_ERR_INVALID outside 1 <= num_steps <= 1000,
+ * 0 <= i < num_steps. */
+int svg_lms_coefs(int num_steps, int i, double* timestep, double* sigma, double* sigma_next, int* order,
+                  double* coefs);
+/* One LMS update of that schedule on caller data (f32, n elements, no CFG combine): eps is stored to slot i & 3 of the caller's
+ * ring dhist (4 * n floats, which must hold the eps of the steps i-1 ... i-3 in their slots when the order asks for them), and
+ * x_out = x + sum_k c_k dhist[(i - k) & 3].  x / x_out may alias. */
+int svg_lms_step(svg_ctx* ctx, const float* x, const float* eps, float* dhist, float* x_out, int64_t n,
+                 int num_steps, int i, void* stream);
 
 int svg_resize_nearest_u8(svg_ctx* ctx, const uint8_t* src, int N, int sh, int sw, int C,
                           uint8_t* dst, int dh, int dw, void* stream);

@@ -14,11 +14,12 @@ LIB_PATH = os.environ.get("SVG_LIB") or os.path.join(_HERE, "libsvg_hip.so")   #
 
 SVG_TRANSFORMER, SVG_VAE, SVG_UNET, SVG_CLIP_TEXT, SVG_MINILM, SVG_I3D = 0, 1, 2, 3, 4, 5
 SVG_ERR_RUNTIME, SVG_ERR_INVALID = -1, -2        # enum svg_status
-SAMPLERS = {"ddim": 0, "dpmpp_2m": 1}              # SVG_SAMPLER_DDIM, SVG_SAMPLER_DPMPP_2M
+SAMPLERS = {"ddim": 0, "dpmpp_2m": 1, "lms": 2}    # SVG_SAMPLER_DDIM, SVG_SAMPLER_DPMPP_2M, SVG_SAMPLER_LMS
 
 
 def sampler_id(name):
-    """the SVG_SAMPLER_* id of a sampler name ("ddim", "dpmpp_2m"); ValueError for any other"""
+    """the SVG_SAMPLER_* id of a sampler name ("ddim", "dpmpp_2m", "lms"); ValueError for any other.  "lms" is the text-to-image
+    sampler of SDUtils.denoise_img_latents: Context.sample_loop takes it, the img2img entry points do not"""
     if name not in SAMPLERS:
         raise ValueError("unknown sampler %r (one of %s)" % (name, ", ".join(SAMPLERS)))
     return SAMPLERS[name]
@@ -97,6 +98,8 @@ SIGNATURES = {
     "svg_ddim_step": [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp],
     "svg_sample_loop": [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp],
     "svg_dpmpp_step": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp],
+    "svg_lms_coefs": [_i, _i, _vp, _vp, _vp, _vp, _vp],
+    "svg_lms_step": [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp],
     "svg_resize_bilinear_f32": [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp],
     "svg_resize_nearest_u8": [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
     "svg_op_gemm": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -213,6 +216,17 @@ def load():
 def env_refresh():
     """the library caches its $SVG_* knobs per name: call after changing one in-process (svg_env_refresh)"""
     load().svg_env_refresh()
+
+
+def lms_coefs(num_steps, i):
+    """step i of the LMS schedule of num_steps steps (svg_lms_coefs; host only, no context, no GPU):
+    (timestep, sigma_i, sigma_{i+1}, order, [c_0 .. c_3]) -- the coefficients zero beyond the order"""
+    lib = load()
+    t, sig, nxt, order, c = C.c_double(), C.c_double(), C.c_double(), C.c_int(), (C.c_double * 4)()
+    rc = lib.svg_lms_coefs(int(num_steps), int(i), C.byref(t), C.byref(sig), C.byref(nxt), C.byref(order), c)
+    if rc != 0:
+        raise (ValueError if rc == SVG_ERR_INVALID else RuntimeError)("svg_lms_coefs: " + lib.svg_last_error(None).decode())
+    return t.value, sig.value, nxt.value, order.value, list(c)
 
 
 def source_hash():
@@ -512,7 +526,9 @@ class Context:
         return hist if return_hist else z
 
     def sample_loop(self, z, text_emb, sampler="ddim", num_steps=50, start_step=0, guidance=7.5, noise=None, return_hist=False):
-        """ddim_loop with the update rule `sampler`: "ddim" (the same bits as ddim_loop) or "dpmpp_2m" (DPM-Solver++(2M), svg_sample_loop)"""
+        """ddim_loop with the update rule `sampler`: "ddim" (the same bits as ddim_loop) or "dpmpp_2m" (DPM-Solver++(2M), svg_sample_loop).
+        "lms" is the reference's text-to-image sampler on its own schedule (svg_hip.h, SVG_SAMPLER_LMS): z holds unit-normal draws,
+        start_step must be 0, noise is ignored"""
         sid = sampler_id(sampler)
         N, c, h, w = z.shape
         z = z.contiguous().float().clone()
@@ -535,6 +551,17 @@ class Context:
         self.check(self.lib.svg_dpmpp_step(self.h, _ptr(x), _ptr(eps), _ptr(m_prev), _ptr(out), _ptr(m), x.numel(), int(t), int(t_next),
                                            int(t_last), _stream()), "svg_dpmpp_step")
         return out, m
+
+    def lms_step(self, x, eps, dhist, num_steps, i, out=None):
+        """one LMS update of step i of a num_steps schedule on caller data (svg_lms_step): eps goes to slot i & 3 of the caller's ring
+        dhist (4, n) f32, which holds the earlier steps' eps; returns x + sum_k c_k dhist[(i - k) & 3] (in `out`, which may be x)"""
+        assert x.dtype == eps.dtype == dhist.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous() and dhist.is_contiguous()
+        assert dhist.numel() == 4 * x.numel() and eps.numel() == x.numel()
+        out = torch.empty_like(x) if out is None else out
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == x.numel()
+        self.check(self.lib.svg_lms_step(self.h, _ptr(x), _ptr(eps), _ptr(dhist), _ptr(out), x.numel(), int(num_steps), int(i), _stream()),
+                   "svg_lms_step")
+        return out
 
     def ddim_step(self, x, eps, t, t_prev):
         x = x.contiguous().float()

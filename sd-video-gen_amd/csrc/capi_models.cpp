@@ -14,6 +14,74 @@ void destroy_models(svg_ctx* ctx) {
   if (ctx->i3d) { ctx->i3d->ws.clear(); delete ctx->i3d; ctx->i3d = nullptr; }
 }
 
+// ---- DDIM table, as diffusers' DDIMScheduler builds it: betas = linspace(sqrt(b0), sqrt(b1), 1000, f32)**2,
+// alphas_cumprod = cumprod(1 - betas) in f32
+const std::vector<float>& sd_alphas_cumprod() {
+  static const std::vector<float> table = [] {
+    std::vector<float> alphas_cumprod(1000);
+    const double b0 = sqrt(0.00085), b1 = sqrt(0.012);
+    float prod = 1.f;
+    for (int i = 0; i < 1000; ++i) {
+      const double step = (b1 - b0) / 999.0;
+      float sb = (float)(i * step + b0);
+      if (i == 999) sb = (float)b1;
+      float beta = sb * sb;
+      float alpha = 1.f - beta;
+      prod = prod * alpha;
+      alphas_cumprod[i] = prod;
+    }
+    return alphas_cumprod;
+  }();
+  return table;
+}
+
+// The LMS schedule in double from the f32 alphas_cumprod.  The coefficient c_k integrates the Lagrange basis polynomial
+// prod_{j != k} (tau - sigma_{i-j}) / (sigma_{i-k} - sigma_{i-j}) (degree <= 3) over [sigma_i, sigma_{i+1}]: expanded in
+// u = tau - sigma_i (roots r_j = sigma_{i-j} - sigma_i, so nothing of the size of sigma^4 is subtracted) and integrated term by
+// term over [0, sigma_{i+1} - sigma_i] -- exact up to rounding, where diffusers runs scipy.integrate.quad(epsrel = 1e-4).
+void lms_coefs(int num_steps, int i, LmsCoef* out) {
+  SVG_CHECK(num_steps >= 1 && num_steps <= 1000 && i >= 0 && i < num_steps, "lms: step %d of %d out of range", i, num_steps);
+  const std::vector<float>& abar = sd_alphas_cumprod();
+  // numpy.linspace(999, 0, n): arange(n) * (-999 / (n - 1)) + 999 with the last element set to 0 (and [999] for n = 1)
+  auto timestep = [&](int j) -> double {
+    if (num_steps == 1) return 999.0;
+    if (j == num_steps - 1) return 0.0;
+    const double step = -999.0 / (num_steps - 1);
+    volatile double prod = j * step;      // rounded on its own, as numpy does (never a fused multiply-add)
+    return prod + 999.0;
+  };
+  auto sigma_at = [&](int j) -> double {
+    if (j >= num_steps) return 0.0;
+    const double t = timestep(j);
+    const int lo = (int)floor(t), hi = (int)ceil(t);
+    const double fr = t - floor(t);
+    auto train = [&](int k) { const double a = abar[k]; return sqrt((1.0 - a) / a); };
+    return (1.0 - fr) * train(lo) + fr * train(hi);
+  };
+  out->t = timestep(i);
+  out->sigma = sigma_at(i);
+  out->sigma_next = sigma_at(i + 1);
+  out->order = std::min(i + 1, 4);
+  const double h = out->sigma_next - out->sigma;
+  double r[4];
+  for (int j = 0; j < out->order; ++j) r[j] = sigma_at(i - j) - out->sigma;
+  for (int k = 0; k < 4; ++k) out->c[k] = 0.0;
+  for (int k = 0; k < out->order; ++k) {
+    double p[4] = {1.0, 0.0, 0.0, 0.0};    // prod_{j != k} (u - r_j), ascending powers of u
+    int deg = 0;
+    double den = 1.0;
+    for (int j = 0; j < out->order; ++j) {
+      if (j == k) continue;
+      for (int m = ++deg; m > 0; --m) p[m] = p[m - 1] - r[j] * p[m];
+      p[0] = -r[j] * p[0];
+      den *= r[k] - r[j];
+    }
+    double integral = 0.0;
+    for (int m = deg; m >= 0; --m) integral = integral * h + p[m] / (m + 1);   // sum_m p_m h^m / (m + 1)
+    out->c[k] = integral * h / den;
+  }
+}
+
 static WeightStore* store_of(svg_ctx* ctx, int model, bool create) {
   switch (model) {
     case SVG_TRANSFORMER: if (!ctx->xf && create) ctx->xf = new XfModel(); return ctx->xf ? &ctx->xf->ws : nullptr;
@@ -137,11 +205,13 @@ int svg_ddim_loop(svg_ctx* ctx, float* z, int N, int h, int w, const float* text
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }
-static_assert(SVG_SAMPLER_DDIM == kSamplerDdim && SVG_SAMPLER_DPMPP_2M == kSamplerDpmpp2m, "sampler ids of svg_hip.h and models.h");
+static_assert(SVG_SAMPLER_DDIM == kSamplerDdim && SVG_SAMPLER_DPMPP_2M == kSamplerDpmpp2m && SVG_SAMPLER_LMS == kSamplerLms,
+              "sampler ids of svg_hip.h and models.h");
 int svg_sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, int w, const float* text_emb, int ctx_len, int num_steps,
                     int start_step, float guidance, const float* noise, float* hist, void* stream) {
   try {
-    SVG_CHECK(sampler == SVG_SAMPLER_DDIM || sampler == SVG_SAMPLER_DPMPP_2M, "svg_sample_loop: unknown sampler %d", sampler);
+    SVG_CHECK(sampler == SVG_SAMPLER_DDIM || sampler == SVG_SAMPLER_DPMPP_2M || sampler == SVG_SAMPLER_LMS,
+              "svg_sample_loop: unknown sampler %d", sampler);
     SVG_CHECK(ctx && ctx->unet, "unet: model not configured");
     xf_walk_check(ctx, false);                       // an earlier layer-walking forward that gave up: walk off + logged; raised to the Transformer's caller
     ctx->unet->sample_loop(ctx, sampler, z, N, h, w, text_emb, ctx_len, num_steps, start_step, guidance, noise, hist, (hipStream_t)stream);
@@ -157,6 +227,29 @@ int svg_dpmpp_step(svg_ctx* ctx, const float* x, const float* eps, const float* 
     float row[kDpmRow];
     ctx->unet->dpmpp_coefs(t, t_next, m_prev ? t_last : -1, row);
     dpmpp_step(x, eps, nullptr, 0.f, m_prev, x_out, m_out, n, row, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+int svg_lms_coefs(int num_steps, int i, double* timestep, double* sigma, double* sigma_next, int* order, double* coefs) {
+  try {
+    LmsCoef lc;
+    lms_coefs(num_steps, i, &lc);
+    if (timestep) *timestep = lc.t;
+    if (sigma) *sigma = lc.sigma;
+    if (sigma_next) *sigma_next = lc.sigma_next;
+    if (order) *order = lc.order;
+    if (coefs) for (int k = 0; k < 4; ++k) coefs[k] = lc.c[k];
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(nullptr, e); }
+}
+int svg_lms_step(svg_ctx* ctx, const float* x, const float* eps, float* dhist, float* x_out, int64_t n, int num_steps, int i, void* stream) {
+  try {
+    SVG_CHECK(ctx, "null context");
+    SVG_CHECK(x && eps && dhist && x_out && n >= 0, "svg_lms_step: null tensor or negative size");
+    LmsCoef lc;
+    lms_coefs(num_steps, i, &lc);
+    const float c[4] = {(float)lc.c[0], (float)lc.c[1], (float)lc.c[2], (float)lc.c[3]};
+    lms_step(x, eps, nullptr, 0.f, dhist, x_out, n, i, lc.order, c, (hipStream_t)stream);
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }

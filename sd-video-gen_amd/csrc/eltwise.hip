@@ -259,6 +259,62 @@ __global__ void dpmpp_step_tab_kernel(const float* x, const float* __restrict__ 
   const bool last = r[6] != 0.f;
   GRID_STRIDE(i, n) dpmpp_elem(x, eu, ec, guidance, mp, xo, mo, i, inv_a, sig, cx, cd, k, last);
 }
+// LMS (diffusers 0.2.3 LMSDiscreteScheduler.step, order <= 4) with the CFG combine in front.  The derivative of step i is the
+// combined eps itself ((x - (x - sigma eps)) / sigma up to f32 rounding); it goes to slot i & 3 of the ring dh (4 x n floats), the
+// up to three older ones come from the slots (i-1) & 3 ... (i-3) & 3, never the slot written:  x' = x + sum_k c_k d_{i-k}, k < order.
+// W = 4: one 16-byte access per operand, W = 1: the scalar tail.  x / x_out may alias (read before written by the same thread).
+// Every product is an explicit fmaf, so that the tabled, the direct, the 16-byte and the scalar form round alike.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+template <int W> struct LmsVec { typedef float T; };
+template <> struct LmsVec<4> { typedef f32x4 T; };
+template <int W>
+__device__ __forceinline__ void lms_elem(const float* x, const float* __restrict__ eu, const float* __restrict__ ec, float guidance, float* dh,
+                                         float* xo, int64_t n, int64_t i, int slot, int order, float c0, float c1, float c2, float c3) {
+  typedef typename LmsVec<W>::T V;
+  const V xv = *(const V*)(x + i);
+  V e = *(const V*)(eu + i);
+  if (ec) e = __builtin_elementwise_fma(V(guidance), *(const V*)(ec + i) - e, e);
+  *(V*)(dh + (int64_t)slot * n + i) = e;
+  V acc = V(c0) * e;
+  if (order > 1) acc = __builtin_elementwise_fma(V(c1), *(const V*)(dh + (int64_t)((slot + 3) & 3) * n + i), acc);
+  if (order > 2) acc = __builtin_elementwise_fma(V(c2), *(const V*)(dh + (int64_t)((slot + 2) & 3) * n + i), acc);
+  if (order > 3) acc = __builtin_elementwise_fma(V(c3), *(const V*)(dh + (int64_t)((slot + 1) & 3) * n + i), acc);
+  *(V*)(xo + i) = xv + acc;
+}
+// nv: the number of 4-float groups taken with 16-byte accesses (0 when n % 4 or a pointer forbids them); the rest is the scalar tail
+__global__ void lms_step_kernel(const float* x, const float* __restrict__ eu, const float* __restrict__ ec, float guidance, float* dh, float* xo,
+                                int64_t n, int64_t nv, int slot, int order, float c0, float c1, float c2, float c3) {
+  GRID_STRIDE(v, nv) lms_elem<4>(x, eu, ec, guidance, dh, xo, n, 4 * v, slot, order, c0, c1, c2, c3);
+  GRID_STRIDE(j, n - 4 * nv) lms_elem<1>(x, eu, ec, guidance, dh, xo, n, 4 * nv + j, slot, order, c0, c1, c2, c3);
+}
+// the same step with its row read from a device table through the loop's step counter: tab[i] = kLmsRow floats
+// {t, 1/sqrt(sigma_i^2 + 1), order, i, c0, c1, c2, c3}; the ring slot follows from i, so a replayed graph needs no new arguments
+__global__ void lms_step_tab_kernel(const float* x, const float* __restrict__ eu, const float* __restrict__ ec, float guidance, float* dh,
+                                    float* xo, int64_t n, int64_t nv, const float* __restrict__ tab, const int* __restrict__ idx) {
+  const float* r = tab + kLmsRow * idx[0];
+  const int order = (int)r[2], slot = (int)r[3] & 3;
+  const float c0 = r[4], c1 = r[5], c2 = r[6], c3 = r[7];
+  GRID_STRIDE(v, nv) lms_elem<4>(x, eu, ec, guidance, dh, xo, n, 4 * v, slot, order, c0, c1, c2, c3);
+  GRID_STRIDE(j, n - 4 * nv) lms_elem<1>(x, eu, ec, guidance, dh, xo, n, 4 * nv + j, slot, order, c0, c1, c2, c3);
+}
+// the UNet input of an LMS step: o0 (and o1, the second half of a guided batch) <- x * c, c = 1 / sqrt(sigma_i^2 + 1)
+template <int W>
+__device__ __forceinline__ void lms_input_elem(const float* x, float* o0, float* o1, int64_t i, float c) {
+  typedef typename LmsVec<W>::T V;
+  const V v = *(const V*)(x + i) * V(c);
+  *(V*)(o0 + i) = v;
+  if (o1) *(V*)(o1 + i) = v;
+}
+__global__ void lms_input_kernel(const float* x, float* o0, float* o1, int64_t n, int64_t nv, float c) {
+  GRID_STRIDE(v, nv) lms_input_elem<4>(x, o0, o1, 4 * v, c);
+  GRID_STRIDE(j, n - 4 * nv) lms_input_elem<1>(x, o0, o1, 4 * nv + j, c);
+}
+__global__ void lms_input_tab_kernel(const float* x, float* o0, float* o1, int64_t n, int64_t nv, const float* __restrict__ tab,
+                                     const int* __restrict__ idx) {
+  const float c = tab[kLmsRow * idx[0] + 1];
+  GRID_STRIDE(v, nv) lms_input_elem<4>(x, o0, o1, 4 * v, c);
+  GRID_STRIDE(j, n - 4 * nv) lms_input_elem<1>(x, o0, o1, 4 * nv + j, c);
+}
 __global__ void ddim_bump_kernel(int* __restrict__ idx) { idx[0] += 1; }
 __global__ void add_noise_kernel(const float* __restrict__ x0, const float* __restrict__ nz, float* __restrict__ out, int64_t n, float sa, float s1a) {
   GRID_STRIDE(i, n) out[i] = sa * x0[i] + s1a * nz[i];
@@ -379,6 +435,41 @@ void dpmpp_step_tab(const float* x, const float* eu, const float* ec, float guid
                     const int* idx, hipStream_t s) {
   hipLaunchKernelGGL(dpmpp_step_tab_kernel, grid_for(n), dim3(256), 0, s, x, eu, ec, guidance, m, x_out, m, n, tab, idx);
   check_launch("dpmpp_step_tab");
+}
+namespace {
+// 4-float groups an LMS kernel may take with 16-byte accesses: all of them when every pointer it indexes is 16-byte aligned
+// (`stride4`: the kernel also indexes p + k * n, so n % 4 must be 0 too), else none
+inline int64_t lms_groups(int64_t n, bool stride4, std::initializer_list<const void*> ptrs) {
+  if (stride4 && n % 4 != 0) return 0;
+  for (const void* p : ptrs)
+    if ((uintptr_t)p & 15) return 0;
+  return n / 4;
+}
+inline dim3 lms_grid(int64_t n, int64_t nv) { return grid_for(std::max<int64_t>(nv, n - 4 * nv)); }
+}  // namespace
+void lms_input(const float* x, float* o0, float* o1, int64_t n, float c, hipStream_t s) {
+  const int64_t nv = lms_groups(n, false, {x, o0, o1});
+  hipLaunchKernelGGL(lms_input_kernel, lms_grid(n, nv), dim3(256), 0, s, x, o0, o1, n, nv, c);
+  check_launch("lms_input");
+}
+void lms_input_tab(const float* x, float* o0, float* o1, int64_t n, const float* tab, const int* idx, hipStream_t s) {
+  const int64_t nv = lms_groups(n, false, {x, o0, o1});
+  hipLaunchKernelGGL(lms_input_tab_kernel, lms_grid(n, nv), dim3(256), 0, s, x, o0, o1, n, nv, tab, idx);
+  check_launch("lms_input_tab");
+}
+void lms_step(const float* x, const float* eu, const float* ec, float guidance, float* dhist, float* x_out, int64_t n, int i, int order,
+              const float* c, hipStream_t s) {
+  SVG_CHECK(i >= 0 && order >= 1 && order <= 4 && order <= i + 1, "lms_step: order %d at step %d", order, i);
+  const int64_t nv = lms_groups(n, true, {x, eu, ec, dhist, x_out});
+  hipLaunchKernelGGL(lms_step_kernel, lms_grid(n, nv), dim3(256), 0, s, x, eu, ec, guidance, dhist, x_out, n, nv, i & 3, order, c[0], c[1],
+                     c[2], c[3]);
+  check_launch("lms_step");
+}
+void lms_step_tab(const float* x, const float* eu, const float* ec, float guidance, float* dhist, float* x_out, int64_t n, const float* tab,
+                  const int* idx, hipStream_t s) {
+  const int64_t nv = lms_groups(n, true, {x, eu, ec, dhist, x_out});
+  hipLaunchKernelGGL(lms_step_tab_kernel, lms_grid(n, nv), dim3(256), 0, s, x, eu, ec, guidance, dhist, x_out, n, nv, tab, idx);
+  check_launch("lms_step_tab");
 }
 void ddim_bump(int* idx, hipStream_t s) {
   hipLaunchKernelGGL(ddim_bump_kernel, dim3(1), dim3(1), 0, s, idx);

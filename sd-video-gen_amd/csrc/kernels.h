@@ -287,6 +287,19 @@ void dpmpp_step(const float* x, const float* eps_u, const float* eps_c, float gu
 // the step with its row read from row idx[0] of a device table (the DDIM loop's counter); m: m_prev in, m out
 void dpmpp_step_tab(const float* x, const float* eps_u, const float* eps_c, float guidance, float* m, float* x_out, int64_t n,
                     const float* tab, const int* idx, hipStream_t s);
+// LMS (order <= 4): one table row of kLmsRow floats {t, 1/sqrt(sigma_i^2 + 1), order, i, c0, c1, c2, c3}
+constexpr int kLmsRow = 8;
+// the UNet input of an LMS step: o0 (and o1 unless null) <- x * c; x / o0 may be the same buffer
+void lms_input(const float* x, float* o0, float* o1, int64_t n, float c, hipStream_t s);
+// the same with c = 1/sqrt(sigma^2 + 1) read from row idx[0] of a device table
+void lms_input_tab(const float* x, float* o0, float* o1, int64_t n, const float* tab, const int* idx, hipStream_t s);
+// x_out <- x + sum_{k < order} c[k] d_{i-k}, d_i = the CFG-combined eps (eps_c null: eps_u), stored to slot i & 3 of the ring
+// dhist (4 x n floats); the older derivatives are read from the slots (i-1) & 3 ...; x / x_out may be the same buffer
+void lms_step(const float* x, const float* eps_u, const float* eps_c, float guidance, float* dhist, float* x_out, int64_t n, int i, int order,
+              const float* c, hipStream_t s);
+// the step with i, order and c read from row idx[0] of a device table (the DDIM loop's counter)
+void lms_step_tab(const float* x, const float* eps_u, const float* eps_c, float guidance, float* dhist, float* x_out, int64_t n,
+                  const float* tab, const int* idx, hipStream_t s);
 void add_noise(const float* x0, const float* noise, float* out, int64_t n, float sa, float s1a, hipStream_t s);
 void fill_f32(float* p, int64_t n, float v, hipStream_t s);
 

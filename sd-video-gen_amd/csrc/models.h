@@ -142,7 +142,15 @@ struct UnetIface {
   virtual void dpmpp_coefs(int t, int t_next, int t_last, float* row) const = 0;
 };
 // sampler ids of svg_sample_loop (SVG_SAMPLER_* of include/svg_hip.h)
-enum { kSamplerDdim = 0, kSamplerDpmpp2m = 1 };
+enum { kSamplerDdim = 0, kSamplerDpmpp2m = 1, kSamplerLms = 2 };
+// The f32 alphas_cumprod of the scaled-linear schedule (0.00085 .. 0.012, 1000 train steps) as diffusers builds it: one table for
+// the DDIM / DPM++ coefficients of the UNet and for the LMS sigmas (host only, no device call).
+const std::vector<float>& sd_alphas_cumprod();
+// Step i of an n-step LMS schedule (diffusers 0.2.3 LMSDiscreteScheduler): timestep linspace(999, 0, n)[i], sigma_i and sigma_{i+1}
+// interpolated between the train sigmas sqrt((1 - abar) / abar) (sigma_n = 0), order min(i + 1, 4), and the integrals over
+// [sigma_i, sigma_{i+1}] of the Lagrange basis on sigma_i ... sigma_{i-order+1}, exact in double (c[k] = 0 for k >= order).
+struct LmsCoef { double t, sigma, sigma_next; int order; double c[4]; };
+void lms_coefs(int num_steps, int i, LmsCoef* out);
 VaeIface* new_vae_bf16();
 VaeIface* new_vae_f16();
 UnetIface* new_unet_bf16();
@@ -234,7 +242,7 @@ struct UnetModel : UnetIface {
   ResW mid0, mid1; XfBlockW mid_attn;
   std::vector<std::vector<ResW>> up_res; std::vector<std::vector<XfBlockW>> up_attn; std::vector<ConvW> up_s;
   // DDIM tables (scaled_linear 0.00085..0.012, 1000 train steps)
-  std::vector<float> alphas_cumprod;
+  std::vector<float> alphas_cumprod;   // = sd_alphas_cumprod()
   void configure(const char* kv) override;
   void finalize(svg_ctx* ctx, int64_t* n_params) override;
   // one UNet call (planned by the caller); cache: cross-attention K / V^T reuse across the steps of a DDIM loop

@@ -261,22 +261,7 @@ void UnetModel::finalize(svg_ctx* ctx, int64_t* n_params) {
   norm_out = load_norm(ctx, ws, "conv_norm_out", c0);
   conv_out = load_conv3x3(ctx, ws, "conv_out", c0, out_ch, s);
   temb_all = load_stacked(ctx, ws, tc.prefixes, tc.couts, temb_dim, true, s);
-  // ---- DDIM table, as diffusers' DDIMScheduler builds it: betas = linspace(sqrt(b0), sqrt(b1), 1000, f32)**2,
-  // alphas_cumprod = cumprod(1 - betas) in f32
-  alphas_cumprod.resize(1000);
-  {
-    const double b0 = sqrt(0.00085), b1 = sqrt(0.012);
-    float prod = 1.f;
-    for (int i = 0; i < 1000; ++i) {
-      const double step = (b1 - b0) / 999.0;
-      float sb = (float)(i * step + b0);
-      if (i == 999) sb = (float)b1;
-      float beta = sb * sb;
-      float alpha = 1.f - beta;
-      prod = prod * alpha;
-      alphas_cumprod[i] = prod;
-    }
-  }
+  alphas_cumprod = sd_alphas_cumprod();
   if (n_params) *n_params = total;
   ready = true;
 }
@@ -689,14 +674,24 @@ void UnetModel::ddim_loop(svg_ctx* ctx, float* z, int N, int h, int w, const flo
 
 // The img2img loop of either sampler: the same timesteps, add_noise, CFG combine, K / V^T cache, fp8 placement and step graph; only
 // the update kernel and its table differ.  DPM++(2M) keeps the previous step's x0 prediction in `mprev` (one latent-sized buffer).
+// LMS (the reference's text-to-image sampler, denoise_img_latents) shares the loop but not the schedule: timesteps linspace(999, 0, n),
+// z = unit-normal draws scaled by sigma_0 on entry, the UNet input is z / sqrt(sigma_i^2 + 1) (lms_input, in place of the guided
+// path's two copies), and the last four derivatives live in the ring `dhist`.  It always starts at step 0 and ignores `noise`.
 void UnetModel::sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, int w, const float* text_emb, int ctx_len, int num_steps,
                             int start_step, float guidance, const float* noise, float* hist, hipStream_t s) {
   SVG_CHECK(ready, "unet: svg_finalize has not been called");
-  SVG_CHECK(sampler == kSamplerDdim || sampler == kSamplerDpmpp2m, "sample_loop: unknown sampler %d", sampler);
-  const bool dpm = sampler == kSamplerDpmpp2m;
-  const int row = dpm ? kDpmRow : 5;      // floats per table row
+  SVG_CHECK(sampler == kSamplerDdim || sampler == kSamplerDpmpp2m || sampler == kSamplerLms, "sample_loop: unknown sampler %d", sampler);
+  const bool dpm = sampler == kSamplerDpmpp2m, lms = sampler == kSamplerLms;
+  const int row = lms ? kLmsRow : dpm ? kDpmRow : 5;      // floats per table row
   SVG_CHECK(num_steps >= 1 && num_steps <= 1000 && start_step >= 0 && start_step <= num_steps, "ddim: bad steps %d/%d", start_step, num_steps);
+  SVG_CHECK(!lms || start_step == 0, "lms: start_step must be 0 (got %d): the multistep rule has no history to start from", start_step);
   SVG_CHECK(start_step == 0 || noise, "ddim: start_step > 0 needs the add_noise draws");
+  std::vector<LmsCoef> lc(lms ? num_steps : 0);
+  for (int i = 0; i < (int)lc.size(); ++i) lms_coefs(num_steps, i, &lc[i]);
+  auto lms_row = [&](int i, float* r) {    // {t, 1/sqrt(sigma^2 + 1), order, i, c0..c3}
+    r[0] = (float)lc[i].t; r[1] = (float)(1.0 / sqrt(lc[i].sigma * lc[i].sigma + 1.0)); r[2] = (float)lc[i].order; r[3] = (float)i;
+    for (int k = 0; k < 4; ++k) r[4 + k] = (float)lc[i].c[k];
+  };
   const int ratio = 1000 / num_steps;
   const int64_t n = (int64_t)N * in_ch * h * w;
   const bool cfg = guidance != 0.f;
@@ -719,22 +714,26 @@ void UnetModel::sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, i
   auto body = [&]() {
     kv.valid = false;   // the context is constant over the loop: K / V^T of the cross-attentions are computed once
     float* tvec = ctx->arena.get<float>(NB);
-    float* zin = cfg ? ctx->arena.get<float>(2 * n) : nullptr;
+    float* zin = (cfg || lms) ? ctx->arena.get<float>((cfg ? 2 : 1) * n) : nullptr;   // LMS: the scaled input, never z itself
     float* eps = ctx->arena.get<float>((int64_t)NB * n / N);
     float* tab = ctx->arena.get<float>((int64_t)row * num_steps);
     int* idx = ctx->arena.get<int>(1);
     float* mprev = dpm ? ctx->arena.get<float>(n) : nullptr;   // DPM++: the previous step's x0 prediction
+    float* dhist = lms ? ctx->arena.get<float>(4 * n) : nullptr;   // LMS: the ring of the last four derivatives
     if (SVG_LAUNCHING(ctx)) {
       if (start_step > 0 && start_step < num_steps) {
         const float a = alphas_cumprod[timestep_at(start_step)];
         add_noise(z, noise, z, n, sqrtf(a), sqrtf(1.f - a), s);
       }
+      if (lms) lms_input(z, z, nullptr, n, (float)lc[0].sigma, s);   // x <- sigma_0 x
       if (hist) HIP_OK(hipMemcpyAsync(hist, z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
       if (use_graph) {
         std::vector<float> h((size_t)row * num_steps);
         for (int i = 0; i < num_steps; ++i) {
           const int t = timestep_at(i);
-          if (dpm) {
+          if (lms) {
+            lms_row(i, &h[(size_t)row * i]);
+          } else if (dpm) {
             dpmpp_coefs(t, t - ratio, i > start_step ? timestep_at(i - 1) : -1, &h[(size_t)row * i]);
           } else {
             h[5 * i] = (float)t;
@@ -753,8 +752,12 @@ void UnetModel::sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, i
       ctx->arena.push();
       if (SVG_LAUNCHING(ctx)) {
         if (tabled) ddim_tvec(tvec, NB, tab, idx, s, row);
-        else fill_f32(tvec, NB, (float)t, s);
-        if (cfg) {
+        else fill_f32(tvec, NB, lms ? (float)lc[i].t : (float)t, s);
+        if (lms) {
+          float r[kLmsRow];
+          if (tabled) lms_input_tab(z, zin, cfg ? zin + n : nullptr, n, tab, idx, s);
+          else { lms_row(i, r); lms_input(z, zin, cfg ? zin + n : nullptr, n, r[1], s); }
+        } else if (cfg) {
           HIP_OK(hipMemcpyAsync(zin, z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
           HIP_OK(hipMemcpyAsync(zin + n, z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
         }
@@ -762,12 +765,19 @@ void UnetModel::sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, i
       // guidance == 0: noise_pred = uncond + 0*(text - uncond) == uncond — only the uncond half is needed
       std::unique_ptr<ProfScope> step_scope;
       if (SVG_LAUNCHING(ctx)) step_scope.reset(new ProfScope(ctx, PK_UNET_STEP, s, 0, 0));
-      run(ctx, cfg ? zin : z, NB, h, w, tvec, text_emb, ctx_len, eps, s, &kv, sites);
+      run(ctx, (cfg || lms) ? zin : z, NB, h, w, tvec, text_emb, ctx_len, eps, s, &kv, sites);
       if (SVG_LAUNCHING(ctx)) {
         if (tabled) {
-          if (dpm) dpmpp_step_tab(z, eps, cfg ? eps + n : nullptr, guidance, mprev, z, n, tab, idx, s);
+          if (lms) lms_step_tab(z, eps, cfg ? eps + n : nullptr, guidance, dhist, z, n, tab, idx, s);
+          else if (dpm) dpmpp_step_tab(z, eps, cfg ? eps + n : nullptr, guidance, mprev, z, n, tab, idx, s);
           else ddim_step_tab(z, eps, cfg ? eps + n : nullptr, guidance, z, n, tab, idx, s);
           ddim_bump(idx, s);
+        } else if (lms) {
+          float r[kLmsRow];
+          lms_row(i, r);
+          ProfScope ps(ctx, PK_ELT, s, 0, 0);
+          lms_step(z, eps, cfg ? eps + n : nullptr, guidance, dhist, z, n, i, lc[i].order, r + 4, s);
+          if (hist) HIP_OK(hipMemcpyAsync(hist + (int64_t)(i - start_step + 1) * n, z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
         } else if (dpm) {
           float r[kDpmRow];
           dpmpp_coefs(t, t - ratio, i > start_step ? timestep_at(i - 1) : -1, r);

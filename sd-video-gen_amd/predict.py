@@ -59,7 +59,8 @@ def sample_clips(model, sd_utils, clips_u8, pred_frames, denoise=False, start_st
     Returns all_latents (C, 4+N, D_lat) f32 [and the decoded frames (C,4+N,F,F,3) uint8].
     """
     ctx = sd_utils.vae.ctx                      # (checked: the context's slots still hold this SDUtils' networks)
-    _lib.sampler_id(sampler)
+    if _lib.sampler_id(sampler) == _lib.SAMPLERS["lms"]:
+        raise ValueError("sample_clips has no LMS sampler (img2img from start_step; LMS starts from noise): see SDUtils.denoise_img_latents")
     if denoise:
         assert sd_utils.unet is not None and sd_utils.unet.ctx is ctx, "sample_clips(denoise=True) needs SDUtils built with --denoise"
     if not _planning:

@@ -400,15 +400,23 @@ class SDUtils():
 
     # ---- sd_utils.py:97-126 ----------------------------------------------------------------------------
     def denoise_img_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5, latents=None,
-                            start_step=None):
+                            start_step=None, in_library=None):
         """text-conditioned LMS sampling from noise (the reference's text-to-image path): UNet calls at batch 2N in the library,
-        the classifier-free-guidance combine and the multistep update on the (N,4,h,w) latents as device tensor arithmetic."""
+        the classifier-free-guidance combine and the multistep update on the (N,4,h,w) latents as device tensor arithmetic.
+        ``in_library``: True runs the whole loop in the library (Context.sample_loop(sampler="lms"): the sigma scaling, the guidance
+        combine and the update as HIP kernels on closed-form coefficients, the step captured as a graph); False is the host loop
+        below; None (default) reads $SVG_LMS_LOOP at each call (unset / 0: the host loop)."""
         if self.unet is None:
             raise RuntimeError("denoise_img_latents needs the UNet: construct SDUtils with --denoise")
         if latents is None:
             latents = torch.randn((text_embeddings.shape[0] // 2, self.unet.in_channels, height // 8, width // 8))
         latents = latents.to(self.device).float()
         text_embeddings = text_embeddings.to(self.device)
+        if in_library is None:
+            in_library = bool(int(os.environ.get("SVG_LMS_LOOP", "0") or 0))
+        if in_library:
+            return self.unet.ctx.sample_loop(latents, text_embeddings, sampler="lms", num_steps=num_inference_steps,
+                                             guidance=guidance_scale)
         self.scheduler.set_timesteps(num_inference_steps)
         latents = latents * float(self.scheduler.sigmas[0])
         with torch.no_grad():
@@ -423,12 +431,13 @@ class SDUtils():
         return latents
 
     # ---- sd_utils.py:171-189 ---------------------------------------------------------------------------
-    def prompt_to_img(self, prompts, height=512, width=512, num_inference_steps=50, guidance_scale=7.5, latents=None):
+    def prompt_to_img(self, prompts, height=512, width=512, num_inference_steps=50, guidance_scale=7.5, latents=None, in_library=None):
+        """``in_library``: as in denoise_img_latents"""
         if isinstance(prompts, str):
             prompts = [prompts]
         text_embeds = self.encode_text(prompts)
         latents = self.denoise_img_latents(text_embeds, height=height, width=width, latents=latents,
-                                           num_inference_steps=num_inference_steps, guidance_scale=guidance_scale)
+                                           num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, in_library=in_library)
         return self.decode_img_latents(latents)
 
     # ---- sd_utils.py:128-154 ---------------------------------------------------------------------------
@@ -465,6 +474,8 @@ class SDUtils():
     def gen_i2i_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5,
                         latents=None, return_all_latents=False, start_step=10, noise=None, sampler="ddim"):
         """`sampler`: "ddim" (the reference's DDIMScheduler) or "dpmpp_2m" (DPM-Solver++(2M) on the same timesteps)"""
+        if sampler == "lms":
+            raise ValueError("gen_i2i_latents has no LMS sampler (the LMS rule starts from noise at step 0): use denoise_img_latents")
         _lib.sampler_id(sampler)
         if self.unet is None:
             raise RuntimeError("gen_i2i_latents needs the UNet: construct SDUtils with --denoise")
