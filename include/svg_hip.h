@@ -351,8 +351,23 @@ typedef struct svg_gemm_desc {
   uint16_t* vt_out;
   int vt_n0, vt_rows, vt_ld;
   int64_t vt_bs;
+  /* appended (the offsets above stay put); all zero = none of it */
+  const uint16_t* A2;       /* dense two-source A = [A | A2]: K columns >= k_split (a multiple of 64) come from A2, row stride lda2; tiled igemm only */
+  int lda2, k_split;
+  float* gn_part;           /* GroupNorm column sums the tile epilogue leaves: gn_part[(tile_m * N + n) * 2 + {0,1}] = sum, sum of squares of the
+                             * STORED values of column n over the rows of row tile tile_m (plan[3] rows; conv_halo: one 16 x 16 pixel block,
+                             * tile_m = (b * Ho / 16 + y / 16) * Wo / 16 + x / 16) */
+  float* ln_part;           /* LayerNorm row partials: ln_part[((z * M + m) * ln_tiles + tile_n) * 2 + {0,1}] = the same of row m over the plan[1]
+                             * columns of column tile tile_n; ln_tiles must be plan[4] */
+  int ln_tiles;
 } svg_gemm_desc;
 int svg_op_gemm_ex(svg_ctx* ctx, const svg_gemm_desc* desc, int* path, void* stream);
+/* What svg_op_gemm_ex would launch for desc, without launching: plan[5] = {kernel family, column tile, split-K, gn_rows (rows per GroupNorm
+ * row tile, 0: the launch cannot emit gn_part), ln_tiles (LayerNorm column tiles, 0: it cannot emit ln_part)}.  The models ask the same
+ * question before every launch that emits: plan, fill gn_part / ln_part / ln_tiles from the answer, launch.  gn_part / ln_part set where the
+ * plan has 0 (split-K, batch > 1 for gn_part, out_f32 = 1, GEGLU, a conv with ln_part ...) or an ln_tiles other than the plan's make
+ * svg_op_gemm_ex return an error without launching anything. */
+int svg_op_gemm_plan(svg_ctx* ctx, const svg_gemm_desc* desc, int* plan);
 /* Fused GEGLU feed-forward of a BasicTransformerBlock (C = 320): out = ff.net.2(GEGLU(ff.net.0(LayerNorm(x)))) + residual in ONE
  * kernel (the M x 4C intermediate never reaches HBM).  x, residual, out: (M,C) bf16; w1 (8C,C) = [h; gate], b1 (8C), w2 (C,4C),
  * b2 (C), LayerNorm gamma / beta (C): f32 in the state_dict layout (folded and packed inside: test hook). */
@@ -490,6 +505,7 @@ int svg_op_conv3x3_gn_f16(svg_ctx* ctx, const uint16_t* x, const float* w_oihw, 
 int svg_op_gemm_lnstats_f16(svg_ctx* ctx, const uint16_t* A, const uint16_t* W, const float* bias, const uint16_t* residual,
                             uint16_t* C, int M, int N, int K, int batch, float* rs, float* rm, int* used, void* stream);
 int svg_op_gemm_ex_f16(svg_ctx* ctx, const svg_gemm_desc* desc, int* path, void* stream);
+int svg_op_gemm_plan_f16(svg_ctx* ctx, const svg_gemm_desc* desc, int* plan);
 int svg_op_gemm_cat_f16(svg_ctx* ctx, const uint16_t* A, const uint16_t* A2, const uint16_t* W, const float* bias, uint16_t* C,
                         int M, int N, int K, int k_split, void* stream);
 int svg_op_ff_fused_f16(svg_ctx* ctx, const uint16_t* x, const float* ln_gamma, const float* ln_beta, const float* w1,

@@ -48,7 +48,8 @@ class GemmDesc(C.Structure):
                 ("bias_bn", _vp), ("rows_per_batch", _i), ("bias_bn_ld", _i),
                 ("residual", _vp), ("ldr", _i), ("act", _i), ("out_f32", _i),
                 ("ln_rs", _vp), ("ln_rm", _vp), ("ln_s", _vp), ("ln_swapped", _i), ("ln_zstride", _i64),
-                ("vt_out", _vp), ("vt_n0", _i), ("vt_rows", _i), ("vt_ld", _i), ("vt_bs", _i64)]
+                ("vt_out", _vp), ("vt_n0", _i), ("vt_rows", _i), ("vt_ld", _i), ("vt_bs", _i64),
+                ("A2", _vp), ("lda2", _i), ("k_split", _i), ("gn_part", _vp), ("ln_part", _vp), ("ln_tiles", _i)]
 
 
 class AttnDesc(C.Structure):
@@ -108,6 +109,7 @@ SIGNATURES = {
     "svg_op_gemm_lnstats": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, C.POINTER(_i), _vp],
     "svg_op_gemm_cat": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "svg_op_gemm_ex": [_vp, C.POINTER(GemmDesc), C.POINTER(_i), _vp],
+    "svg_op_gemm_plan": [_vp, C.POINTER(GemmDesc), C.POINTER(_i)],
     "svg_op_ff_fused": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "svg_op_xattn_fused": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp],
     "svg_op_dropout_mask": [_vp, C.c_uint64, _i, _f, _vp, _i64, _vp],
@@ -144,7 +146,7 @@ SIGNATURES = {
     "svg_debug_captures_active": [],
 }
 # fp16-storage twins of the 16-bit operator hooks (svg_op_<name>_f16: same arguments)
-for _n in ("gemm", "gemm_ex", "conv3x3", "conv3x3_gn", "conv3x3_mx", "gemm_lnstats", "gemm_cat", "ff_fused", "xattn_fused", "quant_mx", "gemm_fp8", "groupnorm", "layernorm",
+for _n in ("gemm", "gemm_ex", "gemm_plan", "conv3x3", "conv3x3_gn", "conv3x3_mx", "gemm_lnstats", "gemm_cat", "ff_fused", "xattn_fused", "quant_mx", "gemm_fp8", "groupnorm", "layernorm",
            "attention", "attention_ex", "vae_attention", "conv3x3_f32s", "groupnorm_f32", "groupnorm_ex", "groupnorm_mx", "gn_fold_weights", "ln_stats",
            "softmax_rows", "rowsum"):
     SIGNATURES["svg_op_%s_f16" % _n] = SIGNATURES["svg_op_" + _n]

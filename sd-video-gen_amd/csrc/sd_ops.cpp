@@ -178,6 +178,22 @@ int SVG_OP(svg_op_groupnorm_f32)(svg_ctx* ctx, const float* x, const float* gamm
   API_END(ctx)
 }
 
+// svg_gemm_desc -> GemmArgs, field by field (svg_hip.h)
+static GemmArgs gemm_desc_args(const svg_gemm_desc* d) {
+  GemmArgs g;
+  g.amode = d->amode; g.H = d->H; g.W = d->W; g.Cin = d->Cin; g.Ho = d->Ho; g.Wo = d->Wo;
+  g.A = (const h16*)d->A; g.lda = d->lda; g.Wt = (const h16*)d->Wt; g.ldb = d->ldb; g.n_valid = d->n_valid;
+  g.C = d->C; g.ldc = d->ldc; g.M = d->M; g.N = d->N; g.K = d->K; g.batch = d->batch; g.sA = d->sA; g.sB = d->sB; g.sC = d->sC;
+  g.alpha = d->alpha; g.bias = d->bias; g.bias_row = d->bias_row; g.bias_zs = d->bias_zs;
+  g.bias_bn = d->bias_bn; g.rows_per_batch = d->rows_per_batch; g.bias_bn_ld = d->bias_bn_ld;
+  g.residual = (const h16*)d->residual; g.ldr = d->ldr; g.act = d->act; g.out_f32 = d->out_f32;
+  g.ln_rs = d->ln_rs; g.ln_rm = d->ln_rm; g.ln_s = d->ln_s; g.ln_swapped = d->ln_swapped; g.ln_zstride = d->ln_zstride;
+  g.vt_out = (h16*)d->vt_out; g.vt_n0 = d->vt_n0; g.vt_rows = d->vt_rows; g.vt_ld = d->vt_ld; g.vt_bs = d->vt_bs;
+  g.A2 = (const h16*)d->A2; g.lda2 = d->lda2; g.k_split = d->k_split;
+  g.gn_part = d->gn_part; g.ln_part = d->ln_part; g.ln_tiles = d->ln_tiles;
+  return g;
+}
+
 // the whole GEMM epilogue contract on caller buffers (svg_hip.h: svg_gemm_desc): the descriptor goes into GemmArgs field by field and
 // through gemm_auto as the models call it; path = {family, column tile, split-K} of the plan that was launched.  Test hook.
 int SVG_OP(svg_op_gemm_ex)(svg_ctx* ctx, const svg_gemm_desc* d, int* path, void* stream) {
@@ -185,19 +201,20 @@ int SVG_OP(svg_op_gemm_ex)(svg_ctx* ctx, const svg_gemm_desc* d, int* path, void
   SVG_CHECK(d != nullptr, "gemm_ex: no descriptor");
   GemmPlan p;
   run_planned(ctx, [&]() {
-    GemmArgs g;
-    g.amode = d->amode; g.H = d->H; g.W = d->W; g.Cin = d->Cin; g.Ho = d->Ho; g.Wo = d->Wo;
-    g.A = (const h16*)d->A; g.lda = d->lda; g.Wt = (const h16*)d->Wt; g.ldb = d->ldb; g.n_valid = d->n_valid;
-    g.C = d->C; g.ldc = d->ldc; g.M = d->M; g.N = d->N; g.K = d->K; g.batch = d->batch; g.sA = d->sA; g.sB = d->sB; g.sC = d->sC;
-    g.alpha = d->alpha; g.bias = d->bias; g.bias_row = d->bias_row; g.bias_zs = d->bias_zs;
-    g.bias_bn = d->bias_bn; g.rows_per_batch = d->rows_per_batch; g.bias_bn_ld = d->bias_bn_ld;
-    g.residual = (const h16*)d->residual; g.ldr = d->ldr; g.act = d->act; g.out_f32 = d->out_f32;
-    g.ln_rs = d->ln_rs; g.ln_rm = d->ln_rm; g.ln_s = d->ln_s; g.ln_swapped = d->ln_swapped; g.ln_zstride = d->ln_zstride;
-    g.vt_out = (h16*)d->vt_out; g.vt_n0 = d->vt_n0; g.vt_rows = d->vt_rows; g.vt_ld = d->vt_ld; g.vt_bs = d->vt_bs;
+    const GemmArgs g = gemm_desc_args(d);
     p = gemm_plan(g);
     gemm_auto(ctx, g, p, (hipStream_t)stream, g.amode == A_DENSE ? PK_GEMM : PK_CONV3);
   });
   if (path) { path[0] = p.family; path[1] = p.bn; path[2] = p.splitk; }
+  API_END(ctx)
+}
+
+// gemm_plan() of the descriptor: {family, column tile, split-K, gn_rows, ln_tiles}; nothing is launched.  Test hook.
+int SVG_OP(svg_op_gemm_plan)(svg_ctx* ctx, const svg_gemm_desc* d, int* plan) {
+  API_BEGIN
+  SVG_CHECK(d != nullptr && plan != nullptr, "gemm_plan: no descriptor / no result array");
+  const GemmPlan p = gemm_plan(gemm_desc_args(d));
+  plan[0] = p.family; plan[1] = p.bn; plan[2] = p.splitk; plan[3] = p.gn_rows; plan[4] = p.ln_tiles;
   API_END(ctx)
 }
 

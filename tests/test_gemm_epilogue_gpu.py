@@ -70,26 +70,90 @@ def gemm_ex(ctx, **f):
     return rc, tuple(path)
 
 
-class _halo_min:
-    """conv_halo takes a conv only from 192 workgroups on; the kernel does not depend on that count, so the small parity shapes
-    lower the threshold ($SVG_HALO_MIN, re-read through env_refresh) and restore it afterwards"""
+class _knobs:
+    """sets $SVG_* planning knobs the library re-reads through env_refresh, and restores them afterwards"""
 
-    def __init__(self, on):
-        self.on = on
+    def __init__(self, env):
+        self.env = dict(env or {})
 
     def __enter__(self):
-        if self.on:
-            self.old = os.environ.get("SVG_HALO_MIN")
-            os.environ["SVG_HALO_MIN"] = "1"
+        self.old = {k: os.environ.get(k) for k in self.env}
+        os.environ.update(self.env)
+        if self.env:
             _lib.env_refresh()
 
     def __exit__(self, *a):
-        if self.on:
-            if self.old is None:
-                os.environ.pop("SVG_HALO_MIN", None)
+        for k, v in self.old.items():
+            if v is None:
+                os.environ.pop(k, None)
             else:
-                os.environ["SVG_HALO_MIN"] = self.old
+                os.environ[k] = v
+        if self.env:
             _lib.env_refresh()
+
+
+class _halo_min(_knobs):
+    """conv_halo takes a conv only from 192 workgroups on; the kernel does not depend on that count, so the small parity shapes
+    lower the threshold ($SVG_HALO_MIN, re-read through env_refresh) and restore it afterwards"""
+
+    def __init__(self, on, more=None):
+        _knobs.__init__(self, dict({"SVG_HALO_MIN": "1"} if on else {}, **(more or {})))
+
+
+def gemm_plan(ctx, **f):
+    """svg_op_gemm_plan(_f16) of the same descriptor: (status, (family, bn, splitk, gn_rows, ln_tiles)); launches nothing"""
+    d = _lib.GemmDesc()
+    d.alpha = 1.0
+    d.batch = 1
+    d.rows_per_batch = 1
+    for k, v in f.items():
+        setattr(d, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
+    plan = (C.c_int * 5)(-1, -1, -1, -1, -1)
+    rc = getattr(ctx.lib, "svg_op_gemm_plan" + HALF.suffix)(ctx.h, C.byref(d), plan)
+    return rc, tuple(plan)
+
+
+def onehot_rows(tile_of, pos_of, size_of, T, L):
+    """(R, L) 0 / 1 matrix H for the one-hot probes.  Item r sits at position pos_of[r] of tile tile_of[r], which has size_of[r] <= T items.
+    P(v) = {0, v - 1} and both sides of every multiple of 16 below v, in order: the probed positions of a tile of v items.  H[r][k] = 1 iff
+    pos_of[r] is the (k mod |P(v)|)-th of them.  So for every tile and every k < L exactly one item of the tile has H[.][k] = 1, the item
+    moves with k through the first and last position and both sides of every 16-item boundary (every wave's range in all four kernels
+    is a whole number of 16-row / 16-column MFMA tiles), and a short last tile is probed the same way."""
+    def P(v):
+        return sorted({0, v - 1} | {p for k in range(16, v, 16) for p in (k - 1, k)})
+    assert len(P(T)) == L
+    dev = pos_of.device
+    Hm = torch.zeros(pos_of.numel(), L, dtype=torch.bool, device=dev)
+    for v in sorted({int(x) for x in size_of.unique()}):
+        pv = P(v)
+        idx = torch.full((T,), -1, dtype=torch.long, device=dev)
+        idx[torch.tensor(pv, device=dev)] = torch.arange(len(pv), device=dev)
+        sel = size_of == v
+        i = idx[pos_of[sel]]
+        Hm[sel] = (i[:, None] == torch.arange(L, device=dev)[None, :] % len(pv)) & (i[:, None] >= 0)
+    return Hm.to(torch.float64)
+
+
+def onehot_len(T):
+    return 2 + 2 * ((T - 1) // 16)
+
+
+def onehot_val(n):
+    """the hot value of column n: a power of two that moves with the column (exact in both storage types, and so is its square)"""
+    return 2.0 ** ((n % 5) - 2).to(torch.float64)
+
+
+CONV_AMODE = {"S1": 1, "S2P1": 2, "S2A": 3, "UP2": 4, "SMALLC": 5}      # AMode (csrc/kernels.h)
+
+
+def conv_out_hw(H, W, mode):
+    """output image of a 3x3 conv: stride 1 pad 1 (S1, SMALLC: the Cin = 8 form), stride 2 pad 1 (S2P1), stride 2 with right / bottom
+    padding only (S2A: F.pad(x, (0, 1, 0, 1)) then no padding, the downsamplers), nearest-2x upsample then stride 1 pad 1 (UP2)"""
+    if mode == "S2P1":
+        return (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if mode == "S2A":
+        return (H - 2) // 2 + 1, (W - 2) // 2 + 1
+    return (2 * H, 2 * W) if mode == "UP2" else (H, W)
 
 
 def im2col(x, mode):
@@ -97,6 +161,13 @@ def im2col(x, mode):
     if mode == "UP2":
         x = x.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
     B, H, W, Cin = x.shape
+    if mode in ("S2P1", "S2A"):
+        Ho, Wo = conv_out_hw(H, W, mode)
+        lead = 1 if mode == "S2P1" else 0                  # rows / columns of zeros in front; behind: whatever the last window needs
+        xp = torch.nn.functional.pad(x, (0, 0, lead, 2, lead, 2))
+        cols = [xp[:, ky:ky + 2 * Ho:2, kx:kx + 2 * Wo:2, :] for ky in range(3) for kx in range(3)]
+        assert 2 * (Ho - 1) + 2 - lead <= H and 2 * (Wo - 1) + 2 - lead <= W      # (at most one row / column of padding is ever read)
+        return torch.cat(cols, dim=3).reshape(B * Ho * Wo, 9 * Cin)
     xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))
     cols = [xp[:, ky:ky + H, kx:kx + W, :] for ky in range(3) for kx in range(3)]
     return torch.cat(cols, dim=3).reshape(B * H * W, 9 * Cin)
@@ -128,20 +199,30 @@ def _check_gelu(x, y):
 
 def run_case(ctx, path, M, N, K, batch=1, conv=None, data="int", sA="own", sB="own", lda_pad=0, ldb_pad=0, ldc_pad=0, sC_pad=0,
              n_valid=None, alpha=1.0, bias=None, bias_zs=False, bias_bn=None, res_pad=None, act=ACT_NONE, out_f32=0, ln=None,
-             vt=None, halo_min=False):
+             vt=None, halo_min=False, a2=None, a_keep=1, onehot=None, knobs=None, emit=None):
     """builds one problem, runs it, checks the path, the values and the untouched memory.
     conv: (B, H, W, Cin, 'S1' | 'UP2') — A is that NHWC image, Wt packed [N][9][Cin]; bias: None | 'col' | 'row';
     bias_bn: (rows_per_batch, extra row stride or None for bias_bn_ld = 0); res_pad: residual row stride ldr = N + res_pad (None: no
-    residual); ln: None | 'normal' | 'swapped'; vt: (vt_n0, vt_rows, vt_ld_pad) for the fused V^T write."""
+    residual); ln: None | 'normal' | 'swapped'; vt: (vt_n0, vt_rows, vt_ld_pad) for the fused V^T write.
+    conv modes: 'S1' | 'UP2' | 'S2P1' | 'S2A' | 'SMALLC' (conv_out_hw).  a2: (k_split, lda2_pad) — A is given as two tensors, columns
+    >= k_split come from the second (row stride K - k_split + lda2_pad).  a_keep = r: integer A keeps one element in r, the rest zero
+    (bounds the sums of a long K).  onehot: ('gn', rows per row tile) | ('ln', columns per column tile) — operands that leave exactly one
+    power of two per (row tile, column) resp. (row, column tile) in C, see onehot_rows; judged as integer-exact.  knobs: further $SVG_*
+    planning knobs for the launch.  emit: an object with prepare(ctx, desc, launch_env) (asks the plan, adds gn_part / ln_part to the
+    descriptor) and check(ctx, stored C (batch, M, N) f64, integer, relaunch): tests/test_gemm_emit_gpu.py."""
     dev = "cuda"
     g = torch.Generator(device=dev).manual_seed(zlib.crc32(repr((path, M, N, K, batch, conv, data, bias, bias_bn, ln, vt, act)).encode()))
-    integer = data == "int"
+    integer = data == "int" or onehot is not None
     dt = HALF.dtype
     f64 = torch.float64
     nv = N if n_valid is None else n_valid
 
     def ints(shape, lo, hi):
         return torch.randint(lo, hi + 1, shape, generator=g, device=dev).to(f64)
+
+    def a_ints(shape):
+        t = ints(shape, -2, 2)
+        return t if a_keep == 1 else t * (torch.randint(0, a_keep, shape, generator=g, device=dev) == 0)
 
     def randn(shape):
         return torch.randn(shape, generator=g, device=dev, dtype=f64)
@@ -154,19 +235,55 @@ def run_case(ctx, path, M, N, K, batch=1, conv=None, data="int", sA="own", sB="o
     # ---- A: a dense [batch | 1][M][lda] buffer (columns past K hold values that must not be read), or a conv image
     if conv is not None:
         B, H, W, Cin, mode = conv
-        Ho, Wo = (H, W) if mode == "S1" else (2 * H, 2 * W)
-        assert batch == 1 and M == B * Ho * Wo and K == 9 * Cin
-        x = (ints((B, H, W, Cin), -2, 2) if integer else randn((B, H, W, Cin))).to(dt)
+        Ho, Wo = conv_out_hw(H, W, mode)
+        assert batch == 1 and M == B * Ho * Wo and K == 9 * Cin and a2 is None
+        x = (a_ints((B, H, W, Cin)) if integer else randn((B, H, W, Cin))).to(dt)
+        if onehot is not None:
+            # stride 1, centre tap only (the weights below): C[pixel][n] = sum_c x[pixel][c] W[n][4][c].  Row tile of a pixel: its 16 x 16 block
+            # on conv_halo (position 16 ly + lx), 128 consecutive pixels on the tiled kernel
+            assert onehot[0] == "gn" and mode == "S1"
+            T = onehot[1]
+            L = onehot_len(T)
+            m = torch.arange(M, device=dev)
+            if halo_min:
+                py, px = (m % (H * W)) // W, m % W
+                tile_of, pos_of = ((m // (H * W)) * (H // 16) + py // 16) * (W // 16) + px // 16, (py % 16) * 16 + px % 16
+                size_of = torch.full((M,), T, device=dev)
+            else:
+                tile_of, pos_of = m // T, m % T
+                size_of = torch.clamp(M - tile_of * T, max=T)
+            x = torch.zeros(M, Cin, device=dev, dtype=f64)
+            x[:, :L] = onehot_rows(tile_of, pos_of, size_of, T, L)
+            x = x.reshape(B, H, W, Cin).to(dt)
         A_ops = [im2col(x.to(f64), mode)]
-        desc.update(A=x, amode=1 if mode == "S1" else 4, H=H, W=W, Cin=Cin, Ho=Ho, Wo=Wo)
+        desc.update(A=x, amode=CONV_AMODE[mode], H=H, W=W, Cin=Cin, Ho=Ho, Wo=Wo)
         keep = [x]
     else:
-        lda = K + lda_pad
+        ks = K if a2 is None else a2[0]                      # columns of the first source
+        lda = ks + lda_pad
         nA = batch if (sA == "own" and batch > 1) else 1
-        Ab = (ints((nA, M, lda), -2, 2) if integer else randn((nA, M, lda))).to(dt)
+        Ab = (a_ints((nA, M, lda)) if integer else randn((nA, M, lda))).to(dt)
+        A2b = None
+        if a2 is not None:
+            assert batch == 1
+            lda2 = K - ks + a2[1]
+            A2b = (a_ints((M, lda2)) if integer else randn((M, lda2))).to(dt)
+            desc.update(A2=A2b, lda2=lda2, k_split=ks)
+        if onehot is not None:
+            assert batch == 1 and a2 is None
+            T = onehot[1]
+            L = onehot_len(T)
+            m = torch.arange(M, device=dev)
+            Ab[0, :, :K] = 0
+            if onehot[0] == "gn":
+                Ab[0, :, :L] = onehot_rows(m // T, m % T, torch.clamp(M - (m // T) * T, max=T), T, L).to(dt)
+            else:
+                Ab[0, m, m % L] = 1                        # row m reads W[n][m mod L]
         A_ops = [Ab[min(z, nA - 1), :, :K].to(f64) for z in range(batch)]
+        if a2 is not None:
+            A_ops = [torch.cat([Ab[0, :, :ks], A2b[:, :K - ks]], dim=1).to(f64)]
         desc.update(A=Ab, lda=lda, sA=M * lda if nA > 1 else 0)
-        keep = [Ab]
+        keep = [Ab, A2b]
     # ---- W: [batch | 1][N][ldb], asymmetric; rows past n_valid hold 77 (must read as zero)
     ldb = K + ldb_pad
     nB = batch if (sB == "own" and batch > 1) else 1
@@ -177,6 +294,17 @@ def run_case(ctx, path, M, N, K, batch=1, conv=None, data="int", sA="own", sB="o
         Wf = (((ni * 7 + zi * 3) % 5 - 2) + ki % 3).to(f64)
     else:
         Wf = randn((nB, N, ldb)) / math.sqrt(K)
+    if onehot is not None:
+        assert nv == N and nB == 1
+        T = onehot[1]
+        L = onehot_len(T)
+        n = torch.arange(N, device=dev)
+        k0 = 4 * conv[3] if conv is not None else 0          # conv: the centre tap
+        Wf[0, :, :K] = 0
+        if onehot[0] == "gn":
+            Wf[0, n, k0 + n % L] = onehot_val(n)           # column n is hot where the row's position is the (n mod L)-th probed one
+        else:
+            Wf[0, :, :L] = onehot_rows(n // T, n % T, torch.clamp(N - (n // T) * T, max=T), T, L) * onehot_val(n)[:, None]
     Wf[:, nv:, :] = 77.0
     Wb = Wf.to(dt)
     W_ops = []
@@ -275,8 +403,15 @@ def run_case(ctx, path, M, N, K, batch=1, conv=None, data="int", sA="own", sB="o
         VTbuf = torch.full((samples * vt_bs,), float("nan"), device=dev, dtype=dt)
         desc.update(vt_out=VTbuf, vt_n0=vt_n0, vt_rows=vt_rows, vt_ld=vt_ld, vt_bs=vt_bs)
 
-    with _halo_min(halo_min):
-        rc, got = gemm_ex(ctx, **desc)
+    launch_env = _halo_min(halo_min, knobs)
+    if emit is not None:
+        emit.prepare(ctx, desc, launch_env)
+
+    def launch():
+        with launch_env:
+            return gemm_ex(ctx, **desc)
+
+    rc, got = launch()
     ctx.check(rc, "gemm_ex")
     torch.cuda.synchronize()
     assert got == tuple(path), "kernel path %s, expected %s" % (got, tuple(path))
@@ -334,6 +469,8 @@ def run_case(ctx, path, M, N, K, batch=1, conv=None, data="int", sA="own", sB="o
             assert bool(((vout - vref).abs() <= HALF.u * vref.abs() + 1.01 * E[:, vt_n0:]).all()), "V^T outside the bound"
         assert bool(VTbuf[~vwritten].isnan().all()), "%d elements written outside V^T's [sample][column][vt_rows] area" % (
             int((~VTbuf[~vwritten].isnan()).sum()))
+    if emit is not None:
+        emit.check(ctx, out, integer, launch)
     del keep
 
 
