@@ -706,11 +706,11 @@ AttnPath attention_describe(const AttnArgs& a, const AttnPath* force) {
   }
   // Two query blocks per wave (QB = 2) when the registers allow two waves per SIMD (d <= 64: 222 VGPRs):
   // 0.67 vs 0.73 ms at 16 x 8 x 4096^2 x 40.  SVG_ATTN_QB=1 forces the single-block form.
-  static const int nst_env = getenv("SVG_ATTN_NST") ? atoi(getenv("SVG_ATTN_NST")) : 1;   // same-box A/B: one stage + two barriers is 1-2 % faster than two stages + one barrier
-  static const int qb_env = getenv("SVG_ATTN_QB") ? atoi(getenv("SVG_ATTN_QB")) : 2;
-  static const int bc_env = getenv("SVG_ATTN_BC") ? atoi(getenv("SVG_ATTN_BC")) : 1;
-  static const int hv_env = getenv("SVG_ATTN_HV") ? atoi(getenv("SVG_ATTN_HV")) : 1;   // same-box A/B at 28 x 8 x 4096^2 x 40: 1.006 vs 1.026 ms
-  static const int dma_env = getenv("SVG_ATTN_DMA") ? atoi(getenv("SVG_ATTN_DMA")) : 1;
+  const int nst_env = (int)svg_env_i64("SVG_ATTN_NST", 1);   // same-box A/B: one stage + two barriers is 1-2 % faster than two stages + one barrier
+  const int qb_env = (int)svg_env_i64("SVG_ATTN_QB", 2);
+  const int bc_env = (int)svg_env_i64("SVG_ATTN_BC", 1);
+  const int hv_env = (int)svg_env_i64("SVG_ATTN_HV", 1);   // same-box A/B at 28 x 8 x 4096^2 x 40: 1.006 vs 1.026 ms
+  const int dma_env = (int)svg_env_i64("SVG_ATTN_DMA", 1);
   const int d = a.d;
   const bool can_bc = (d % 16) == 8;
   AttnPath p;

@@ -18,11 +18,6 @@ namespace SDNS {
 
 namespace {
 
-// compile-time ablation switch for tools/abl_halo.sh (-DHALO_ABL=n): 1 no stores, 2 no MFMA, 3 no DMA, 4 no fragment reads, 6 no barrier
-#ifndef HALO_ABL
-#define HALO_ABL 0
-#endif
-constexpr int ABL = HALO_ABL;
 constexpr int PW = 18;                 // patch width / height in pixels
 static_assert(PW == HALO_SIDE + 2, "the patch is the tile of output pixels the plan counts (gemm_tiles.h) plus its halo");
 constexpr int PPIX = PW * PW;          // 324
@@ -32,17 +27,14 @@ __host__ __device__ constexpr int halo_slot_at(int o, int nm) {
   return o == 0 ? nm / 2 - 1 : o == 1 ? nm + 1 : o == 2 ? nm + nm / 2 - 1 : o == 3 ? (3 * nm) / 4 : 2 * nm - 5;
 }
 
-// PP = ping-pong schedule: the 8 waves run as two groups of four (one wave of each group per SIMD) staggered by one
-// barrier, so that while one group multiplies (20 MFMAs between two barriers, s_setprio 1) the other issues its fragment
-// reads and DMAs — the matrix pipe always has a wave feeding it instead of all eight loading, then all eight multiplying.
-// MODE 0: lock-step loop, 1: ping-pong (PP), 2: merged ping-pong (below, BN = 128 with an even number of channel chunks),
-// 3: the merged ping-pong loop with the f32 residual stream's epilogue (GemmArgs::out_f32 == 2: f32 output and residual through the
-// narrow tile epilogue, natural weight rows).  A mode, not a further template parameter: the instantiations 0-2 keep their code.
-template <int BN, int MODE>
+// Ping-pong schedule: the 8 waves run as two groups of four (one wave of each group per SIMD) staggered by one barrier, so that while
+// one group multiplies (s_setprio 1) the other issues its fragment reads and DMAs — the matrix pipe always has a wave feeding it instead
+// of all eight loading, then all eight multiplying.  (A lock-step loop and a two-phase ping-pong loop — one k half per phase — were
+// measured against this one and removed: DESIGN.md 4.1.)
+// One step (tap) is one phase of the merged loop below.  RF: the f32 residual stream's epilogue (GemmArgs::out_f32 == 2: f32 output and
+// residual through the narrow tile epilogue, natural weight rows); otherwise 16-bit output through the wide epilogue.
+template <int BN, bool RF>
 __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
-  constexpr bool PP = MODE != 0;
-  constexpr bool RF = MODE == 3;
-  constexpr int LOOP = RF ? 2 : MODE;
   constexpr int NT = BN / 32;            // 16-wide channel tiles per wave
   constexpr int MT = 4;                  // image rows per wave
   constexpr int BIT = BN / 64;           // weight row groups per thread (64 rows per DMA instruction of all 8 waves)
@@ -51,11 +43,8 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
   constexpr int NWS = 3;                 // weight stages
   constexpr int NW = (BN + 63) / 64;     // weight DMA instructions per wave and slab (BN = 160: waves 4-7 pad with a dummy)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* const sP = smem;                 // 2 patch buffers
-  char* const sB = smem + 2 * PBUF;      // NWS weight stages
-  char* const sDummy = sB + NWS * B_BYTES;   // 8 KiB sink for the padding DMAs (1 KiB per wave)
+  // smem: 2 patch buffers, NWS weight stages, then an 8 KiB sink for the padding DMAs (1 KiB per wave)
   constexpr unsigned INVALID = 0x80000000u;
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
@@ -106,7 +95,7 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
   // ---- patch DMA map: linear LDS image [pixel][8 chunks]; lane id -> (pp, position); the swizzle rides on the source chunk
   auto patch_voff = [&](int i) -> unsigned {
     int ln = lane;
-    if (PP) asm volatile("" : "+v"(ln));               // keeps LICM from hoisting the six offsets back into registers
+    asm volatile("" : "+v"(ln));                       // keeps LICM from hoisting the six offsets back into registers
     const int id = (i * 8 + wid) * 64 + ln;            // 16-byte slot in the patch buffer
     const int pp = id >> 3, pos = id & 7;
     const int c = pos ^ (pp & 7);
@@ -116,11 +105,12 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
     const int sy = up2 ? yy >> 1 : yy, sx = up2 ? xx >> 1 : xx;
     return ok ? (unsigned)(((b * g.H + sy) * g.W + sx) * g.Cin + c * 8) * 2u : INVALID;
   };
-  // the lock-step loop keeps the six offsets in registers; the ping-pong loop (one piece per step, registers are its
-  // scarce resource) recomputes the piece's offset when it issues it
+  // The removed lock-step loop kept the six offsets here.  Zero-filled, never read and eliminated by the compiler — yet without it (and
+  // likewise without the dead HALO_NOPAD bodies below) the prologue of the BN = 160 kernels is scheduled in another order, so both stay
+  // until that change is measured: profiles/r16_retired_variants.md.
   unsigned p_voff[NPD];
 #pragma unroll
-  for (int i = 0; i < NPD; ++i) p_voff[i] = PP ? 0u : patch_voff(i);
+  for (int i = 0; i < NPD; ++i) p_voff[i] = 0u;
   // ---- weight DMA map (as gemm.hip): rows r0 + 64 i, chunk swizzled on the source
   const int r0 = tid >> 3;                                // 0..63
   const int cB = (tid & 7) ^ (r0 & 7);
@@ -146,17 +136,6 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
   }
 
   constexpr int OFF_B = 2 * PBUF, OFF_DUMMY = OFF_B + NWS * B_BYTES;
-  auto dma_patch = [&](int cc, int buf) {
-    const unsigned dst = lds0 + buf * PBUF + wave_u * 1024;
-    const int soff = cc * 128;
-#pragma unroll
-    for (int i = 0; i < NPD - 1; ++i) dma16(srdA, p_voff[i], soff, dst + i * 8192);
-    // last piece: only slots < 324*8 exist (32 of them, on wave 0).  Every wave still issues the instruction so that all
-    // waves count the same number of DMAs: wave 0 with lanes 32-63 switched off (a DMA writes active lanes only), the
-    // other waves into the sink with an out-of-range source.
-    const unsigned d5 = (wave_u == 0) ? (dst + (NPD - 1) * 8192) : (lds0 + OFF_DUMMY + wave_u * 1024);
-    if (wid != 0 || lane < 32) dma16(srdA, wid == 0 ? p_voff[NPD - 1] : INVALID, soff, d5);
-  };
   auto dma_patch_piece = [&](int cc, int buf, int i) {      // one of the NPD pieces (i is a compile-time constant after unrolling)
     const unsigned dst = lds0 + buf * PBUF + wave_u * 1024;
     const int soff = cc * 128;
@@ -186,174 +165,17 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // patch pixel of (image row wm*4 + i, column l15) for tap (0,0); tap (ky,kx) adds ky*18 + kx
-  int pp0[MT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i) pp0[i] = (wm * 4 + i) * PW + l15;
-
-  auto compute = [&](int pbuf, int stage, int toff) {
-    const char* sp = sP + pbuf * PBUF;
-    const char* sb = sB + stage * B_BYTES;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      h16x8 xf[MT], wf[NT];
-      if (ABL != 4) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i) xf[i] = *(const h16x8*)(sp + lds_off7(pp0[i] + toff, kk * 4 + lq));
-#pragma unroll
-      for (int j = 0; j < NT; ++j) wf[j] = *(const h16x8*)(sb + lds_off7(wn * (BN / 2) + j * 16 + l15, kk * 4 + lq));
-      } else {
-#pragma unroll
-      for (int i = 0; i < MT; ++i) asm volatile("" : "=v"(xf[i]));
-#pragma unroll
-      for (int j = 0; j < NT; ++j) asm volatile("" : "=v"(wf[j]));
-      }
-      if (ABL == 2) {
-#pragma unroll
-        for (int i = 0; i < MT; ++i) asm volatile("" :: "v"(xf[i]));
-#pragma unroll
-        for (int j = 0; j < NT; ++j) asm volatile("" :: "v"(wf[j]));
-        continue;
-      }
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-          acc[i][j] = MFMA_16x16x32(wf[j], xf[i], acc[i][j]);
-    }
-  };
-
-  // the operands were read a phase ago (the compiler's own counted lgkmcnt covers them, not the reads just issued)
-  auto mma_phase = [&](const h16x8 (&xf)[MT], const h16x8 (&wf)[NT]) {
-    __builtin_amdgcn_sched_barrier(0);
-    if (ABL == 2) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i) asm volatile("" :: "v"(xf[i]));
-#pragma unroll
-      for (int j = 0; j < NT; ++j) asm volatile("" :: "v"(wf[j]));
-      return;
-    }
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-        acc[i][j] = MFMA_16x16x32(wf[j], xf[i], acc[i][j]);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  };
-
-  // ---- ping-pong main loop ------------------------------------------------------------------------------------------
-  // Step s = (cc, tap) is two phases (the k halves of the 64-channel chunk); a phase is
-  //     [issue the fragment reads of the NEXT phase + this phase's share of the DMAs (+ counted wait in phase 0)]
-  //     barrier  [20 MFMAs]  barrier
-  // and group 1 (waves 4-7) runs one barrier behind group 0, so its load segment coincides with group 0's MFMAs.
-  // Fragments are read one phase ahead into the other register set, so an MFMA segment never waits on LDS latency; every
-  // wave drains its own reads (lgkmcnt(0), long since landed) before the barrier that closes its MFMA segment.
-  //   RAW: slab s+1 is retired by every wave's counted vmcnt in the load segment of phase (s,0); its first reads are
-  //        issued in the load segment of phase (s,1), two barriers later for that wave's group, one for the other group.
-  //   WAR: slab s+2 (issued from phase (s,0) on) overwrites the stage of slab s-1, whose last reads were issued in phase
-  //        (s-1,0) and drained before that phase's closing barrier — two barriers earlier for the issuing group, one for
-  //        the other.  The next chunk's patch goes into the other patch buffer one piece per step (taps 0-5).
-  //   DMA issue order per step: phase 0: the first N0 instructions of slab s+2; phase 1: the rest, then a patch piece.
-  //   vmcnt in phase (s,0), after its issues; oldest first: [slab s+1 ...][patch piece of s-1][first N0 of slab s+2].
-  // The load segment has to be shorter than the MFMA segment it hides under, so its address arithmetic is hoisted: the
-  // swizzle key of a patch read is (l15 + d) & 7 with d = (18 i + tap offset) & 7 a compile-time constant, so 8 x 2
+  // ---- main loop: steps s = (cc, tap), weight slab s lives in stage s % 3, the patch alternates per chunk -------------------------
+  // A step (tap) is ONE phase: both k halves, 32 (BN = 128) / 40 (BN = 160) MFMAs between two barriers.  The fragments of a step are
+  // read in the step's own load segment (one register set): its latency runs beside the OTHER group's MFMA segment, which is what the
+  // stagger is for.  The swizzle key of a patch read is (l15 + d) & 7 with d = (18 i + tap offset) & 7 a compile-time constant, so 8 x 2
   // precomputed lane addresses + an immediate serve all 72 reads of a chunk; the weight reads need 2.
-  if (LOOP == 1 && cc_begin < cc_end) {
-    constexpr int N0 = (NW + 1) / 2;
-    const int grp = wave_u >> 2;
-#pragma unroll
-    for (int i = 0; i < NPD; ++i) dma_patch_piece(cc_begin, 0, i);
-    dma_weights(cc_begin, 0, 0);
-    dma_weights(cc_begin, 1, 1);
-    wait_vm(NW);
-    bar();
-    if (grp == 1) bar();
-
-    int xaddr[8][2];                     // patch lane address for key offset d and k half (buffer 0; flipped per chunk)
-#pragma unroll
-    for (int d = 0; d < 8; ++d)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-        xaddr[d][kk] = (wm * 4 * PW + l15) * 128 + (((kk * 4 + lq) ^ ((l15 + d) & 7)) << 4);
-    int waddr[2];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) waddr[kk] = OFF_B + (wn * (BN / 2) + l15) * 128 + (((kk * 4 + lq) ^ (l15 & 7)) << 4);
-    auto rd_x = [&](int tap, int kk, h16x8 (&xf)[MT]) {
-      const int toff = (tap / 3) * PW + (tap % 3);
-#pragma unroll
-      for (int i = 0; i < MT; ++i) {
-        const int rel = i * PW + toff;
-        if (ABL != 4) xf[i] = *(const h16x8*)(smem + xaddr[rel & 7][kk] + rel * 128);
-      }
-    };
-    auto rd_w = [&](int stage, int kk, h16x8 (&wf)[NT]) {
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-        if (ABL != 4) wf[j] = *(const h16x8*)(smem + waddr[kk] + stage * B_BYTES + j * 2048);
-    };
-    auto dma_w_part = [&](int cc, int tap, int stage, int i0, int i1) {     // instructions [i0, i1) of a slab's NW
-      const unsigned dst = lds0 + OFF_B + stage * B_BYTES + wave_u * 1024;
-      const int soff = (tap * g.Cin + cc * 64) * 2;
-#pragma unroll
-      for (int i = i0; i < i1; ++i) {
-        if (i < BIT) dma16(srdB, b_voff[i], soff, dst + i * 8192);
-        else dma16(srdB, b_voff_tail, soff, (wave_u < 4) ? (dst + BIT * 8192) : (lds0 + OFF_DUMMY + wave_u * 1024));
-      }
-    };
-
-    h16x8 xa[MT], wa[NT], xb[MT], wb[NT];
-    rd_x(0, 0, xa);
-    rd_w(0, 0, wa);
-    for (int cc = cc_begin; cc < cc_end; ++cc) {
-      const int pbuf = (cc - cc_begin) & 1;
-      const int hn = (cc + 1 < cc_end) ? 1 : 0;
-#pragma unroll
-      for (int tap = 0; tap < 9; ++tap) {
-        const bool more_w = tap < 7 || hn;                    // slab s+2 exists
-        const int wcc = tap < 7 ? cc : cc + 1, wtap = tap < 7 ? tap + 2 : tap - 7, wst = (tap + 2) % NWS;
-        // phase 0: second half of this step's fragments, first share of the DMAs, counted wait
-        rd_x(tap, 1, xb);
-        rd_w(tap % NWS, 1, wb);
-        if (ABL != 3 && more_w) dma_w_part(wcc, wtap, wst, 0, N0);
-        wait_vm(more_w && ABL != 3 ? N0 : 0);
-        bar();
-        mma_phase(xa, wa);
-        bar();
-        // phase 1: first half of the next step's fragments, the rest of the DMAs
-        if (tap == 8) {                                        // the next step reads the other patch buffer
-          const int flip = pbuf ? -PBUF : PBUF;
-#pragma unroll
-          for (int d = 0; d < 8; ++d) { xaddr[d][0] += flip; xaddr[d][1] += flip; }
-        }
-        if (tap < 8 || hn) {
-          rd_x((tap + 1) % 9, 0, xa);
-          rd_w((tap + 1) % NWS, 0, wa);
-        }
-        if (ABL != 3 && more_w) dma_w_part(wcc, wtap, wst, N0, NW);
-        if (ABL != 3 && tap < NPD && hn) dma_patch_piece(cc + 1, pbuf ^ 1, tap);
-        bar();
-        mma_phase(xb, wb);
-        bar();
-      }
-    }
-    if (grp == 0) bar();
-  }
-
-  // ---- merged ping-pong loop (MODE 2) ---------------------------------------------------------------------------------------------
-  // A phase of the loop above is 16 (BN = 128) or 20 (BN = 160) MFMAs per wave — 256 / 320 matrix cycles — between two barriers,
-  // against a load segment of 8-9 fragment reads + DMA issue that does not get shorter: the VAE's 128-channel convs at 512 x 512 ran
-  // at 0.29-0.35 of the peak.  Here a step (tap) is ONE phase: both k halves, 32 / 40 MFMAs between two barriers, half the barriers.
-  // The fragments of a step are read in the step's own load segment (one register set, not two): its latency runs beside the OTHER
-  // group's MFMA segment, which is what the stagger is for.
   //   group 0:  [L(s)] P [M(s)] P [L(s+1)] ...      group 1 one barrier behind: its L(s) runs beside group 0's M(s).
   //   L(s): read the 2 (MT + NT) fragments of step s (slab s: own pieces retired by the counted vmcnt of L(s - 1), the others'
   //         published by the barriers since); DMA slab s + 2 -> stage (s + 2) % 3 (slab s - 1: its reads were drained — lgkmcnt(0) —
   //         before the barrier that closed L(s - 1) in BOTH groups); patch piece (taps 0-5) of the next chunk; vmcnt(own issues): slab
   //         s + 1 and the previous patch piece have landed; lgkmcnt(0).
-  if (LOOP == 2 && cc_begin < cc_end) {
+  if (cc_begin < cc_end) {
     const int grp = wave_u >> 2;
     // HALO_NOPAD = 1: no padding DMAs (round 5, VERDICT r04 #5: the scheme of conv_halo_fp8.hip).  The counted vmcnt of a load segment only
     // has to leave THIS wave's just-issued DMAs in flight — a wave's counter sees its own operations, in order — so the waves need not
@@ -490,44 +312,7 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
     if (grp == 0) bar();
   }
 
-  // ---- lock-step main loop over steps s = (cc, tap): weight slab s lives in stage s % 3; the patch alternates per chunk
-  // iteration s:  wait until slab s (and anything older) has landed, leaving only slab s+1 (and a just-issued patch)
-  //               in flight -> barrier (everyone's pieces landed; stage (s+2)%3 and, at tap 0, the other patch buffer
-  //               were last read in iteration s-1) -> issue patch(cc+1) [tap 0] and slab s+2 -> multiply slab s.
-  if (!PP && cc_begin < cc_end) {
-    const int nsteps = (cc_end - cc_begin) * 9;
-    auto issue_w = [&](int sidx) {
-      if (ABL == 3) return;
-      if (sidx < nsteps) dma_weights(cc_begin + sidx / 9, sidx % 9, sidx % NWS);
-    };
-    dma_patch(cc_begin, 0);
-    issue_w(0);
-    issue_w(1);
-    bool patch_just_issued = false;
-    int s = 0;
-    for (int cc = cc_begin; cc < cc_end; ++cc) {
-      const int pbuf = (cc - cc_begin) & 1;
-      for (int tap = 0; tap < 9; ++tap, ++s) {
-        // outstanding, oldest first: [slab s] [patch (if issued last iteration)] [slab s+1]
-        if (s + 1 >= nsteps) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (patch_just_issued) {
-          if (NW == 3) asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        } else {
-          if (NW == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        }
-        if (ABL != 6) __builtin_amdgcn_s_barrier();
-        patch_just_issued = false;
-        if (tap == 0 && cc + 1 < cc_end && ABL != 3) { dma_patch(cc + 1, pbuf ^ 1); patch_just_issued = true; }
-        issue_w(s + 2);
-        const int ky = tap / 3, kx = tap - ky * 3;
-        compute(pbuf, s % NWS, ky * PW + kx);
-      }
-    }
-    __syncthreads();
-  }
-
   // ---- epilogue -----------------------------------------------------------------------------------------------
-  if (ABL == 1 && acc[0][0][0] != 12345.f) return;
   const int mr = (b * OH + y0 + wm * 4) * OW + x0 + l15;        // image row i of the wave adds i * OW
   const int nc = n0 + wn * (BN / 2) + lq * 4;
   if (g.splitk > 1) {
@@ -548,46 +333,30 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
   }
 }
 
-template <int BN, int MODE>
+template <int BN, bool RF>
 void launch_halo(const GemmArgs& g, dim3 grid, hipStream_t s) {
   constexpr int smem = 2 * PPIX * 128 + 3 * BN * 128 + 8192;
-  hipLaunchKernelGGL((conv_halo_kernel<BN, MODE>), grid, dim3(512), smem, s, g);
+  hipLaunchKernelGGL((conv_halo_kernel<BN, RF>), grid, dim3(512), smem, s, g);
 }
+
+constexpr int HALO_DMA_M = 4;          // DMA instructions of a step issued among its MFMAs (the kernel reads GemmArgs::pp_dma_m at run time)
 
 }  // namespace
 
 void conv_halo_init_device() {
-  HIP_OK(hipFuncSetAttribute((const void*)conv_halo_kernel<128, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PPIX * 128 + 3 * 128 * 128 + 8192));
-  HIP_OK(hipFuncSetAttribute((const void*)conv_halo_kernel<128, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PPIX * 128 + 3 * 128 * 128 + 8192));
-  HIP_OK(hipFuncSetAttribute((const void*)conv_halo_kernel<128, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PPIX * 128 + 3 * 128 * 128 + 8192));
-  HIP_OK(hipFuncSetAttribute((const void*)conv_halo_kernel<160, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PPIX * 128 + 3 * 160 * 128 + 8192));
-  HIP_OK(hipFuncSetAttribute((const void*)conv_halo_kernel<160, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PPIX * 128 + 3 * 160 * 128 + 8192));
-  HIP_OK(hipFuncSetAttribute((const void*)conv_halo_kernel<160, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PPIX * 128 + 3 * 160 * 128 + 8192));
-  HIP_OK(hipFuncSetAttribute((const void*)conv_halo_kernel<128, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PPIX * 128 + 3 * 128 * 128 + 8192));
-  HIP_OK(hipFuncSetAttribute((const void*)conv_halo_kernel<160, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PPIX * 128 + 3 * 160 * 128 + 8192));
+  HIP_OK(hipFuncSetAttribute((const void*)conv_halo_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PPIX * 128 + 3 * 128 * 128 + 8192));
+  HIP_OK(hipFuncSetAttribute((const void*)conv_halo_kernel<160, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PPIX * 128 + 3 * 160 * 128 + 8192));
+  HIP_OK(hipFuncSetAttribute((const void*)conv_halo_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PPIX * 128 + 3 * 128 * 128 + 8192));
+  HIP_OK(hipFuncSetAttribute((const void*)conv_halo_kernel<160, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PPIX * 128 + 3 * 160 * 128 + 8192));
 }
 
 // bn: the channel-tile width of the plan (gemm_plan.cpp), 128 or 160
 void launch_conv_halo(const GemmArgs& g, int bn, dim3 grid, hipStream_t s) {
-  static const int pp = getenv("SVG_HALO_PP") ? atoi(getenv("SVG_HALO_PP")) : 1;
-  const bool w160 = bn == 160;
-  if (g.out_f32 == 2) {     // f32 residual stream: the merged loop at either width, whatever the A/B switches below say
-    GemmArgs gm = g;
-    gm.pp_dma_m = std::max(0, std::min(4, (int)svg_env_i64("SVG_HALO_DMA_M", 4)));
-    if (w160) launch_halo<160, 3>(gm, grid, s); else launch_halo<128, 3>(gm, grid, s);
-    return;
-  }
-  // merged ping-pong (one 32 / 40-MFMA phase per tap); SVG_HALO_MERGE (cached, svg_env_refresh): 0 off, 1 BN = 128 only, 2 / unset both widths
-  const int mm = (int)svg_env_i64("SVG_HALO_MERGE", 2);
-  if (pp && mm >= 1 && (mm >= 2 || !w160)) {
-    GemmArgs gm = g;
-    gm.pp_dma_m = std::max(0, std::min(4, (int)svg_env_i64("SVG_HALO_DMA_M", 4)));   // DMA instructions of a step issued among its MFMAs (merged loop)
-    if (w160) launch_halo<160, 2>(gm, grid, s); else launch_halo<128, 2>(gm, grid, s);
-    return;
-  }
-  if (false) {}
-  else if (pp) { if (w160) launch_halo<160, 1>(g, grid, s); else launch_halo<128, 1>(g, grid, s); }
-  else    { if (w160) launch_halo<160, 0>(g, grid, s); else launch_halo<128, 0>(g, grid, s); }
+  GemmArgs gm = g;
+  gm.pp_dma_m = HALO_DMA_M;
+  const bool rf = g.out_f32 == 2;        // f32 residual stream
+  if (bn == 160) { if (rf) launch_halo<160, true>(gm, grid, s); else launch_halo<160, false>(gm, grid, s); }
+  else           { if (rf) launch_halo<128, true>(gm, grid, s); else launch_halo<128, false>(gm, grid, s); }
 }
 
 }  // namespace SDNS

@@ -393,8 +393,7 @@ void launch_inst(const GemmArgs& g, dim3 grid, hipStream_t s) {
     if (g.act != ACT_GEGLU && !g.out_f32) { hipLaunchKernelGGL((igemm_kernel<BN, AMODE, 1>), grid, dim3(256), smem, s, g); return; }
   }
   if constexpr (kPermInst<BN, AMODE>) {
-    static const int perm_on = getenv("SVG_IGEMM_PERM") ? atoi(getenv("SVG_IGEMM_PERM")) : 1;
-    if (perm_on && g.act != ACT_GEGLU && !g.out_f32 && g.splitk == 1) { hipLaunchKernelGGL((igemm_kernel<BN, AMODE, 2>), grid, dim3(256), smem, s, g); return; }
+    if (g.act != ACT_GEGLU && !g.out_f32 && g.splitk == 1) { hipLaunchKernelGGL((igemm_kernel<BN, AMODE, 2>), grid, dim3(256), smem, s, g); return; }
   }
   hipLaunchKernelGGL((igemm_kernel<BN, AMODE>), grid, dim3(256), smem, s, g);
 }
@@ -464,17 +463,15 @@ static void launch_gemm(svg_ctx* ctx, const GemmArgs& g, const GemmPlan& plan, h
   if (g.vt_out) SVG_CHECK(g.vt_rows > 0 && g.M % g.vt_rows == 0, "gemm: the V^T write needs whole samples (M %d, vt_rows %d)", g.M, g.vt_rows);
   if (!SVG_LAUNCHING(ctx)) return;
   GemmArgs a = g;
-  static const int dbg_env = getenv("SVG_GEMM_DBG") ? atoi(getenv("SVG_GEMM_DBG")) : 0;
-  a.dbg = dbg_env;
+  a.dbg = (int)svg_env_i64("SVG_GEMM_DBG", 0);
   a.splitk = plan.splitk;
   {
     // Each XCD has its own L2: with the A rows adjacent every XCD streams ALL the weights (8 x N*K*2 bytes per launch),
     // with the weights adjacent every XCD streams all of A.  Pick the cheaper (16 x 16 / 8 x 8 convs: 30 MB of weights
     // against 5-18 MB of image).
-    static const int tn_env = getenv("SVG_TN_MAJOR") ? atoi(getenv("SVG_TN_MAJOR")) : -1;
     const double a_bytes_phys = (a.amode == A_DENSE ? (double)a.M * a.K : (double)(a.M / (a.Ho * a.Wo)) * a.H * a.W * a.Cin) * 2.0;
     const double w_bytes = (double)a.N * a.K * 2.0;
-    a.tn_major = tn_env >= 0 ? tn_env : (a.batch == 1 && w_bytes > a_bytes_phys);
+    a.tn_major = a.batch == 1 && w_bytes > a_bytes_phys;
   }
   // algorithmic bytes: every operand once (a conv reads its image once, not once per tap)
   const double a_elems = g.amode == A_DENSE ? (double)g.M * g.K : (double)(g.M / (g.Ho * g.Wo)) * g.H * g.W * g.Cin;

@@ -28,8 +28,8 @@ int search_bn(int64_t row_tiles, int N, bool tie_wider) {
 // ---- halo conv: stride-1 3x3 convs on images whose sides are multiples of 16, with enough 16x16-pixel blocks x channel tiles to give
 // every CU a workgroup (below that the 128-row implicit GEMM with its split-K is faster: same-box A/B at 16x16 images)
 bool conv_halo_supported(const GemmArgs& g, int* bn) {
-  static const int off = getenv("SVG_NO_HALO") ? atoi(getenv("SVG_NO_HALO")) : 0;
-  static const int up_on = getenv("SVG_HALO_UP2") ? atoi(getenv("SVG_HALO_UP2")) : 1;
+  const int off = (int)svg_env_i64("SVG_NO_HALO", 0);
+  const int up_on = (int)svg_env_i64("SVG_HALO_UP2", 1);
   const bool s1 = g.amode == A_CONV_S1 && g.Ho == g.H && g.Wo == g.W;
   const bool up = up_on && g.amode == A_CONV_UP2 && g.Ho == 2 * g.H && g.Wo == 2 * g.W && !g.A2;
   if (off || !(s1 || up) || g.Cin % 64 != 0 || g.Ho % HALO_SIDE != 0 || g.Wo % HALO_SIDE != 0 || g.batch != 1 || g.out_f32 == 1 ||
@@ -44,7 +44,7 @@ bool conv_halo_supported(const GemmArgs& g, int* bn) {
 int conv_halo_splitk(const GemmArgs& g, int bn) {
   const int64_t blocks = (int64_t)(g.M / HALO_ROWS) * cdiv(g.N, bn);
   const int CC = g.Cin / 64;
-  static const int tgt = getenv("SVG_HALO_SPLIT_TGT") ? atoi(getenv("SVG_HALO_SPLIT_TGT")) : 320;
+  const int tgt = (int)svg_env_i64("SVG_HALO_SPLIT_TGT", 320);
   if (blocks < 192 && CC >= 4) return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((tgt + blocks - 1) / blocks, CC / 2), 8));
   return 1;
 }
@@ -52,7 +52,7 @@ int conv_halo_splitk(const GemmArgs& g, int bn) {
 // ---- weight-stationary: dense, 16-bit output, K = 320, whole column groups, unbatched (one W for all rows), no GEGLU / row bias /
 // per-sample bias / swapped LayerNorm / two-source A
 bool gemm_ws_supported(const GemmArgs& g) {
-  static const int on = getenv("SVG_GEMM_WS") ? atoi(getenv("SVG_GEMM_WS")) : 1;
+  const int on = (int)svg_env_i64("SVG_GEMM_WS", 1);
   if (!on) return false;
   if (g.amode != A_DENSE || g.A2 || g.out_f32 || g.act == ACT_GEGLU || g.bias_row || g.bias_bn || g.ln_swapped || g.batch != 1) return false;
   // K = 640 (80-column groups) builds and is correct but loses: two register sets of 80 A-fragment registers spill, and eight /
@@ -69,8 +69,8 @@ bool gemm_ws_supported(const GemmArgs& g) {
 
 // ---- ping-pong: dense, unbatched, K a multiple of 64 and long enough, enough 256-row tiles to give every CU a workgroup
 bool gemm_pp_supported(const GemmArgs& g, int* bn) {
-  static const int on = getenv("SVG_GEMM_PP") ? atoi(getenv("SVG_GEMM_PP")) : 1;
-  static const int min_kt = getenv("SVG_GEMM_PP_MINKT") ? atoi(getenv("SVG_GEMM_PP_MINKT")) : 16;
+  const int on = (int)svg_env_i64("SVG_GEMM_PP", 1);
+  const int min_kt = (int)svg_env_i64("SVG_GEMM_PP_MINKT", 16);
   // wide outputs (the GEGLU projection at 32 x 32: N = 5120, K = 640) amortise the tile's unhidden prologue over enough columns at
   // 10 slabs already: 0.248 against 0.258-0.262 ms on the 128-row kernel, same box; N = 1280 at K = 640 loses (0.081 against 0.073)
   const int need_kt = g.N >= 2560 ? std::min(min_kt, 10) : min_kt;
@@ -82,7 +82,7 @@ bool gemm_pp_supported(const GemmArgs& g, int* bn) {
 
 // ---- tiled kernel: takes everything else
 int pick_bn(const GemmArgs& g) {
-  static const int force = getenv("SVG_GEMM_BN") ? atoi(getenv("SVG_GEMM_BN")) : 0;
+  const int force = (int)svg_env_i64("SVG_GEMM_BN", 0);
   if (force && g.act != ACT_GEGLU && g.N > 64) return force;
   if (g.act == ACT_GEGLU) return 128;
   if (g.out_f32 != 2) {                 // (the f32 stream has 128 / 160-column instantiations only)

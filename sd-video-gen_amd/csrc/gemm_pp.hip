@@ -289,7 +289,7 @@ void gemm_pp_init_device() {
 
 // bn: the column-tile width of the plan (gemm_plan.cpp), 128 or 160
 void launch_gemm_pp(const GemmArgs& g0, int bn, hipStream_t s) {
-  static const int gm_env = getenv("SVG_PP_GROUPM") ? atoi(getenv("SVG_PP_GROUPM")) : 4;
+  const int gm_env = (int)svg_env_i64("SVG_PP_GROUPM", 4);
   GemmArgs g = g0;
   g.group_m = gm_env;
   g.pp_merge = (int)svg_env_i64("SVG_PP_MERGE", 1);        // 0 = the two-phase loop

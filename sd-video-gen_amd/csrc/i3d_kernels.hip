@@ -363,7 +363,7 @@ void frechet_distance(const float* x1, int n1, const float* x2, int n2, int d, d
   double* S1 = cs + 2 * d; double* S2 = S1 + (int64_t)d * d; double* Wk = S2 + (int64_t)d * d; double* V = Wk + (int64_t)d * d;
   double* R = V + (int64_t)d * d; double* T2 = R + (int64_t)d * d;
   const dim3 g1((d + 127) / 128), g2((d + 127) / 128, d);
-  const int sweeps = getenv("SVG_JACOBI_SWEEPS") ? atoi(getenv("SVG_JACOBI_SWEEPS")) : 40;      // an upper bound: the kernel stops when the off-diagonal mass is below 1e-30 of the diagonal's (10-12 sweeps full rank, ~20 rank-deficient)
+  constexpr int sweeps = 40;      // an upper bound: the kernel stops when the off-diagonal mass is below 1e-30 of the diagonal's (10-12 sweeps full rank, ~20 rank-deficient)
   hipLaunchKernelGGL(col_mean_kernel, g1, dim3(128), 0, s, x1, m1, n1, d);
   hipLaunchKernelGGL(col_mean_kernel, g1, dim3(128), 0, s, x2, m2, n2, d);
   hipLaunchKernelGGL(cov_kernel, g2, dim3(128), 0, s, x1, m1, S1, n1, d);

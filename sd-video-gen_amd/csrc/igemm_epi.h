@@ -18,9 +18,6 @@ namespace {
 // (ff_fused) that was three quarters of the matrix time.  Coefficients: tools/fit_gelu.py.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x4 gelu_erf4(f32x4 x) {
-#ifdef GELU_ABL
-  return x;
-#endif
 #ifdef GELU_AS      // A/B switch: the Abramowitz-Stegun form of rounds 1-2 (tools/build_variant.sh as "-DGELU_AS")
   f32x4 o;
   for (int i = 0; i < 4; ++i) {
@@ -42,9 +39,6 @@ __device__ __forceinline__ f32x4 gelu_erf4(f32x4 x) {
   return out;
 }
 __device__ __forceinline__ float gelu_erf(float x) {
-#ifdef GELU_ABL
-  return x;
-#endif
   const float a = fminf(fabsf(x), 6.f);
   float p = 3.4645448e-05f;
   p = fmaf(p, a, -0.000782622703f); p = fmaf(p, a, 0.00812418268f); p = fmaf(p, a, -0.0534785727f);

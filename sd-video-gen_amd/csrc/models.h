@@ -275,7 +275,7 @@ static inline int64_t gn_part_floats(int64_t B, int64_t HW, int64_t N) { return 
 
 // a GnEmit with its arena buffer for an (N, hw, Cout) output; none below 1024 rows per sample (the single-launch GroupNorm takes those)
 GnEmit emit_for(svg_ctx* ctx, int N, int64_t hw, int Cout);
-// hands ln->buf to a planned dense GEMM when its launch emits few enough column tiles ($SVG_LN_EPI=0: never); ln->tiles says whether
+// hands ln->buf to a planned dense GEMM when its launch emits few enough column tiles; ln->tiles says whether
 void plan_ln_emit(GemmArgs& g, const GemmPlan& plan, LnEmit* ln);
 
 // shared graph pieces (sdnet.cpp)

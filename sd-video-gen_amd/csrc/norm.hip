@@ -542,10 +542,10 @@ void gn_fold_weights(const float* W, const float* bias, const float* gamma, cons
 static int gn_apply_blocks(int B, int HW, int PL) { return std::max(1, std::min(HW / PL, std::max(HW / (PL * 16), (2048 + B - 1) / B))); }
 
 GnPath groupnorm_describe(const GnShape& a, const GnPath* force) {
-  static const int no_small = getenv("SVG_GN_NOSMALL") ? atoi(getenv("SVG_GN_NOSMALL")) : 0;
-  static const int vw8 = getenv("SVG_GN_SMALL_VW8") ? atoi(getenv("SVG_GN_SMALL_VW8")) : 1;
-  static const int use_epi = getenv("SVG_GN_EPI") ? atoi(getenv("SVG_GN_EPI")) : 1;
-  static const int fused_mx = getenv("SVG_GN_MX") ? atoi(getenv("SVG_GN_MX")) : 1;
+  const int no_small = (int)svg_env_i64("SVG_GN_NOSMALL", 0);
+  const int vw8 = (int)svg_env_i64("SVG_GN_SMALL_VW8", 1);
+  const int use_epi = (int)svg_env_i64("SVG_GN_EPI", 1);
+  const int fused_mx = (int)svg_env_i64("SVG_GN_MX", 1);
   const int C1 = a.C1, C2 = a.C2, C = C1 + C2, B = a.B, HW = a.HW, groups = a.groups;
   GnPath p;
   if (a.mx_out) {

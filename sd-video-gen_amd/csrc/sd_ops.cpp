@@ -275,8 +275,6 @@ int SVG_OP(svg_op_ff_fused)(svg_ctx* ctx, const uint16_t* x, const float* ln_gam
     float* b1p = ctx->arena.get<float>(2 * F);
     float* s1 = ctx->arena.get<float>(2 * F);
     h16* w2p = ctx->arena.get<h16>((int64_t)C * F);
-    float* rs = ctx->arena.get<float>(M + 8);
-    float* rm = ctx->arena.get<float>(M + 8);
     if (SVG_LAUNCHING(ctx)) {
       HIP_OK(hipMemcpyAsync(w1d, w1, (size_t)2 * F * C * 4, hipMemcpyDefault, s));
       HIP_OK(hipMemcpyAsync(b1d, b1, (size_t)2 * F * 4, hipMemcpyDefault, s));
@@ -289,10 +287,8 @@ int SVG_OP(svg_op_ff_fused)(svg_ctx* ctx, const uint16_t* x, const float* ln_gam
       rowsum_h16(w1p, s1, 2 * F, C, s);
       pack_ff2_perm(w2d, w2p, C, F, s);
     }
-    // the kernel derives the LayerNorm statistics from the rows it holds (the UNet's path); SVG_FF_LNSTATS=1 feeds it ln_stats' instead
-    static const bool ext = getenv("SVG_FF_LNSTATS") && atoi(getenv("SVG_FF_LNSTATS"));
-    if (ext) ln_stats(ctx, (const h16*)x, rs, rm, M, C, 1e-5f, s);
-    ff_fused(ctx, (const h16*)x, C, w1p, b1p, s1, ext ? rs : nullptr, ext ? rm : nullptr, w2p, b2d, (const h16*)residual, C, (h16*)out, C, M, s);
+    // the kernel derives the LayerNorm statistics from the rows it holds (the UNet's path)
+    ff_fused(ctx, (const h16*)x, C, w1p, b1p, s1, w2p, b2d, (const h16*)residual, C, (h16*)out, C, M, s);
   });
   API_END(ctx)
 }

@@ -94,8 +94,7 @@ GnEmit emit_for(svg_ctx* ctx, int N, int64_t hw, int Cout) {
 // fills g.gn_part / emit->st when the launch of g leaves the output's GroupNorm column sums per `rows` output rows (gemm_plan()'s
 // gn_rows, or the 16 x 16 pixel block of the fp8 halo conv) and a sample is whole row tiles
 static void attach_gn_emit(GemmArgs& g, GnEmit* emit, int rows_per_sample, int rows) {
-  static const int use_epi = getenv("SVG_GN_EPI") ? atoi(getenv("SVG_GN_EPI")) : 1;   // 0: A/B switch, statistics pass as before
-  if (!use_epi || !emit || !emit->buf || rows_per_sample < 1024) return;   // small images take the single-launch GroupNorm (one read)
+  if (!emit || !emit->buf || rows_per_sample < 1024) return;   // small images take the single-launch GroupNorm (one read)
   if (rows <= 0 || rows_per_sample % rows != 0) return;
   g.gn_part = emit->buf;
   emit->st.part = emit->buf;
@@ -105,8 +104,7 @@ static void attach_gn_emit(GemmArgs& g, GnEmit* emit, int rows_per_sample, int r
 void plan_ln_emit(GemmArgs& g, const GemmPlan& plan, LnEmit* ln) {
   if (ln) ln->tiles = 0;
   if (!ln || !ln->buf) return;
-  static const int use_ln = getenv("SVG_LN_EPI") ? atoi(getenv("SVG_LN_EPI")) : 1;    // 0: A/B switch, ln_stats pass as before
-  const int tiles = use_ln ? plan.ln_tiles : 0;
+  const int tiles = plan.ln_tiles;
   if (tiles > 0 && tiles <= 5) { g.ln_part = ln->buf; g.ln_tiles = tiles; ln->tiles = tiles; }   // C = 1280 (8 tiles): the finish costs what the 8 us pass did
 }
 

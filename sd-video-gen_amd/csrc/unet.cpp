@@ -86,25 +86,9 @@ PackedLinear load_stacked(svg_ctx* ctx, WeightStore& ws, const std::vector<std::
   return pl;
 }
 
-// SVG_LN_FOLD=0 keeps the three LayerNorms of a transformer block as separate kernels (A/B and debugging)
-bool ln_fold_enabled() {
-  static const int on = getenv("SVG_LN_FOLD") ? atoi(getenv("SVG_LN_FOLD")) : 1;
-  return on != 0;
-}
-
-// rows per ff1 -> ff2 chunk: SVG_FF_CHUNK_MB bounds the chunk's GEGLU intermediate (rows x 4C x 2 bytes); 0 = unchunked.
-// Rounded to a multiple of 4096 rows (whole 256-row tiles of gemm_pp, whole samples at 64 x 64).
-int ff_chunk_rows(int M, int C) {
-  static const int mb = getenv("SVG_FF_CHUNK_MB") ? atoi(getenv("SVG_FF_CHUNK_MB")) : 0;
-  if (mb <= 0) return M;
-  const int64_t rows = ((int64_t)mb << 20) / ((int64_t)8 * C);
-  return (int)std::max<int64_t>(4096, std::min<int64_t>(M, rows / 4096 * 4096));
-}
-
 XfBlockW load_xf(svg_ctx* ctx, WeightStore& ws, const std::string& p, int C, int ctx_dim, hipStream_t s) {
   XfBlockW b;
   b.C = C;
-  const bool fold = ln_fold_enabled();
   b.gn = load_norm(ctx, ws, p + ".norm", C);
   {   // f32 copy of proj_in (GroupNorm folding rounds W * gamma * rstd once, per sample, at run time)
     const Weight& w = ws.get(p + ".proj_in.weight");
@@ -120,7 +104,7 @@ XfBlockW load_xf(svg_ctx* ctx, WeightStore& ws, const std::string& p, int C, int
   b.ln3 = load_norm(ctx, ws, t + ".norm3", C);
   // C = 320 (the 64 x 64 level): q | k | v stacked for the fused projection of gemm_ws.hip (one read of the tokens instead of two).
   // fold_ln_weights scales the f32 copy in place, so the stacked copy is packed from a scratch duplicate of the three matrices
-  if (fold && C == 320) {
+  if (C == 320) {
     WeightStore tmp;
     for (const char* n : {".attn1.to_q", ".attn1.to_k", ".attn1.to_v"}) {
       const Weight& w = ws.get(t + n + ".weight", {C, C});
@@ -130,10 +114,10 @@ XfBlockW load_xf(svg_ctx* ctx, WeightStore& ws, const std::string& p, int C, int
     b.qkv1 = load_stacked(ctx, tmp, {t + ".attn1.to_q", t + ".attn1.to_k", t + ".attn1.to_v"}, {C, C, C}, C, false, s, &b.ln1);
     tmp.clear();
   }
-  b.qk1 = load_stacked(ctx, ws, {t + ".attn1.to_q", t + ".attn1.to_k"}, {C, C}, C, false, s, fold ? &b.ln1 : nullptr);
-  b.v1 = load_linear(ctx, ws, t + ".attn1.to_v", C, C, false, s, fold ? &b.ln1 : nullptr);
+  b.qk1 = load_stacked(ctx, ws, {t + ".attn1.to_q", t + ".attn1.to_k"}, {C, C}, C, false, s, &b.ln1);
+  b.v1 = load_linear(ctx, ws, t + ".attn1.to_v", C, C, false, s, &b.ln1);
   b.o1 = load_linear(ctx, ws, t + ".attn1.to_out.0", C, C, true, s);
-  if (fold && C == 320) {   // packed copies for the one-launch cross-attention (xattn_fused.hip), made before load_linear releases the f32 originals
+  if (C == 320) {   // packed copies for the one-launch cross-attention (xattn_fused.hip), made before load_linear releases the f32 originals
     const Weight& wq = ws.get(t + ".attn2.to_q.weight", {C, C});
     const Weight& wo = ws.get(t + ".attn2.to_out.0.weight", {C, C});
     b.xq = (h16*)ctx->dalloc((int64_t)384 * C * sizeof(h16));
@@ -146,7 +130,7 @@ XfBlockW load_xf(svg_ctx* ctx, WeightStore& ws, const std::string& p, int C, int
     xattn_pack_o(wo.f32, b.xo, s);
     HIP_OK(hipStreamSynchronize(s));
   }
-  b.q2 = load_linear(ctx, ws, t + ".attn2.to_q", C, C, false, s, fold ? &b.ln2 : nullptr);
+  b.q2 = load_linear(ctx, ws, t + ".attn2.to_q", C, C, false, s, &b.ln2);
   b.k2 = load_linear(ctx, ws, t + ".attn2.to_k", C, ctx_dim, false, s);
   b.v2 = load_linear(ctx, ws, t + ".attn2.to_v", C, ctx_dim, false, s);
   b.o2 = load_linear(ctx, ws, t + ".attn2.to_out.0", C, C, true, s);
@@ -158,19 +142,14 @@ XfBlockW load_xf(svg_ctx* ctx, WeightStore& ws, const std::string& p, int C, int
     b.ff1.w = (h16*)ctx->dalloc((int64_t)2 * F * C * sizeof(h16));
     b.ff1.b = (float*)ctx->dalloc(2 * F * sizeof(float));
     float* bias = keep_f32(ctx, ws, t + ".ff.net.0.proj.bias", 2 * F);
-    float* btmp = nullptr;
-    if (fold) {   // fold LayerNorm 3 on the unpacked rows, then pack weights and bias together
-      HIP_OK(hipMalloc(&btmp, (size_t)2 * F * sizeof(float)));
-      fold_ln_weights(w.f32, bias, b.ln3.g, b.ln3.b, btmp, 2 * F, C, s);
-      bias = btmp;
-    }
-    pack_geglu(w.f32, bias, b.ff1.w, b.ff1.b, F, C, s);
-    if (fold) {
-      b.ff1.ln_s = (float*)ctx->dalloc((size_t)2 * F * sizeof(float));
-      rowsum_h16(b.ff1.w, b.ff1.ln_s, 2 * F, C, s);
-    }
+    float* btmp = nullptr;   // fold LayerNorm 3 on the unpacked rows, then pack weights and bias together
+    HIP_OK(hipMalloc(&btmp, (size_t)2 * F * sizeof(float)));
+    fold_ln_weights(w.f32, bias, b.ln3.g, b.ln3.b, btmp, 2 * F, C, s);
+    pack_geglu(w.f32, btmp, b.ff1.w, b.ff1.b, F, C, s);
+    b.ff1.ln_s = (float*)ctx->dalloc((size_t)2 * F * sizeof(float));
+    rowsum_h16(b.ff1.w, b.ff1.ln_s, 2 * F, C, s);
     HIP_OK(hipStreamSynchronize(s));
-    if (btmp) HIP_OK(hipFree(btmp));
+    HIP_OK(hipFree(btmp));
     ws.release(t + ".ff.net.0.proj.weight");
   }
   if (ff_fused_supported(C, 1 << 30)) {   // k-permuted copy of ff.net.2 for the fused feed-forward
@@ -406,8 +385,7 @@ struct UnetRun {
     // LayerNorm's partials are consumed before the next producer runs)
     LnEmit le;
     le.buf = ctx->arena.get<float>((int64_t)M * 16);
-    static const int gn_fold = getenv("SVG_GN_FOLD") ? atoi(getenv("SVG_GN_FOLD")) : 1;
-    if (gn_fold && xa.st.valid() && b.proj_in_f32) {
+    if (xa.st.valid() && b.proj_in_f32) {
       // GroupNorm (no activation) -> proj_in: the normalisation is folded into per-sample weights, so the normalised tensor
       // is never written: h_b = x_b (W diag(gamma rstd_b))^T + (bias + W (beta - mean_b rstd_b gamma)), one batched GEMM
       ctx->arena.push();
@@ -433,25 +411,18 @@ struct UnetRun {
       LinearOpts o; o.ln = &le;
       linear(ctx, n0, C, b.proj_in, h, C, M, s, o);
     }
-    // LayerNorms: folded into the consuming projections (row statistics only) unless SVG_LN_FOLD=0
-    const bool fold = b.qk1.ln_s != nullptr;
-    h16* ln = fold ? nullptr : ctx->arena.get<h16>(P * C);
-    float* rs = fold ? ctx->arena.get<float>(M + 8) : nullptr;
-    float* rm = fold ? ctx->arena.get<float>(M + 8) : nullptr;
+    // LayerNorms: folded into the consuming projections (load_xf), only the row statistics are computed here
+    float* rs = ctx->arena.get<float>(M + 8);
+    float* rm = ctx->arena.get<float>(M + 8);
     LinearOpts stat; stat.ln_rs = rs; stat.ln_rm = rm;       // a LayerNorm-folded projection: the current row statistics
-    auto norm = [&](const h16* src, const NormW& n) -> const h16* {
-      if (fold) {
-        if (le.tiles > 0) ln_finish(ctx, le.buf, le.tiles, rs, rm, M, C, 1e-5f, s);   // src's producer left its row partials
-        else ln_stats(ctx, src, rs, rm, M, C, 1e-5f, s);
-        le.tiles = 0;
-        return src;
-      }
-      layernorm(ctx, src, n.g, n.b, ln, M, C, 1e-5f, s);
-      return ln;
+    auto row_stats = [&](const h16* src) {
+      if (le.tiles > 0) ln_finish(ctx, le.buf, le.tiles, rs, rm, M, C, 1e-5f, s);   // src's producer left its row partials
+      else ln_stats(ctx, src, rs, rm, M, C, 1e-5f, s);
+      le.tiles = 0;
     };
     h16* ao = ctx->arena.get<h16>(P * C);
     // ---- self-attention
-    const h16* a1 = norm(h, b.ln1);
+    row_stats(h);
     {
       ctx->arena.push();
       const int HWp = (int)align_up(HW, 8);
@@ -462,26 +433,25 @@ struct UnetRun {
         // q | k | V^T in ONE weight-stationary launch: the V column groups write V^T directly (GemmArgs::vt_out)
         GemmArgs g;
         g.ln_rs = rs; g.ln_rm = rm; g.ln_s = b.qkv1.ln_s;
-        g.A = a1; g.lda = C; g.Wt = b.qkv1.w; g.ldb = C; g.M = M; g.N = 3 * C; g.K = C; g.n_valid = 3 * C;
+        g.A = h; g.lda = C; g.Wt = b.qkv1.w; g.ldb = C; g.M = M; g.N = 3 * C; g.K = C; g.n_valid = 3 * C;
         g.bias = b.qkv1.b; g.C = qk; g.ldc = 2 * C;
         g.vt_n0 = 2 * C; g.vt_rows = HW; g.vt_ld = HWp; g.vt_bs = (int64_t)C * HWp;
         vt = ctx->arena.get<h16>((int64_t)N * C * HWp);
         g.vt_out = vt;
-        static const int qkv_env = getenv("SVG_QKV_FUSED") ? atoi(getenv("SVG_QKV_FUSED")) : 1;
         const GemmPlan plan = gemm_plan(g);      // V^T out of the epilogue: the weight-stationary kernel only
-        if (qkv_env && plan.family == GF_WS) { gemm_auto(ctx, g, plan, s, PK_GEMM); fused = true; }
+        if (plan.family == GF_WS) { gemm_auto(ctx, g, plan, s, PK_GEMM); fused = true; }
       }
       if (!fused) {
-        linear(ctx, a1, C, b.qk1, qk, 2 * C, M, s, stat);
+        linear(ctx, h, C, b.qk1, qk, 2 * C, M, s, stat);
         vt = ctx->arena.get<h16>((int64_t)N * C * HWp);
-        vt_proj_into(ctx, b.v1, a1, N, HW, HWp, C, vt, s, rs, rm);
+        vt_proj_into(ctx, b.v1, h, N, HW, HWp, C, vt, s, rs, rm);
       }
       attn_core(qk, 2 * C, qk + C, 2 * C, (int64_t)HW * 2 * C, vt, HWp, (int64_t)C * HWp, ao, C, HW, HW);
       ctx->arena.pop();
     }
     h16* h1 = ctx->arena.get<h16>(P * C);
     // C = 320: to_q + attention over the context + to_out + residual in ONE launch (xattn_fused.hip), LayerNorm 2 from the rows it holds
-    const bool xa_one = fold && b.xq && xattn_fused_supported(C, m->heads, M, HW, L);
+    const bool xa_one = b.xq && xattn_fused_supported(C, m->heads, M, HW, L);
     // ... and, CHAIN form, the self-attention's output projection + residual in front of it: h1 is never written
     const bool xa_chain = xa_one && xattn_chain_enabled() && b.o1.K == C && b.o1.N == C;
     LinearOpts o1, o2;     // the attention output projections: + residual, leaving the row partials of the next LayerNorm
@@ -489,11 +459,11 @@ struct UnetRun {
     if (!xa_chain) linear(ctx, ao, C, b.o1, h1, C, M, s, o1);
     h16* h2 = ctx->arena.get<h16>(P * C);
     // ---- cross-attention
-    const h16* a2 = xa_one ? h1 : norm(h1, b.ln2);
+    if (!xa_one) row_stats(h1);
     {
       ctx->arena.push();
       h16* q = xa_one ? nullptr : ctx->arena.get<h16>(P * C);
-      if (!xa_one) linear(ctx, a2, C, b.q2, q, C, M, s, stat);
+      if (!xa_one) linear(ctx, h1, C, b.q2, q, C, M, s, stat);
       const int idx = xf_idx++;
       const int64_t kn = (int64_t)N * L * C, vn = (int64_t)N * C * Lp;
       // the cache lives outside the arena (it survives the call); plan mode sizes it too, so the first real step allocates nothing
@@ -527,28 +497,23 @@ struct UnetRun {
     o2.residual = h1; o2.ldr = C; o2.ln = &le;
     if (!xa_one) linear(ctx, ao, C, b.o2, h2, C, M, s, o2);
     // ---- GEGLU feed-forward
-    const bool ff_one = fold && b.ff2p && ff_fused_supported(C, M);
-    const h16* a3 = ff_one ? h2 : norm(h2, b.ln3);     // the fused feed-forward takes its LayerNorm statistics from the rows it holds
+    const bool ff_one = b.ff2p && ff_fused_supported(C, M);
+    if (!ff_one) row_stats(h2);                 // the fused feed-forward takes its LayerNorm statistics from the rows it holds
     {
-      // The GEGLU intermediate is M x 4C (293 MB at 28 clips x 64 x 64 x 1280): written by ff1 and read back by ff2.  Run
-      // the pair over row chunks whose intermediate fits the 256 MiB Infinity Cache (with the other stream group's share):
-      // the same chunk-sized buffer is rewritten per chunk, so ff2 reads it from the cache instead of HBM.
       if (ff_one) {
         // ff1 -> GEGLU -> ff2 in one kernel: the M x 4C intermediate never leaves the CU (h is free again: reused as h3)
-        ff_fused(ctx, h2, C, b.ff1.w, b.ff1.b, b.ff1.ln_s, nullptr, nullptr, b.ff2p, b.ff2.b, h2, C, h, C, M, s);
+        ff_fused(ctx, h2, C, b.ff1.w, b.ff1.b, b.ff1.ln_s, b.ff2p, b.ff2.b, h2, C, h, C, M, s);
       } else {
-      ctx->arena.push();
-      const int rows = ff_chunk_rows(M, C);
-      h16* g = ctx->arena.get<h16>((int64_t)std::min(rows, M) * 4 * C);
-      for (int m0 = 0; m0 < M; m0 += rows) {
-        const int mc = std::min(rows, M - m0);
+        // two GEMMs through the M x 4C GEGLU intermediate (the option of running the pair over row chunks that fit the Infinity Cache
+        // was never the default and is removed)
+        ctx->arena.push();
+        h16* g = ctx->arena.get<h16>((int64_t)M * 4 * C);
         LinearOpts f1, f2;
-        f1.act = ACT_GEGLU; f1.ln_rs = rs ? rs + m0 : nullptr; f1.ln_rm = rm ? rm + m0 : nullptr;
-        f2.residual = h2 + (int64_t)m0 * C; f2.ldr = C;
-        linear(ctx, a3 + (int64_t)m0 * C, C, b.ff1, g, 4 * C, mc, s, f1);
-        linear(ctx, g, 4 * C, b.ff2, h + (int64_t)m0 * C, C, mc, s, f2);   // h is free again: reuse as h3
-      }
-      ctx->arena.pop();
+        f1.act = ACT_GEGLU; f1.ln_rs = rs; f1.ln_rm = rm;
+        f2.residual = h2; f2.ldr = C;
+        linear(ctx, h2, C, b.ff1, g, 4 * C, M, s, f1);
+        linear(ctx, g, 4 * C, b.ff2, h, C, M, s, f2);   // h is free again: reuse as h3
+        ctx->arena.pop();
       }
     }
     LinearOpts po; po.residual = x; po.ldr = C; po.emit = &eo; po.rows_per_sample = HW;

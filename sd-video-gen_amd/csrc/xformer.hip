@@ -452,8 +452,6 @@ static void xf_gemm_v2(svg_ctx* ctx, const float* X, const float* W, const float
   // enough workgroups for two per CU while each keeps >= 8 steps (two rounds of its 4-deep pipeline)
   int ksplit = 1;
   while (nb * ksplit < 512 && steps / (ksplit * 2) >= 8 && ksplit < 16) ksplit *= 2;
-  static const int ks_env = getenv("SVG_XF_KSPLIT") ? atoi(getenv("SVG_XF_KSPLIT")) : 0;
-  if (ks_env > 0) ksplit = ks_env;
   float* slabs = nullptr;
   if (ksplit > 1) { ctx->arena.push(); slabs = ctx->arena.get<float>((int64_t)ksplit * M * N); ctx->arena.pop(); }
   if (!SVG_LAUNCHING(ctx)) return;
@@ -487,16 +485,13 @@ void xf_gemm(svg_ctx* ctx, const float* X, const float* W, const float* bias, fl
   SVG_CHECK(M >= 1 && M <= 16 * XF_MAXMT, "xf_gemm: M=%d must be in 1..%d", M, 16 * XF_MAXMT);
   // Two forms (same-box kbench, profiles/README.md): up to 47 rows the 16-column form below (every wave streams its own K slice,
   // X straight from L2: 1.6-3.1 TB/s at 6 rows) is ahead; from 48 rows on X re-reads bound it and the column-block form (X
-  // shared through LDS) wins: 71 vs 53 TFLOP/s at 168 x 6144 x 2048.  SVG_XF_V forces one.
-  static const int ver = getenv("SVG_XF_V") ? atoi(getenv("SVG_XF_V")) : 0;
-  if (ver == 2 || (ver == 0 && M >= 48 && K >= 32)) { xf_gemm_v2(ctx, X, W, bias, Y, M, N, K, act_in, s, residual); return; }
+  // shared through LDS) wins: 71 vs 53 TFLOP/s at 168 x 6144 x 2048.
+  if (M >= 48 && K >= 32) { xf_gemm_v2(ctx, X, W, bias, Y, M, N, K, act_in, s, residual); return; }
   const int nb = cdiv(N, 16);
   // K split: enough workgroups to put >= 2 on every CU while every wave keeps >= 2 steps of 32 (its load pipeline)
   const int steps = cdiv(K, 32);
   int ksplit = 1;
   while (nb * ksplit < 512 && steps / (XF_WAVES * ksplit * 2) >= 2 && ksplit < 8) ksplit *= 2;
-  static const int ks_env = getenv("SVG_XF_KSPLIT") ? atoi(getenv("SVG_XF_KSPLIT")) : 0;
-  if (ks_env > 0) ksplit = ks_env;
   float* slabs = nullptr;
   if (ksplit > 1) { ctx->arena.push(); slabs = ctx->arena.get<float>((int64_t)ksplit * M * N); ctx->arena.pop(); }   // stream order protects it
   if (!SVG_LAUNCHING(ctx)) return;

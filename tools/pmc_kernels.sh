@@ -1,6 +1,6 @@
 # SQ counters of the kernels VERDICT r02 names (fused FF, the K = 320 projection, attention d = 40, the halo conv for reference):
 # one rocprofv3 --pmc pass per counter group (kernel-trace only), summarised per kernel by tools/pmc_kernels.py.
-#   usage (GPU box, repo root): bash tools/pmc_kernels.sh <out.json> [problem set: r03 (default) | r04 = the MX-fp8 conv and the layer-walking launch | r05 = the kernels whose epilogue / schedule changed in round 5 | r06 = gemm_pp / conv_halo shapes of the DMA-placement change: run once with SVG_PP_DMA_M=0 SVG_HALO_DMA_M=0 exported (before) and once without (after)]
+#   usage (GPU box, repo root): bash tools/pmc_kernels.sh <out.json> [problem set: r03 (default) | r04 = the MX-fp8 conv and the layer-walking launch | r05 = the kernels whose epilogue / schedule changed in round 5 | r06 = the gemm_pp / conv_halo shapes of the DMA-placement change]
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=${1:-gpurun_out/pmc_kernels.json}
 d=gpurun_out/pmck; rm -rf $d; mkdir -p $d
