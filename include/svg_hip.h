@@ -137,8 +137,13 @@ typedef struct svg_train_cfg {
 } svg_train_cfg;
 /* src (B,Ts,D_lat), tgt (B,Tt,D_lat), expected (B,Tt,D_lat) batch-first f32 (trainer.py:124-131: new_batch, new_batch[:,:-1],
  * new_batch[:,1:]); text (B,text_dim) or NULL; mask (Tt,Tt) additive or NULL.  backward = 0: eval-mode forward + criterion only;
- * 1: train mode (dropout) and the gradient of every parameter (overwriting the previous step's: zero_grad + backward).
+ * 1: train mode (dropout) and the gradient of every parameter (overwriting the previous step's: zero_grad + backward);
+ * SVG_BACKWARD_ACCUMULATE (2): as 1, but every parameter gradient is ADDED to what its slot holds (loss.backward() without
+ * zero_grad()).  The gradients are zero when the training state is created; 1 starts a new sum and 2 continues it, so the first
+ * micro-batch of an optimizer step uses 1, the following ones 2, and there is no separate zero-grad entry point.  The order of
+ * the additions inside a call is fixed: the same sequence of calls gives the same bits.  Any other non-zero value behaves as 1.
  * losses: host float[5] = {total, mse, l1, gdl, contrastive} (synchronises the stream), or NULL.  B <= 64, Ts, Tt <= 32. */
+#define SVG_BACKWARD_ACCUMULATE 2
 int svg_transformer_loss(svg_ctx* ctx, const svg_train_cfg* cfg, const float* src, const float* tgt, const float* expected,
                          const float* text, int B, int Ts, int Tt, const float* mask, int backward, float* losses, void* stream);
 /* The train-mode forward on its own (models/transformer.py:47-68 with model.train(): dropout active, same sites and masks as
@@ -148,6 +153,27 @@ int svg_transformer_forward_train(svg_ctx* ctx, const float* src, const float* t
 /* torch.optim.Adam(lr, betas=(beta1, beta2), eps) step on the gradients of the last svg_transformer_loss(backward=1)
  * (trainer.py:365: optim.Adam(model.parameters(), lr=lr) -> betas (0.9, 0.999), eps 1e-8, no weight decay). */
 int svg_transformer_adam_step(svg_ctx* ctx, float lr, float beta1, float beta2, float eps, void* stream);
+/* 2-norm over ALL parameter gradients as they stand (the total_norm of torch.nn.utils.clip_grad_norm_(params, ., 2.0)), reduced on
+ * the device: squares and sums in double, in a fixed order (same gradients -> same double).  out: host double; synchronises the
+ * stream like `losses` does. */
+int svg_transformer_grad_norm(svg_ctx* ctx, double* out, void* stream);
+/* The optimizer step with what a Transformer of this size is usually trained with.  With g' = grad_scale * g:
+ *   total = ||g'||_2 over all parameters;  coef = min(1, max_grad_norm / (total + 1e-6))  (clip_grad_norm_), the update sees coef * g';
+ *   then torch.optim.AdamW (decoupled = 1: p *= 1 - lr * weight_decay, then Adam) or torch.optim.Adam(weight_decay) (decoupled = 0:
+ *   g += weight_decay * p), with the arithmetic of svg_transformer_adam_step.
+ * Unlike torch's in-place clip the STORED gradients are not modified: svg_transformer_tensor(SVG_TENSOR_GRAD) afterwards still returns
+ * the unscaled, unclipped sum.  grad_norm_out (host double, may be NULL) receives `total` and synchronises the stream; with NULL the
+ * call only enqueues (the norm never visits the host: the update reads it from device memory).  Advances the same step counter as
+ * svg_transformer_adam_step.  SVG_ERR_INVALID: no gradients yet, weight_decay < 0, max_grad_norm < 0, grad_scale <= 0, or the
+ * hyper-parameter ranges svg_transformer_adam_step rejects. */
+typedef struct svg_optim_cfg {
+  float lr, beta1, beta2, eps;
+  float weight_decay;     /* 0: none */
+  int   decoupled;        /* 1: AdamW (p *= 1 - lr*wd, then Adam); 0: torch.optim.Adam(weight_decay=wd) (g += wd*p) */
+  float max_grad_norm;    /* 0: no clipping; else torch.nn.utils.clip_grad_norm_(params, max_grad_norm, 2.0) */
+  float grad_scale;       /* gradients are multiplied by this first (1/k after k accumulated micro-batches = loss/k in torch); 1: none */
+} svg_optim_cfg;
+int svg_transformer_optim_step(svg_ctx* ctx, const svg_optim_cfg* cfg, double* grad_norm_out, void* stream);
 /* copies a parameter / its gradient / its Adam moments out (host or device `out`, numel floats; state_dict key names):
  * what torch.save(model.state_dict()) at trainer.py:469-480 needs after steps taken in the library. */
 enum svg_tensor_kind { SVG_TENSOR_PARAM = 0, SVG_TENSOR_GRAD = 1, SVG_TENSOR_EXP_AVG = 2, SVG_TENSOR_EXP_AVG_SQ = 3 };

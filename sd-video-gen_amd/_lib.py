@@ -29,6 +29,7 @@ _lib = None
 _vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
 
 SVG_TENSOR_PARAM, SVG_TENSOR_GRAD, SVG_TENSOR_EXP_AVG, SVG_TENSOR_EXP_AVG_SQ = 0, 1, 2, 3   # enum svg_tensor_kind
+SVG_BACKWARD_ACCUMULATE = 2     # svg_transformer_loss(backward=): add the gradients to what the slots hold
 
 
 class TrainCfg(C.Structure):
@@ -36,6 +37,12 @@ class TrainCfg(C.Structure):
     _fields_ = [("frames_to_predict", _i), ("feat_h", _i), ("feat_w", _i),
                 ("w_mse", _f), ("w_l1", _f), ("w_gdl", _f), ("gdl_alpha", _f), ("w_contrastive", _f), ("temperature", _f),
                 ("dropout_p", _f), ("seed", C.c_uint64)]
+
+
+class OptimCfg(C.Structure):
+    """struct svg_optim_cfg (include/svg_hip.h)."""
+    _fields_ = [("lr", _f), ("beta1", _f), ("beta2", _f), ("eps", _f), ("weight_decay", _f), ("decoupled", _i), ("max_grad_norm", _f),
+                ("grad_scale", _f)]
 
 
 class GemmDesc(C.Structure):
@@ -85,6 +92,8 @@ SIGNATURES = {
     "svg_transformer_loss": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp],
     "svg_transformer_forward_train": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _f, C.c_uint64, _vp, _vp],
     "svg_transformer_adam_step": [_vp, _f, _f, _f, _f, _vp],
+    "svg_transformer_grad_norm": [_vp, C.POINTER(C.c_double), _vp],
+    "svg_transformer_optim_step": [_vp, C.POINTER(OptimCfg), C.POINTER(C.c_double), _vp],
     "svg_transformer_tensor": [_vp, _i, C.c_char_p, _vp, _i64, _vp],
     "svg_clip_text_forward": [_vp, _vp, _i, _i, _vp, _vp],
     "svg_minilm_encode": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
@@ -378,7 +387,8 @@ class Context:
 
     # ---- training step of the latent Transformer ---------------------------------------------------
     def transformer_loss(self, cfg, src, tgt, expected, mask=None, text=None, backward=True, read_losses=True):
-        """-> dict(total, mse, l1, gdl, contrastive).  backward=True: train mode, gradients left in the library.
+        """-> dict(total, mse, l1, gdl, contrastive).  backward=True (1): train mode, gradients left in the library;
+        SVG_BACKWARD_ACCUMULATE (2): the same, added to the gradients the library already holds.
         read_losses=False: nothing is copied back and the stream is not synchronised (returns None)."""
         B, Ts, _ = src.shape
         Tt = tgt.shape[1]
@@ -390,7 +400,7 @@ class Context:
         text = text.to(device=src.device, dtype=torch.float32).contiguous() if text is not None else None
         out = (_f * 5)() if read_losses else None
         self.check(self.lib.svg_transformer_loss(self.h, C.byref(cfg), _ptr(src), _ptr(tgt), _ptr(expected), _ptr(text), B, Ts, Tt,
-                                                 _ptr(mask), int(bool(backward)), out, _stream()), "svg_transformer_loss")
+                                                 _ptr(mask), int(backward), out, _stream()), "svg_transformer_loss")
         if out is None:
             return None
         return dict(zip(("total", "mse", "l1", "gdl", "contrastive"), [float(v) for v in out]))
@@ -410,6 +420,20 @@ class Context:
 
     def transformer_adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8):
         self.check(self.lib.svg_transformer_adam_step(self.h, lr, betas[0], betas[1], eps, _stream()), "svg_transformer_adam_step")
+
+    def transformer_grad_norm(self):
+        """2-norm over all parameter gradients as they stand, reduced on the device in double (synchronises the stream)"""
+        out = C.c_double()
+        self.check(self.lib.svg_transformer_grad_norm(self.h, C.byref(out), _stream()), "svg_transformer_grad_norm")
+        return out.value
+
+    def transformer_optim_step(self, cfg, read_norm=False):
+        """svg_transformer_optim_step with an OptimCfg.  read_norm: -> the pre-clip norm of the scaled gradients (synchronises);
+        otherwise the call only enqueues and returns None"""
+        out = C.c_double() if read_norm else None
+        self.check(self.lib.svg_transformer_optim_step(self.h, C.byref(cfg), C.byref(out) if read_norm else None, _stream()),
+                   "svg_transformer_optim_step")
+        return out.value if read_norm else None
 
     def transformer_tensor(self, name, like, kind=SVG_TENSOR_PARAM):
         """Copy of parameter `name` (or its gradient / Adam moment) shaped like `like`, on the CPU."""

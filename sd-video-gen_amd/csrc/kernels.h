@@ -347,7 +347,7 @@ void xf_relu_drop(const float* h, float* r, int64_t n, const XfDrop d, hipStream
 void xf_add_ln_train(const float* x, const float* r, const XfDrop dr, const float* g, const float* b, float* y, float* xhat, float* rstd, int M,
                      int d, float eps, hipStream_t s);
 void xf_ln_bwd(const float* dy, const float* xhat, const float* rstd, const float* g, float* dz, float* dz_drop, const XfDrop dr, float* dgamma,
-               float* dbeta, int M, int d, hipStream_t s);
+               float* dbeta, int M, int d, int accumulate, hipStream_t s);
 void xf_embed_post_train(const float* emb, const float* pe, const int32_t* pe_row, const float* text, int d_txt, float* y, int B, int T, int d,
                          float scale, const XfDrop dr, hipStream_t s);
 void xf_embed_post_bwd(const float* dy, float* de, int B, int T, int d, int d_img, float scale, const XfDrop dr, hipStream_t s);
@@ -360,6 +360,11 @@ void xf_criterion(const float* pred, const float* expected, float* dpred, float*
                   int fh, int fw, float w_mse, float w_l1, float w_gdl, float alpha, float w_nce, float temperature, hipStream_t s);
 void xf_adam(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chunks, float lr, float beta1, float beta2, float eps, int step,
              hipStream_t s);
+// norm[0] = 2-norm of all gradients of the chunk table, in double; part: n_chunks doubles of scratch
+void xf_grad_norm(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chunks, double* part, double* norm, hipStream_t s);
+// Adam / AdamW on g * grad_scale * min(1, max_norm / (grad_scale * norm[0] + 1e-6)) (norm == nullptr: no clipping); g is not written
+void xf_adamw(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chunks, float lr, float beta1, float beta2, float eps, int step,
+              float weight_decay, int decoupled, float grad_scale, float max_norm, const double* norm, hipStream_t s);
 // seq-first MHA core on packed projections: q (Tq,B,ldq) k,v (Tk,B,ldk) -> o (Tq,B,d); mask (Tq,Tk) or null;
 // kpad (B,Tk) or null: additive key-padding bias per batch row
 void xf_attention(const float* q, int ldq, const float* k, const float* v, int ldk, const float* mask,

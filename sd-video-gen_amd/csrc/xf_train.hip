@@ -287,8 +287,9 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const float* __restrict__ d
 
 // dgamma[c] = sum_rows dy xhat, dbeta[c] = sum_rows dy: a block owns 64 columns, its 4 waves take the rows m = w mod 4 (ascending)
 // and are added in wave order
+// accumulate: the sums are added to what dg / db hold (old value first) instead of replacing it
 __global__ void __launch_bounds__(256) ln_bwd_params_kernel(const float* __restrict__ dy, const float* __restrict__ xhat, float* __restrict__ dg,
-                                                             float* __restrict__ db, int M, int d) {
+                                                             float* __restrict__ db, int M, int d, int accumulate) {
   __shared__ float red[2][4][64];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + lane;
@@ -298,8 +299,10 @@ __global__ void __launch_bounds__(256) ln_bwd_params_kernel(const float* __restr
   red[0][wid][lane] = sg; red[1][wid][lane] = sb;
   __syncthreads();
   if (wid == 0 && c < d) {
-    dg[c] = ((red[0][0][lane] + red[0][1][lane]) + red[0][2][lane]) + red[0][3][lane];
-    db[c] = ((red[1][0][lane] + red[1][1][lane]) + red[1][2][lane]) + red[1][3][lane];
+    const float g = ((red[0][0][lane] + red[0][1][lane]) + red[0][2][lane]) + red[0][3][lane];
+    const float b = ((red[1][0][lane] + red[1][1][lane]) + red[1][2][lane]) + red[1][3][lane];
+    dg[c] = accumulate ? dg[c] + g : g;
+    db[c] = accumulate ? db[c] + b : b;
   }
 }
 
@@ -590,6 +593,91 @@ __global__ void __launch_bounds__(256) adam_kernel(const XfAdamTensor* __restric
   }
 }
 
+// ---- global 2-norm of the gradients: one block per Adam chunk, squares and sums in double ------------------------------------
+// The pass is a read-only HBM stream (4 bytes per parameter), so the double adds hide under the loads and the result carries no
+// f32 summation error.  Fixed order everywhere: a lane adds its float4s ascending (x, y, z, w), the wave folds by xor 32, 16, .. 1,
+// wave sums are added 0..3.  A chunk starts at a multiple of 65 536 elements of a hipMalloc'd gradient: float4 loads are aligned;
+// the at most 3 elements behind the last whole float4 go to lane 0.
+__global__ void __launch_bounds__(256) grad_sqsum_kernel(const XfAdamTensor* __restrict__ tens, const XfAdamChunk* __restrict__ chunks,
+                                                          double* __restrict__ part) {
+  __shared__ double red[4];
+  const XfAdamChunk ch = chunks[blockIdx.x];
+  const float* __restrict__ g = tens[ch.ten].g + ch.off;
+  const int n4 = ch.n >> 2;
+  const f32x4* __restrict__ g4 = (const f32x4*)g;
+  double acc = 0.0;
+  int i = threadIdx.x;
+  for (; i + 768 < n4; i += 1024) {                          // four loads in flight per lane
+    const f32x4 a = g4[i], b = g4[i + 256], c = g4[i + 512], e = g4[i + 768];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc += (double)a[j] * (double)a[j];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc += (double)b[j] * (double)b[j];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc += (double)c[j] * (double)c[j];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc += (double)e[j] * (double)e[j];
+  }
+  for (; i < n4; i += 256) {
+    const f32x4 a = g4[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc += (double)a[j] * (double)a[j];
+  }
+  if (threadIdx.x == 0)
+    for (int k = 4 * n4; k < ch.n; ++k) acc += (double)g[k] * (double)g[k];
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// norm[0] = sqrt(sum of the partials): thread t adds its contiguous run of partials ascending, thread 0 adds the 256 runs ascending
+__global__ void __launch_bounds__(256) grad_norm_finish_kernel(const double* __restrict__ part, int n, double* __restrict__ norm) {
+  __shared__ double red[256];
+  const int per = (n + 255) / 256;
+  const int lo = threadIdx.x * per, hi = min(n, lo + per);
+  double acc = 0.0;
+  for (int i = lo; i < hi; ++i) acc += part[i];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int i = 0; i < 256; ++i) t += red[i];
+    norm[0] = sqrt(t);
+  }
+}
+
+// ---- Adam / AdamW on scaled, clipped gradients ------------------------------------------------------------------------------
+// g' = g * s with s = grad_scale * min(1, max_norm / (grad_scale * norm + 1e-6)) (torch.nn.utils.clip_grad_norm_; norm == nullptr:
+// s = grad_scale), read from the device double the norm pass left: no host round trip.  The stored gradient is not written.
+// decay_mul != 1: p *= decay_mul first (AdamW, decay_mul = 1 - lr * wd);  wd_l2 != 0: g' += wd_l2 * p (Adam(weight_decay)).
+// From there on the statements of adam_kernel, so that s == 1 without decay gives its bits.
+__global__ void __launch_bounds__(256) adamw_kernel(const XfAdamTensor* __restrict__ tens, const XfAdamChunk* __restrict__ chunks, float lr, float beta1,
+                                                     float beta2, float eps, float bc1, float bc2_sqrt, float decay_mul, float wd_l2,
+                                                     float grad_scale, float max_norm, const double* __restrict__ norm) {
+  const XfAdamChunk ch = chunks[blockIdx.x];
+  const XfAdamTensor tn = tens[ch.ten];
+  const float step_size = lr / bc1;
+  float s = grad_scale;
+  if (norm) {
+    const double total = (double)grad_scale * norm[0];
+    s = (float)((double)grad_scale * fmin(1.0, (double)max_norm / (total + 1e-6)));
+  }
+  const bool scaled = s != 1.f, decays = decay_mul != 1.f, l2 = wd_l2 != 0.f;
+  for (int64_t i = ch.off + threadIdx.x; i < ch.off + ch.n; i += 256) {
+    float g = tn.g[i];
+    float p = tn.p[i];
+    if (scaled) g = g * s;
+    if (decays) p = p * decay_mul;
+    if (l2) g = g + wd_l2 * p;
+    const float m = tn.m[i] + (g - tn.m[i]) * (1.f - beta1);              // exp_avg.lerp_(grad, 1 - beta1)
+    const float v = tn.v[i] * beta2 + (1.f - beta2) * g * g;              // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    tn.m[i] = m; tn.v[i] = v;
+    const float denom = sqrtf(v) / bc2_sqrt + eps;
+    tn.p[i] = p - step_size * (m / denom);
+  }
+}
+
 constexpr int kAttnTrainLds = 150 * 1024;   // + 2 x 4.3 KiB of static score tiles: under the 160 KiB of a CU
 
 int grid_for(int64_t n, int per_block) { return (int)std::min<int64_t>(4096, (n + per_block - 1) / per_block); }
@@ -656,10 +744,10 @@ void xf_add_ln_train(const float* x, const float* r, const XfDrop dr, const floa
 }
 
 void xf_ln_bwd(const float* dy, const float* xhat, const float* rstd, const float* g, float* dz, float* dz_drop, const XfDrop dr, float* dgamma,
-               float* dbeta, int M, int d, hipStream_t s) {
+               float* dbeta, int M, int d, int accumulate, hipStream_t s) {
   SVG_CHECK(d <= 3072, "xf_ln_bwd: d %d > 3072", d);
   hipLaunchKernelGGL(ln_bwd_kernel, dim3(M), dim3(256), 0, s, dy, xhat, rstd, g, dz, dz_drop, dr, d);
-  hipLaunchKernelGGL(ln_bwd_params_kernel, dim3(cdiv(d, 64)), dim3(256), 0, s, dy, xhat, dgamma, dbeta, M, d);
+  hipLaunchKernelGGL(ln_bwd_params_kernel, dim3(cdiv(d, 64)), dim3(256), 0, s, dy, xhat, dgamma, dbeta, M, d, accumulate);
   check_launch("xf_ln_bwd");
 }
 
@@ -713,4 +801,22 @@ void xf_adam(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chunks, 
   const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
   hipLaunchKernelGGL(adam_kernel, dim3(n_chunks), dim3(256), 0, s, tens, chunks, lr, beta1, beta2, eps, bc1, bc2_sqrt);
   check_launch("xf_adam");
+}
+
+void xf_grad_norm(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chunks, double* part, double* norm, hipStream_t s) {
+  hipLaunchKernelGGL(grad_sqsum_kernel, dim3(n_chunks), dim3(256), 0, s, tens, chunks, part);
+  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, s, part, n_chunks, norm);
+  check_launch("xf_grad_norm");
+}
+
+void xf_adamw(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chunks, float lr, float beta1, float beta2, float eps, int step,
+              float weight_decay, int decoupled, float grad_scale, float max_norm, const double* norm, hipStream_t s) {
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));          // as xf_adam
+  const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+  // torch.optim.AdamW: param.mul_(1 - lr * weight_decay) with the factor evaluated in double
+  const float decay_mul = decoupled ? (float)(1.0 - (double)lr * (double)weight_decay) : 1.f;
+  const float wd_l2 = decoupled ? 0.f : weight_decay;
+  hipLaunchKernelGGL(adamw_kernel, dim3(n_chunks), dim3(256), 0, s, tens, chunks, lr, beta1, beta2, eps, bc1, bc2_sqrt, decay_mul, wd_l2, grad_scale,
+                     max_norm, norm);
+  check_launch("xf_adamw");
 }

@@ -17,6 +17,10 @@ struct XfTrain {
   XfAdamChunk* d_chunks = nullptr;
   int n_chunks = 0;
   int step = 0;
+  bool has_grads = false;        // a backward pass has been enqueued since the state was created
+  double* d_norm_part = nullptr; // [n_chunks] per-chunk sums of squares of the gradient-norm pass
+  double* d_norm = nullptr;      // the global gradient 2-norm, where the clipped update reads it
+  double* h_norm = nullptr;      // pinned mirror
   float* d_losses = nullptr;     // [5]
   float* h_losses = nullptr;     // pinned mirror: a device-to-pageable copy goes through the runtime's staging path and its host thread
   // One plan per call signature (shapes + every criterion / dropout parameter except the seed): the workspace high-water mark and,
@@ -51,6 +55,7 @@ struct XfTrain {
     for (void* p : bufs) hipFree(p);
     if (h_losses) hipHostFree(h_losses);
     if (h_seed) hipHostFree(h_seed);
+    if (h_norm) hipHostFree(h_norm);
     for (auto e : seed_ev) if (e) hipEventDestroy(e);
     if (ws_buf.p) hipFree(ws_buf.p);
   }
@@ -76,6 +81,7 @@ struct DecTape { MhaTape sa; LnTape n1; MhaTape ca; LnTape n2; FfnTape ff; LnTap
 
 struct Run {
   svg_ctx* ctx; XfModel* m; XfTrain* tr; hipStream_t s; int B; const uint64_t* seed; float p; bool grads;
+  bool acc;      // SVG_BACKWARD_ACCUMULATE: every gradient store adds to its slot
   const float* text = nullptr;
   uint32_t site = 0;
   bool go() const { return SVG_LAUNCHING(ctx); }
@@ -99,7 +105,7 @@ struct Run {
     if (!go()) return;
     // (dW on a side stream beside the dX chain — a fork / join per linear layer inside the captured step — was bit-equal and 6-9 %
     // slower per step; removed, DESIGN.md "Training")
-    xf_gemm_tn(dy, t.N, t.x, t.K, G(t.w) + t.woff, G(t.b) + t.boff, t.M, t.N, t.K, accumulate, s);
+    xf_gemm_tn(dy, t.N, t.x, t.K, G(t.w) + t.woff, G(t.b) + t.boff, t.M, t.N, t.K, accumulate || acc, s);
     if (dx) xf_gemm_nn(dy, t.N, W(t.w) + t.woff, slabs, dx, t.M, t.N, t.K, gate, gate_scale, add, s);
   }
 
@@ -121,7 +127,7 @@ struct Run {
     float* dzd = nullptr;
     if (dz_drop) { dzd = t.dr.p > 0.f ? get<float>((int64_t)t.M * d) : dz; *dz_drop = dzd; }
     if (go())
-      xf_ln_bwd(dy, t.xhat, t.rstd, W(t.p + "weight"), dz, dzd == dz ? nullptr : dzd, t.dr, G(t.p + "weight"), G(t.p + "bias"), t.M, d, s);
+      xf_ln_bwd(dy, t.xhat, t.rstd, W(t.p + "weight"), dz, dzd == dz ? nullptr : dzd, t.dr, G(t.p + "weight"), G(t.p + "bias"), t.M, d, acc, s);
     return dz;
   }
 
@@ -223,6 +229,9 @@ void ensure_train(svg_ctx* ctx, XfModel* m) {
   tr->d_tens = (XfAdamTensor*)tr->dalloc(tens.size() * sizeof(XfAdamTensor));
   tr->d_chunks = (XfAdamChunk*)tr->dalloc(chunks.size() * sizeof(XfAdamChunk));
   tr->d_losses = (float*)tr->dalloc(5 * sizeof(float));
+  tr->d_norm_part = (double*)tr->dalloc(chunks.size() * sizeof(double));
+  tr->d_norm = (double*)tr->dalloc(sizeof(double));
+  HIP_OK(hipHostMalloc((void**)&tr->h_norm, sizeof(double), hipHostMallocDefault));
   HIP_OK(hipHostMalloc((void**)&tr->h_losses, 5 * sizeof(float), hipHostMallocDefault));
   tr->d_seed = (uint64_t*)tr->dalloc(sizeof(uint64_t));
   HIP_OK(hipHostMalloc((void**)&tr->h_seed, 16 * sizeof(uint64_t), hipHostMallocDefault));
@@ -247,9 +256,10 @@ void loss_pass(svg_ctx* ctx, XfModel* m, const svg_train_cfg& cfg, const float* 
   }
   ensure_train(ctx, m);
   XfTrain* tr = m->train;
+  if (expected && backward) tr->has_grads = true;
   const int d = m->d_model, Ms = Ts * B, Mt = Tt * B;
   auto body = [&](const float* src, const float* tgt, const float* expected, const float* text, const float* mask) {
-    Run r{ctx, m, tr, s, B, tr->d_seed, backward ? cfg.dropout_p : 0.f, backward != 0};
+    Run r{ctx, m, tr, s, B, tr->d_seed, backward ? cfg.dropout_p : 0.f, backward != 0, backward == SVG_BACKWARD_ACCUMULATE};
     r.text = text;
     LinTape e_src, e_tgt, l_out;
     XfDrop d_src, d_tgt;
@@ -419,7 +429,9 @@ extern "C" int svg_transformer_loss(svg_ctx* ctx, const svg_train_cfg* cfg, cons
   try {
     SVG_CHECK(ctx && ctx->xf, "transformer: model not configured");
     SVG_CHECK(cfg && src && tgt && expected, "svg_transformer_loss: null argument");
-    loss_pass(ctx, ctx->xf, *cfg, src, tgt, expected, text, B, Ts, Tt, mask, backward, losses, (hipStream_t)stream);
+    // 0, 1 or SVG_BACKWARD_ACCUMULATE: the plan (and its captured graph) is keyed on the normalised mode
+    const int mode = backward == 0 ? 0 : (backward == SVG_BACKWARD_ACCUMULATE ? SVG_BACKWARD_ACCUMULATE : 1);
+    loss_pass(ctx, ctx->xf, *cfg, src, tgt, expected, text, B, Ts, Tt, mask, mode, losses, (hipStream_t)stream);
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }
@@ -444,6 +456,48 @@ extern "C" int svg_transformer_adam_step(svg_ctx* ctx, float lr, float beta1, fl
     XfTrain* tr = ctx->xf->train;
     tr->step += 1;
     xf_adam(tr->d_tens, tr->d_chunks, tr->n_chunks, lr, beta1, beta2, eps, tr->step, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+namespace {
+// enqueues the norm pass; host != nullptr: reads the norm back (synchronises)
+void grad_norm_pass(XfTrain* tr, double* host, hipStream_t s) {
+  xf_grad_norm(tr->d_tens, tr->d_chunks, tr->n_chunks, tr->d_norm_part, tr->d_norm, s);
+  if (!host) return;
+  HIP_OK(hipMemcpyAsync(tr->h_norm, tr->d_norm, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  *host = *tr->h_norm;
+}
+}  // namespace
+
+extern "C" int svg_transformer_grad_norm(svg_ctx* ctx, double* out, void* stream) {
+  try {
+    SVG_CHECK(ctx && ctx->xf && out, "svg_transformer_grad_norm: null argument");
+    SVG_CHECK(ctx->xf->train && ctx->xf->train->has_grads, "gradient norm: no gradients yet (call svg_transformer_loss with backward=1 first)");
+    grad_norm_pass(ctx->xf->train, out, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+extern "C" int svg_transformer_optim_step(svg_ctx* ctx, const svg_optim_cfg* cfg, double* grad_norm_out, void* stream) {
+  try {
+    SVG_CHECK(ctx && ctx->xf && cfg, "svg_transformer_optim_step: null argument");
+    SVG_CHECK(ctx->xf->train && ctx->xf->train->has_grads, "optimizer step: no gradients yet (call svg_transformer_loss with backward=1 first)");
+    SVG_CHECK(cfg->lr >= 0.f && cfg->beta1 >= 0.f && cfg->beta1 < 1.f && cfg->beta2 >= 0.f && cfg->beta2 < 1.f && cfg->eps >= 0.f,
+              "optimizer step: bad hyper-parameters");
+    SVG_CHECK(cfg->weight_decay >= 0.f, "optimizer step: weight_decay %g is negative", cfg->weight_decay);
+    SVG_CHECK(cfg->max_grad_norm >= 0.f, "optimizer step: max_grad_norm %g is negative", cfg->max_grad_norm);
+    SVG_CHECK(cfg->grad_scale > 0.f, "optimizer step: grad_scale %g is not positive", cfg->grad_scale);
+    XfTrain* tr = ctx->xf->train;
+    hipStream_t s = (hipStream_t)stream;
+    const bool clip = cfg->max_grad_norm > 0.f;
+    double norm = 0.0;
+    if (clip || grad_norm_out) grad_norm_pass(tr, grad_norm_out ? &norm : nullptr, s);
+    tr->step += 1;
+    xf_adamw(tr->d_tens, tr->d_chunks, tr->n_chunks, cfg->lr, cfg->beta1, cfg->beta2, cfg->eps, tr->step, cfg->weight_decay, cfg->decoupled != 0,
+             cfg->grad_scale, cfg->max_grad_norm, clip ? tr->d_norm : nullptr, s);
+    if (grad_norm_out) *grad_norm_out = (double)cfg->grad_scale * norm;
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }

@@ -7,15 +7,25 @@ objects the reference's loop passes around keep their roles:
 
   * ``criterion(...)``      trainer.py:91-109 — returns the loss description the library evaluates (a ``Criterion``), with the
                             same keyword arguments; the invalid use_mse + use_L1 combination prints and returns None like there
-  * ``Adam(model, lr)``     stands for ``optim.Adam(model.parameters(), lr=lr)`` (trainer.py:365): ``zero_grad()`` / ``step()``
+  * ``Adam(model, lr)``     stands for ``optim.Adam(model.parameters(), lr=lr)`` (trainer.py:365): ``zero_grad()`` / ``step()``;
+                            ``AdamW`` for ``optim.AdamW``.  Both carry what the reference's loop does not have: ``max_grad_norm``
+                            (``clip_grad_norm_`` before the step) and ``accumulate`` (micro-batches per optimizer step), see below
   * ``train_loop`` / ``validation_loop`` / ``fit``   trainer.py:111-190, :192-260, :262-273 (same arguments, same returns)
   * ``main()``              trainer.py:303-480 without wandb (absent here): hyper-parameters come from the YAML config
                             (first entry of each list, exactly the values a one-point wandb sweep would deliver), the log is
                             JSON lines on stdout; checkpoints ``./checkpoints/<config>_<index>_{train,test}.pt`` as at :469-480.
 
+Additions (all off by default; the defaults run the reference's loop step for step): ``--grad_accum K`` sums the gradients of K
+batches before one optimizer step on their mean (the loss of each micro-batch divided by the number accumulated, as
+``(loss / K).backward()`` would; a ragged tail at the end of an epoch is a step of its own), ``--clip_grad_norm X`` clips the
+global gradient 2-norm, ``--weight_decay W`` and ``--optimizer adam|adamw`` choose the decay and its form.  The norm, the clip
+and the update run in the library (``svg_transformer_optim_step``); with clipping on, the pre-clip norm is read back once per step
+and its epoch mean is logged as ``grad_norm_train``.
+
 Deviations, logging only: the per-term losses logged are those of the F predicted positions (the reference logs the GDL of all
 positions, trainer.py:176) and the contrastive term is reported directly instead of as ``loss - mse - gdl`` (:178).
 """
+import contextlib
 import json
 import os
 import time
@@ -45,16 +55,36 @@ class Criterion:
 
 
 class Adam:
-    """``optim.Adam(model.parameters(), lr=lr)`` for a model whose gradients live in the library (trainer.py:365)."""
+    """``optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)`` for a model whose gradients live in the library
+    (trainer.py:365).  max_grad_norm > 0: ``clip_grad_norm_(model.parameters(), max_grad_norm)`` in front of every step;
+    accumulate: the trainer's loop calls ``step(n)`` once per `accumulate` batches, n = the number of micro-batches summed."""
+    decoupled = False       # weight decay as an L2 term of the gradient
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0, accumulate=1):
+        if weight_decay < 0 or max_grad_norm < 0 or int(accumulate) < 1:
+            raise ValueError("weight_decay and max_grad_norm must be >= 0 and accumulate >= 1")
         self.model, self.lr, self.betas, self.eps = model, lr, betas, eps
+        self.weight_decay, self.max_grad_norm, self.accumulate = float(weight_decay), float(max_grad_norm), int(accumulate)
+        self.grad_norm = None       # pre-clip norm of the last step (clipping on only: reading it is a synchronisation)
 
     def zero_grad(self):
         pass            # svg_transformer_loss(backward=1) overwrites the gradients: zero_grad + backward in one
 
-    def step(self):
-        self.model.adam_step(self.lr, self.betas, self.eps)
+    def step(self, n=1):
+        """n: micro-batches whose gradients were summed since the last step (the update sees their mean)"""
+        if n == 1 and self.weight_decay == 0.0 and self.max_grad_norm == 0.0:
+            self.model.adam_step(self.lr, self.betas, self.eps)
+            return
+        self.grad_norm = self.model.optim_step(self.lr, self.betas, self.eps, weight_decay=self.weight_decay, decoupled=self.decoupled,
+                                               max_grad_norm=self.max_grad_norm, grad_scale=1.0 / n, read_norm=self.max_grad_norm > 0)
+
+
+class AdamW(Adam):
+    """``optim.AdamW(model.parameters(), lr=lr)``: decoupled weight decay, torch's default 1e-2."""
+    decoupled = True
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=0.0, accumulate=1):
+        super().__init__(model, lr, betas, eps, weight_decay, max_grad_norm, accumulate)
 
 
 class Trainer:
@@ -84,33 +114,66 @@ class Trainer:
         return Criterion(use_mse, use_L1, use_gdl, lambda_gdl, alpha, use_contrastive, temperature, lambda_contrastive,
                          self.config.FRAME_SIZE // 8)
 
+    def _on_stream(self):
+        """the capturable side stream of the training step (a stub model on a host without a GPU runs without one)"""
+        return torch.cuda.stream(self._stream) if self._stream is not None else contextlib.nullcontext()
+
     def _loop(self, model, loss_fn, dataloader, frames_to_predict, opt):
         sums = {"total": 0.0, "mse": 0.0, "l1": 0.0, "gdl": 0.0, "contrastive": 0.0}
         n = 0
+        train = opt is not None
+        accumulate = max(1, int(getattr(opt, "accumulate", 1))) if train else 1
+        pending = 0                    # micro-batches whose gradients are summed in the library and not yet applied
+        norms = []
         for index_list, batch in dataloader:
             new_batch = self.sd_utils.encode_batch(batch, use_sos=True)                  # trainer.py:123
             new_batch = torch.as_tensor(new_batch).to(self.device)
-            train = opt is not None
-            self.seed += 1
+            self.seed += 1                                                                 # every micro-batch: its own dropout masks
             cfg = loss_fn.cfg(frames_to_predict, model.positional_encoder.dropout_p if train else 0.0, self.seed)
-            if train:
+            if train and pending == 0:
                 opt.zero_grad()
-            torch.cuda.current_stream().synchronize()                                      # the encoded batch is ready
-            with torch.cuda.stream(self._stream):
-                terms = model.training_loss(cfg, new_batch, backward=train)                # :141-145 (+ loss.backward(), :164)
-                if train:
-                    opt.step()                                                             # :165
-            self._stream.synchronize()
+            if self._stream is not None:
+                torch.cuda.current_stream().synchronize()                                  # the encoded batch is ready
+            with self._on_stream():
+                # :141-145 (+ loss.backward(), :164); the first micro-batch of a step overwrites the gradients, the others add
+                terms = model.training_loss(cfg, new_batch, backward=(1 if pending == 0 else _lib.SVG_BACKWARD_ACCUMULATE) if train else 0)
+                pending += 1
+                if train and pending == accumulate:
+                    pending = self._step(opt, pending, norms)                              # :165
+            if self._stream is not None:
+                self._stream.synchronize()
             for k in sums:
                 sums[k] += terms[k]
             n += 1
-        return {k: v / max(n, 1) for k, v in sums.items()}
+        if train and pending:                                                              # ragged tail of the epoch: a step of its own
+            with self._on_stream():
+                pending = self._step(opt, pending, norms)
+            if self._stream is not None:
+                self._stream.synchronize()
+        avg = {k: v / max(n, 1) for k, v in sums.items()}
+        if norms:
+            avg["grad_norm"] = sum(norms) / len(norms)
+        return avg
+
+    @staticmethod
+    def _step(opt, n, norms):
+        """one optimizer step on the mean of the n accumulated micro-batch gradients -> 0 (nothing pending)"""
+        if getattr(opt, "accumulate", 1) > 1:
+            opt.step(n)
+        else:
+            opt.step()
+        if getattr(opt, "max_grad_norm", 0.0) > 0 and getattr(opt, "grad_norm", None) is not None:
+            norms.append(opt.grad_norm)
+        return 0
 
     def train_loop(self, model, opt, scheduler, loss_fn, dataloader, frames_to_predict):
         model.train()
         avg = self._loop(model, loss_fn, dataloader, frames_to_predict, opt)
-        self.log({"train_loss": avg["total"], "mse_train": avg["mse"], "L1_train": avg["l1"], "gdl_train": avg["gdl"],
-                  "contrastive_train": avg["contrastive"]})
+        rec = {"train_loss": avg["total"], "mse_train": avg["mse"], "L1_train": avg["l1"], "gdl_train": avg["gdl"],
+               "contrastive_train": avg["contrastive"]}
+        if "grad_norm" in avg:
+            rec["grad_norm_train"] = avg["grad_norm"]          # pre-clip, mean over the epoch's optimizer steps (clipping on only)
+        self.log(rec)
         return avg["total"]
 
     def validation_loop(self, model, loss_fn, dataloader, frames_to_predict):
@@ -153,6 +216,13 @@ def make_loaders(args, config, frames_per_clip, frames_to_predict, stride, batch
     return out
 
 
+def make_optimizer(args, model, lr):
+    """the optimizer the command line asks for: --optimizer adam|adamw, --weight_decay, --clip_grad_norm, --grad_accum (all defaults:
+    the reference's ``optim.Adam(model.parameters(), lr=lr)`` stepping on every batch)"""
+    return {"adam": Adam, "adamw": AdamW}[args.optimizer](model, lr=lr, weight_decay=args.weight_decay, max_grad_norm=args.clip_grad_norm,
+                                                          accumulate=args.grad_accum)
+
+
 def main():
     config, args = parse_config_args()
     frames_per_clip, frames_to_predict = _first(config.FRAMES_PER_CLIP), _first(config.FRAMES_TO_PREDICT)
@@ -166,7 +236,7 @@ def main():
     print("number of parameters: ", sum(p.numel() for p in model.parameters() if p.requires_grad))
     if args.resume:
         model.load_state_dict(torch.load("./checkpoints/" + args.old_name + ".pt", weights_only=True))
-    opt = Adam(model, lr=lr)
+    opt = make_optimizer(args, model, lr)
     loss_fn = trainer.criterion(use_mse=_first(config.USE_MSE), use_L1=_first(getattr(config, "USE_L1", False)), use_gdl=_first(config.USE_GDL),
                                 lambda_gdl=_first(config.LAMBDA_GDL), alpha=_first(config.ALPHA),
                                 use_contrastive=_first(getattr(config, "USE_CONTRASTIVE", False)),

@@ -42,7 +42,8 @@ class LibraryTraining:
     def training_loss(self, cfg, new_batch, tgt_mask=None, cls_list=None, backward=True, read_losses=True):
         """Loss of one trainer iteration on the encoded batch `new_batch` (B, T, D_lat): src = new_batch, tgt = new_batch[:, :-1],
         expected = new_batch[:, 1:] (trainers/trainer.py:124-145; trainer_text.py passes the class names as well).  backward=True
-        runs in train mode (dropout_p of `cfg`) and leaves the gradients in the library for adam_step(); False is the validation
+        (1) runs in train mode (dropout_p of `cfg`) and leaves the gradients in the library for adam_step() / optim_step(); 2 adds
+        them to the gradients already there (the second and later micro-batches of an accumulated step); False is the validation
         loss (eval mode).  -> dict of the loss terms."""
         if not new_batch.is_cuda:
             raise RuntimeError("the training step runs on the HIP library and needs CUDA tensors; there is no CPU fallback")
@@ -62,6 +63,22 @@ class LibraryTraining:
         ctx = self._sync_weights()
         ctx.transformer_adam_step(lr, betas, eps)
         self._lib_ahead = True
+
+    def optim_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, max_grad_norm=0.0, grad_scale=1.0,
+                   read_norm=False):
+        """Adam / AdamW step on grad_scale * gradients, clipped to a global 2-norm of max_grad_norm (0: off) like
+        torch.nn.utils.clip_grad_norm_; decoupled=True is torch.optim.AdamW, False torch.optim.Adam(weight_decay=).  The stored
+        gradients stay as they are.  read_norm: -> the pre-clip norm (one synchronisation); otherwise nothing leaves the device."""
+        ctx = self._sync_weights()
+        cfg = _lib.OptimCfg(lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, weight_decay=weight_decay, decoupled=int(bool(decoupled)),
+                            max_grad_norm=max_grad_norm, grad_scale=grad_scale)
+        norm = ctx.transformer_optim_step(cfg, read_norm)
+        self._lib_ahead = True
+        return norm
+
+    def grad_norm(self):
+        """global 2-norm of the gradients the library holds (what clip_grad_norm_ would return before clipping)"""
+        return self._ctx.transformer_grad_norm()
 
     def pull_weights(self):
         """copies the library's (trained) weights back into this module's parameters"""
