@@ -37,6 +37,20 @@ inline void run_planned(svg_ctx* ctx, F&& body) {
 }
 
 // ---- latent Transformer ------------------------------------------------------------------------------
+// One pointer per parameter, by role.  The model keeps its weights in this shape (XfTable<const float*>, resolved once in finalize())
+// and the trainer its gradients (XfTable<float*>): the launch paths reach a parameter through these and never by name.
+template <class P>
+struct XfTable {
+  struct Layer {
+    P in_w, in_b, out_w, out_b;          // self-attention
+    P cin_w, cin_b, cout_w, cout_b;      // decoder: attention over the encoder memory
+    P l1_w, l1_b, l2_w, l2_b;
+    P n_w[3], n_b[3];
+  };
+  std::vector<Layer> enc, dec;
+  P emb_w{}, emb_b{}, out_w{}, out_b{}, encn_w{}, encn_b{}, decn_w{}, decn_b{};
+};
+
 struct XfModel {
   WeightStore ws;
   int d_lat = 0, d_model = 0, heads = 8, enc_layers = 0, dec_layers = 0, ffn = 2048;
@@ -46,16 +60,40 @@ struct XfModel {
   int pe_d = 0;
   int32_t* iota = nullptr;
   struct XfTrain* train = nullptr;   // gradients + Adam moments (xf_trainer.cpp); dropped whenever weights are (re)loaded
-  // weight pointers by role, resolved once in finalize() (the layer-walking forward builds its stage table from them)
-  struct LayerW {
-    const float *in_w, *in_b, *out_w, *out_b;          // self-attention
-    const float *cin_w, *cin_b, *cout_w, *cout_b;      // decoder: attention over the encoder memory
-    const float *l1_w, *l1_b, *l2_w, *l2_b;
-    const float *n_w[3], *n_b[3];
-  };
-  std::vector<LayerW> enc_w, dec_w;
-  const float *emb_w = nullptr, *emb_b = nullptr, *out_w = nullptr, *out_b = nullptr, *encn_w = nullptr, *encn_b = nullptr, *decn_w = nullptr,
-              *decn_b = nullptr;
+  using LayerW = XfTable<const float*>::Layer;
+  XfTable<const float*> w;
+  // The state_dict name, the shape and the place in a table of every parameter: the one name -> role mapping.  f(name, shape, slot) is
+  // called once per parameter; finalize() checks the shape and resolves the weight with it, the trainer resolves the gradient.
+  template <class P, class F>
+  void each_param(XfTable<P>& t, F&& f) const {
+    using Shape = std::initializer_list<int64_t>;
+    const int64_t d = d_model;
+    const std::string emb = text_dim ? "project_image_embedding" : "embedding";     // transformer_text.py:60 vs transformer.py:37
+    f(emb + ".weight", Shape{d - text_dim, d_lat}, t.emb_w); f(emb + ".bias", Shape{d - text_dim}, t.emb_b);
+    f("out.weight", Shape{d_lat, d}, t.out_w); f("out.bias", Shape{d_lat}, t.out_b);
+    auto mha = [&](const std::string& p, P& in_w, P& in_b, P& out_w, P& out_b) {
+      f(p + "in_proj_weight", Shape{3 * d, d}, in_w); f(p + "in_proj_bias", Shape{3 * d}, in_b);
+      f(p + "out_proj.weight", Shape{d, d}, out_w); f(p + "out_proj.bias", Shape{d}, out_b);
+    };
+    auto stack = [&](const char* side, int n, bool dec, std::vector<typename XfTable<P>::Layer>& layers) {
+      layers.assign(n, typename XfTable<P>::Layer{});
+      for (int i = 0; i < n; ++i) {
+        const std::string p = std::string("transformer.") + side + ".layers." + std::to_string(i) + ".";
+        auto& l = layers[i];
+        mha(p + "self_attn.", l.in_w, l.in_b, l.out_w, l.out_b);
+        if (dec) mha(p + "multihead_attn.", l.cin_w, l.cin_b, l.cout_w, l.cout_b);
+        f(p + "linear1.weight", Shape{ffn, d}, l.l1_w); f(p + "linear1.bias", Shape{ffn}, l.l1_b);
+        f(p + "linear2.weight", Shape{d, ffn}, l.l2_w); f(p + "linear2.bias", Shape{d}, l.l2_b);
+        for (int k = 0; k < (dec ? 3 : 2); ++k) {
+          f(p + "norm" + std::to_string(k + 1) + ".weight", Shape{d}, l.n_w[k]); f(p + "norm" + std::to_string(k + 1) + ".bias", Shape{d}, l.n_b[k]);
+        }
+      }
+    };
+    stack("encoder", enc_layers, false, t.enc);
+    stack("decoder", dec_layers, true, t.dec);
+    f("transformer.encoder.norm.weight", Shape{d}, t.encn_w); f("transformer.encoder.norm.bias", Shape{d}, t.encn_b);
+    f("transformer.decoder.norm.weight", Shape{d}, t.decn_w); f("transformer.decoder.norm.bias", Shape{d}, t.decn_b);
+  }
   void configure(const char* kv);
   void finalize(svg_ctx* ctx, int64_t* n_params);
   // src_pad (B,Ts) / tgt_pad (B,Tt): additive key-padding biases (models/transformer.py:64) or null

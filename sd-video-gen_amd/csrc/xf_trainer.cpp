@@ -4,7 +4,7 @@
 // (validation_loop: the same loss in eval mode) over torch.nn.Transformer (post-norm, ReLU, dropout after the positional
 // encoding, on the attention probabilities, after each sublayer and inside the feed-forward) and torch.optim.Adam(lr).
 // The Stable Diffusion side stays frozen (encode_batch is the VAE encoder the sampling path already has).
-#include "models.h"
+#include "xf_plan.h"
 #include "../../include/svg_hip.h"
 #include <cmath>
 #include <cstring>
@@ -12,7 +12,8 @@
 
 struct XfTrain {
   struct Slot { float* g = nullptr; float* m = nullptr; float* v = nullptr; int64_t n = 0; };
-  std::unordered_map<std::string, Slot> slots;
+  std::unordered_map<std::string, Slot> slots;   // by state_dict name: svg_transformer_tensor only
+  XfTable<float*> g;                              // Slot::g by role: what backward writes through
   XfAdamTensor* d_tens = nullptr;
   XfAdamChunk* d_chunks = nullptr;
   int n_chunks = 0;
@@ -65,8 +66,9 @@ namespace {
 
 constexpr int kAdamChunk = 1 << 16;
 
-struct LinTape { const float* x = nullptr; int M = 0, N = 0, K = 0; std::string w, b; int64_t woff = 0, boff = 0; };
-struct LnTape { float* xhat = nullptr; float* rstd = nullptr; std::string p; XfDrop dr{nullptr, 0, 0.f}; int M = 0; };
+// what a forward operation leaves for its backward: activations, and the parameters (w) with where their gradients go (gw, gb)
+struct LinTape { const float* x = nullptr; int M = 0, N = 0, K = 0; const float* w = nullptr; float* gw = nullptr; float* gb = nullptr; };
+struct LnTape { float* xhat = nullptr; float* rstd = nullptr; const float* w = nullptr; float* gw = nullptr; float* gb = nullptr; XfDrop dr{nullptr, 0, 0.f}; int M = 0; };
 struct MhaTape {
   LinTape in_q, in_kv, outp;   // self: in_q is the whole packed projection
   float *qkv = nullptr, *q = nullptr, *kv = nullptr, *P = nullptr;
@@ -76,26 +78,31 @@ struct MhaTape {
   XfDrop dr{nullptr, 0, 0.f};
 };
 struct FfnTape { LinTape l1, l2; float* r = nullptr; float gate_scale = 1.f; };
-struct EncTape { MhaTape sa; LnTape n1; FfnTape ff; LnTape n2; };
-struct DecTape { MhaTape sa; LnTape n1; MhaTape ca; LnTape n2; FfnTape ff; LnTape n3; };
+struct LayerTape { MhaTape sa, ca; FfnTape ff; LnTape n[3]; };     // an encoder layer leaves ca and n[2] unused
 
+// the training kernels (xf_train.hip) as the operations of xf_graph(), and their backward counterparts
 struct Run {
+  static constexpr bool kSharesEmbedding = false;   // each embedding draws its own dropout mask
   svg_ctx* ctx; XfModel* m; XfTrain* tr; hipStream_t s; int B; const uint64_t* seed; float p; bool grads;
   bool acc;      // SVG_BACKWARD_ACCUMULATE: every gradient store adds to its slot
   const float* text = nullptr;
   uint32_t site = 0;
+  std::vector<LayerTape> enc, dec;
+  LinTape e_lin[2], l_out;
+  XfDrop e_drop[2];
+  LnTape n_enc, n_dec;
+  struct Layer { const XfModel::LayerW& w; const XfTable<float*>::Layer& g; LayerTape& t; };
+  Layer layer(bool d, int i) { return d ? Layer{m->w.dec[i], tr->g.dec[i], dec[i]} : Layer{m->w.enc[i], tr->g.enc[i], enc[i]}; }
   bool go() const { return SVG_LAUNCHING(ctx); }
   XfDrop drop() { return XfDrop{seed, site++, p}; }
-  const float* W(const std::string& n) { return m->ws.get(n).f32; }
-  float* G(const std::string& n) { return tr->slots.at(n).g; }
   template <typename T> T* get(int64_t n) { return ctx->arena.get<T>(n); }
 
   // ---- linear ------------------------------------------------------------------------------------------------------------
-  float* lin(LinTape& t, const float* x, const std::string& w, const std::string& b, int M, int N, int K, int64_t woff = 0, int64_t boff = 0) {
-    t = LinTape{x, M, N, K, w, b, woff, boff};
+  float* lin(LinTape& t, const float* x, const float* w, const float* b, float* gw, float* gb, int M, int N, int K) {
+    t = LinTape{x, M, N, K, w, gw, gb};
     float* y = get<float>((int64_t)M * N);
     for (int m0 = 0; m0 < M; m0 += 336)       // xf_gemm streams W once per 336 rows (it plans its own split-K slabs in the dry pass)
-      xf_gemm(ctx, x + (int64_t)m0 * K, W(w) + woff, W(b) + boff, y + (int64_t)m0 * N, std::min(336, M - m0), N, K, 0, s);
+      xf_gemm(ctx, x + (int64_t)m0 * K, w, b, y + (int64_t)m0 * N, std::min(336, M - m0), N, K, 0, s);
     return y;
   }
   // dW, db of the layer; dx = gate(dy W) + add (dx == nullptr: not wanted)
@@ -105,20 +112,25 @@ struct Run {
     if (!go()) return;
     // (dW on a side stream beside the dX chain — a fork / join per linear layer inside the captured step — was bit-equal and 6-9 %
     // slower per step; removed, DESIGN.md "Training")
-    xf_gemm_tn(dy, t.N, t.x, t.K, G(t.w) + t.woff, G(t.b) + t.boff, t.M, t.N, t.K, accumulate || acc, s);
-    if (dx) xf_gemm_nn(dy, t.N, W(t.w) + t.woff, slabs, dx, t.M, t.N, t.K, gate, gate_scale, add, s);
+    xf_gemm_tn(dy, t.N, t.x, t.K, t.gw, t.gb, t.M, t.N, t.K, accumulate || acc, s);
+    if (dx) xf_gemm_nn(dy, t.N, t.w, slabs, dx, t.M, t.N, t.K, gate, gate_scale, add, s);
   }
 
   // ---- add + LayerNorm --------------------------------------------------------------------------------------------------
-  float* add_ln(LnTape& t, const float* x, const float* r, const std::string& p, int M, bool drop_r) {
+  float* ln(LnTape& t, const float* x, const float* r, const float* w, const float* b, float* gw, float* gb, int M, bool drop_r) {
     const int d = m->d_model;
-    t.p = p; t.M = M;
+    t.w = w; t.gw = gw; t.gb = gb; t.M = M;
     t.dr = drop_r ? drop() : XfDrop{seed, 0, 0.f};
     t.xhat = get<float>((int64_t)M * d);
     t.rstd = get<float>(M);
     float* y = get<float>((int64_t)M * d);
-    if (go()) xf_add_ln_train(x, r, t.dr, W(p + "weight"), W(p + "bias"), y, t.xhat, t.rstd, M, d, 1e-5f, s);
+    if (go()) xf_add_ln_train(x, r, t.dr, w, b, y, t.xhat, t.rstd, M, d, 1e-5f, s);
     return y;
+  }
+  float* add_ln(const Layer& L, int k, const float* x, const float* r, int M) { return ln(L.t.n[k], x, r, L.w.n_w[k], L.w.n_b[k], L.g.n_w[k], L.g.n_b[k], M, true); }
+  float* final_ln(bool d, const float* x, int M) {
+    return d ? ln(n_dec, x, nullptr, m->w.decn_w, m->w.decn_b, tr->g.decn_w, tr->g.decn_b, M, false)
+             : ln(n_enc, x, nullptr, m->w.encn_w, m->w.encn_b, tr->g.encn_w, tr->g.encn_b, M, false);
   }
   // returns dz (gradient of both the residual input and, masked in *dz_drop, of the sublayer output)
   float* add_ln_bwd(const LnTape& t, const float* dy, float** dz_drop) {
@@ -126,28 +138,29 @@ struct Run {
     float* dz = get<float>((int64_t)t.M * d);
     float* dzd = nullptr;
     if (dz_drop) { dzd = t.dr.p > 0.f ? get<float>((int64_t)t.M * d) : dz; *dz_drop = dzd; }
-    if (go())
-      xf_ln_bwd(dy, t.xhat, t.rstd, W(t.p + "weight"), dz, dzd == dz ? nullptr : dzd, t.dr, G(t.p + "weight"), G(t.p + "bias"), t.M, d, acc, s);
+    if (go()) xf_ln_bwd(dy, t.xhat, t.rstd, t.w, dz, dzd == dz ? nullptr : dzd, t.dr, t.gw, t.gb, t.M, d, acc, s);
     return dz;
   }
 
-  // ---- multi-head attention ---------------------------------------------------------------------------------------------
-  float* mha(MhaTape& t, const std::string& p, const float* xq, int Tq, const float* xkv, int Tk, const float* mask, bool self) {
+  // ---- multi-head attention (training takes no key-padding bias) ------------------------------------------------------------
+  float* mha(const Layer& L, bool cross, const float* xq, int Tq, const float* xkv, int Tk, const float* mask, const float*) {
     const int d = m->d_model, hd = d / m->heads;
-    t.Tq = Tq; t.Tk = Tk; t.self = self; t.mask = mask;
+    MhaTape& t = cross ? L.t.ca : L.t.sa;
+    t.Tq = Tq; t.Tk = Tk; t.self = !cross; t.mask = mask;
     float* o = get<float>((int64_t)Tq * B * d);
     t.P = get<float>((int64_t)B * m->heads * Tq * Tk);
-    if (self) {
-      t.qkv = lin(t.in_q, xq, p + "in_proj_weight", p + "in_proj_bias", Tq * B, 3 * d, d);
+    if (!cross) {
+      t.qkv = lin(t.in_q, xq, L.w.in_w, L.w.in_b, L.g.in_w, L.g.in_b, Tq * B, 3 * d, d);
       t.dr = drop();
       if (go()) xf_attention_train(t.qkv, 3 * d, t.qkv + d, t.qkv + 2 * d, 3 * d, mask, o, t.P, Tq, Tk, B, m->heads, hd, t.dr, s);
-    } else {
-      t.q = lin(t.in_q, xq, p + "in_proj_weight", p + "in_proj_bias", Tq * B, d, d);
-      t.kv = lin(t.in_kv, xkv, p + "in_proj_weight", p + "in_proj_bias", Tk * B, 2 * d, d, (int64_t)d * d, d);
-      t.dr = drop();
-      if (go()) xf_attention_train(t.q, d, t.kv, t.kv + d, 2 * d, mask, o, t.P, Tq, Tk, B, m->heads, hd, t.dr, s);
+      return lin(t.outp, o, L.w.out_w, L.w.out_b, L.g.out_w, L.g.out_b, Tq * B, d, d);
     }
-    return lin(t.outp, o, p + "out_proj.weight", p + "out_proj.bias", Tq * B, d, d);
+    const int64_t dd = (int64_t)d * d;
+    t.q = lin(t.in_q, xq, L.w.cin_w, L.w.cin_b, L.g.cin_w, L.g.cin_b, Tq * B, d, d);
+    t.kv = lin(t.in_kv, xkv, L.w.cin_w + dd, L.w.cin_b + d, L.g.cin_w + dd, L.g.cin_b + d, Tk * B, 2 * d, d);
+    t.dr = drop();
+    if (go()) xf_attention_train(t.q, d, t.kv, t.kv + d, 2 * d, mask, o, t.P, Tq, Tk, B, m->heads, hd, t.dr, s);
+    return lin(t.outp, o, L.w.cout_w, L.w.cout_b, L.g.cout_w, L.g.cout_b, Tq * B, d, d);
   }
   // da: gradient of the block output.  dxq = ... + add_q; self: the k/v gradients flow into the same dxq; cross: dmem (+)= ...
   void mha_bwd(const MhaTape& t, const float* da, float* dxq, const float* add_q, float* dmem, bool dmem_accumulate) {
@@ -171,13 +184,14 @@ struct Run {
   }
 
   // ---- feed-forward: linear2(dropout(relu(linear1(x)))) ---------------------------------------------------------------------
-  float* ffn(FfnTape& t, const std::string& p, const float* x, int M) {
-    float* h = lin(t.l1, x, p + "linear1.weight", p + "linear1.bias", M, m->ffn, m->d_model);
+  float* ffn(const Layer& L, const float* x, int M) {
+    FfnTape& t = L.t.ff;
+    float* h = lin(t.l1, x, L.w.l1_w, L.w.l1_b, L.g.l1_w, L.g.l1_b, M, m->ffn, m->d_model);
     t.r = get<float>((int64_t)M * m->ffn);
     const XfDrop dr = drop();
     t.gate_scale = dr.p > 0.f ? 1.f / (1.f - dr.p) : 1.f;
     if (go()) xf_relu_drop(h, t.r, (int64_t)M * m->ffn, dr, s);
-    return lin(t.l2, t.r, p + "linear2.weight", p + "linear2.bias", M, m->d_model, m->ffn);
+    return lin(t.l2, t.r, L.w.l2_w, L.w.l2_b, L.g.l2_w, L.g.l2_b, M, m->d_model, m->ffn);
   }
   void ffn_bwd(const FfnTape& t, const float* df, float* dx, const float* add) {
     float* dh = get<float>((int64_t)t.l1.M * m->ffn);
@@ -185,22 +199,22 @@ struct Run {
     lin_bwd(t.l1, dh, dx, add);
   }
 
-  // ---- embedding + positional encoding --------------------------------------------------------------------------------------
-  float* embed(LinTape& t, XfDrop& dr, const float* x, int T, const int32_t* pe_row) {
+  // ---- embedding + positional encoding (which: 0 source, 1 target) ----------------------------------------------------------
+  float* embed(int which, const float* x, int T) {
     const int d = m->d_model, d_img = d - m->text_dim;
-    const std::string en = m->text_dim ? "project_image_embedding" : "embedding";
-    float* e = lin(t, x, en + ".weight", en + ".bias", B * T, d_img, m->d_lat);
+    float* e = lin(e_lin[which], x, m->w.emb_w, m->w.emb_b, tr->g.emb_w, tr->g.emb_b, B * T, d_img, m->d_lat);
     float* y = get<float>((int64_t)B * T * d);
-    dr = drop();
-    if (go()) xf_embed_post_train(e, m->pe, pe_row, text, m->text_dim, y, B, T, d, sqrtf((float)d), dr, s);
+    e_drop[which] = drop();
+    if (go()) xf_embed_post_train(e, m->pe, m->iota, text, m->text_dim, y, B, T, d, sqrtf((float)d), e_drop[which], s);
     return y;
   }
-  void embed_bwd(const LinTape& t, const XfDrop& dr, const float* dy, int T, bool accumulate) {
+  void embed_bwd(int which, const float* dy, int T, bool accumulate) {
     const int d = m->d_model, d_img = d - m->text_dim;
     float* de = get<float>((int64_t)B * T * d_img);
-    if (go()) xf_embed_post_bwd(dy, de, B, T, d, d_img, sqrtf((float)d), dr, s);
-    lin_bwd(t, de, nullptr, nullptr, nullptr, 1.f, accumulate);
+    if (go()) xf_embed_post_bwd(dy, de, B, T, d, d_img, sqrtf((float)d), e_drop[which], s);
+    lin_bwd(e_lin[which], de, nullptr, nullptr, nullptr, 1.f, accumulate);
   }
+  float* out(const float* x, int M) { return lin(l_out, x, m->w.out_w, m->w.out_b, tr->g.out_w, tr->g.out_b, M, m->d_lat, m->d_model); }
 };
 
 void ensure_train(svg_ctx* ctx, XfModel* m) {
@@ -238,6 +252,7 @@ void ensure_train(svg_ctx* ctx, XfModel* m) {
   HIP_OK(hipMemcpy(tr->d_tens, tens.data(), tens.size() * sizeof(XfAdamTensor), hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(tr->d_chunks, chunks.data(), chunks.size() * sizeof(XfAdamChunk), hipMemcpyHostToDevice));
   tr->n_chunks = (int)chunks.size();
+  m->each_param(tr->g, [&](const std::string& name, std::initializer_list<int64_t>, float*& slot) { slot = tr->slots.at(name).g; });
   m->train = tr.release();
 }
 
@@ -261,29 +276,8 @@ void loss_pass(svg_ctx* ctx, XfModel* m, const svg_train_cfg& cfg, const float* 
   auto body = [&](const float* src, const float* tgt, const float* expected, const float* text, const float* mask) {
     Run r{ctx, m, tr, s, B, tr->d_seed, backward ? cfg.dropout_p : 0.f, backward != 0, backward == SVG_BACKWARD_ACCUMULATE};
     r.text = text;
-    LinTape e_src, e_tgt, l_out;
-    XfDrop d_src, d_tgt;
-    float* xs = r.embed(e_src, d_src, src, Ts, m->iota);
-    float* xt = r.embed(e_tgt, d_tgt, tgt, Tt, m->iota);
-    std::vector<EncTape> enc(m->enc_layers);
-    std::vector<DecTape> dec(m->dec_layers);
-    for (int i = 0; i < m->enc_layers; ++i) {
-      const std::string p = "transformer.encoder.layers." + std::to_string(i) + ".";
-      EncTape& t = enc[i];
-      xs = r.add_ln(t.n1, xs, r.mha(t.sa, p + "self_attn.", xs, Ts, xs, Ts, nullptr, true), p + "norm1.", Ms, true);
-      xs = r.add_ln(t.n2, xs, r.ffn(t.ff, p, xs, Ms), p + "norm2.", Ms, true);
-    }
-    LnTape n_enc, n_dec;
-    float* mem = r.add_ln(n_enc, xs, nullptr, "transformer.encoder.norm.", Ms, false);
-    for (int i = 0; i < m->dec_layers; ++i) {
-      const std::string p = "transformer.decoder.layers." + std::to_string(i) + ".";
-      DecTape& t = dec[i];
-      xt = r.add_ln(t.n1, xt, r.mha(t.sa, p + "self_attn.", xt, Tt, xt, Tt, mask, true), p + "norm1.", Mt, true);
-      xt = r.add_ln(t.n2, xt, r.mha(t.ca, p + "multihead_attn.", xt, Tt, mem, Ts, nullptr, false), p + "norm2.", Mt, true);
-      xt = r.add_ln(t.n3, xt, r.ffn(t.ff, p, xt, Mt), p + "norm3.", Mt, true);
-    }
-    xt = r.add_ln(n_dec, xt, nullptr, "transformer.decoder.norm.", Mt, false);
-    float* pred = r.lin(l_out, xt, "out.weight", "out.bias", Mt, m->d_lat, d);
+    r.enc.resize(m->enc_layers); r.dec.resize(m->dec_layers);
+    float* pred = xf_graph(r, *m, XfChunk{B, Ts, Tt, src, tgt, mask, text, nullptr, nullptr, m->iota, nullptr});
     if (!expected) {                                           // forward only
       if (r.go()) HIP_OK(hipMemcpyAsync(pred_out, pred, (size_t)Mt * m->d_lat * sizeof(float), hipMemcpyDeviceToDevice, s));
       return;
@@ -300,40 +294,40 @@ void loss_pass(svg_ctx* ctx, XfModel* m, const svg_train_cfg& cfg, const float* 
 
     // ---- backward ----------------------------------------------------------------------------------------------------------
     float* dx = r.get<float>((int64_t)Mt * d);
-    r.lin_bwd(l_out, dpred, dx);
-    float* dxt = r.add_ln_bwd(n_dec, dx, nullptr);
+    r.lin_bwd(r.l_out, dpred, dx);
+    float* dxt = r.add_ln_bwd(r.n_dec, dx, nullptr);
     float* dmem = r.get<float>((int64_t)Ms * d);
     bool dmem_set = false;
     for (int i = m->dec_layers - 1; i >= 0; --i) {
-      DecTape& t = dec[i];
+      LayerTape& t = r.dec[i];
       float *dzd = nullptr, *dz;
-      dz = r.add_ln_bwd(t.n3, dxt, &dzd);                     // x2 + dropout(ff(x2))
+      dz = r.add_ln_bwd(t.n[2], dxt, &dzd);                     // x2 + dropout(ff(x2))
       float* dx2 = r.get<float>((int64_t)Mt * d);
       r.ffn_bwd(t.ff, dzd, dx2, dz);
-      dz = r.add_ln_bwd(t.n2, dx2, &dzd);                     // x1 + dropout(cross(x1, mem))
+      dz = r.add_ln_bwd(t.n[1], dx2, &dzd);                     // x1 + dropout(cross(x1, mem))
       float* dx1 = r.get<float>((int64_t)Mt * d);
       r.mha_bwd(t.ca, dzd, dx1, dz, dmem, dmem_set);
       dmem_set = true;
-      dz = r.add_ln_bwd(t.n1, dx1, &dzd);                     // x + dropout(self(x))
+      dz = r.add_ln_bwd(t.n[0], dx1, &dzd);                     // x + dropout(self(x))
       float* dx0 = r.get<float>((int64_t)Mt * d);
       r.mha_bwd(t.sa, dzd, dx0, dz, nullptr, false);
       dxt = dx0;
     }
     if (!dmem_set && r.go()) SDNS::fill_f32(dmem, (int64_t)Ms * d, 0.f, s);
-    float* dxs = r.add_ln_bwd(n_enc, dmem, nullptr);
+    float* dxs = r.add_ln_bwd(r.n_enc, dmem, nullptr);
     for (int i = m->enc_layers - 1; i >= 0; --i) {
-      EncTape& t = enc[i];
+      LayerTape& t = r.enc[i];
       float *dzd = nullptr, *dz;
-      dz = r.add_ln_bwd(t.n2, dxs, &dzd);
+      dz = r.add_ln_bwd(t.n[1], dxs, &dzd);
       float* dx1 = r.get<float>((int64_t)Ms * d);
       r.ffn_bwd(t.ff, dzd, dx1, dz);
-      dz = r.add_ln_bwd(t.n1, dx1, &dzd);
+      dz = r.add_ln_bwd(t.n[0], dx1, &dzd);
       float* dx0 = r.get<float>((int64_t)Ms * d);
       r.mha_bwd(t.sa, dzd, dx0, dz, nullptr, false);
       dxs = dx0;
     }
-    r.embed_bwd(e_src, d_src, dxs, Ts, false);
-    r.embed_bwd(e_tgt, d_tgt, dxt, Tt, true);                 // the embedding layer is shared: second contribution accumulates
+    r.embed_bwd(0, dxs, Ts, false);
+    r.embed_bwd(1, dxt, Tt, true);                // the embedding layer is shared: second contribution accumulates
   };
   // ---- the plan of this call signature ----------------------------------------------------------------------------------------
   struct ArenaSwap {       // the training workspace stands in for the context arena until this call returns (or throws)

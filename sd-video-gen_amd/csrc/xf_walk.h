@@ -1,6 +1,7 @@
 // Stage table of the layer-walking kernel of the latent Transformer (xf_walk.hip): ONE launch walks embedding -> encoder layers ->
 // decoder layers -> output projection of models/transformer.py:47-68 (torch.nn.Transformer, post-norm, ReLU).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
@@ -45,10 +46,18 @@ struct alignas(16) WalkOp {
 constexpr int kWalkMaxRows = 176;
 constexpr int kWalkMaxOps = 512;                      // stages of one launch (the pinned / device table ring is sized for it)
 inline bool xf_walk_gemm_ok(int N, int K) { return N % 128 == 0 && K % 128 == 0 && N >= 128 && K >= 128; }
-// dynamic LDS of a launch: the X tile of a GEMM stage (rows rounded to 16, 4 steps of 128 B) + a sink for padding DMAs, or the q/k/v
-// slices of one attention job
-int64_t xf_walk_lds_bytes(int rows, int Tq, int Tk, int hd);
-bool xf_walk_available(int rows, int64_t lds_bytes);
+// dynamic LDS of a launch, each size in one place (the forward plan, the launch call sites and the launch's own table check use these)
+constexpr int64_t kWalkMaxLds = 150 * 1024;           // most a launch may ask for
+inline int xf_walk_mt(int rows) {                     // 16-row accumulator tiles of the kernel instantiation that serves `rows`
+  const int mt = (rows + 15) / 16;
+  return mt <= 4 ? mt : (mt <= 6 ? 6 : (mt <= 8 ? 8 : 11));
+}
+// the X tile of a split-K GEMM stage (rows rounded to 16, 4 steps of 128 B) + a sink for padding DMAs
+inline int64_t xf_walk_gemm_lds_bytes(int rows) { return (int64_t)4 * xf_walk_mt(rows) * 16 * 128 + 4096; }
+// the q / k / v slices of one attention job, the 32 x 33 score and probability tiles, 32 row sums
+inline int64_t xf_walk_attn_lds_bytes(int Tq, int Tk, int hd) { return ((int64_t)(Tq + 2 * Tk) * hd + 2 * 32 * 33 + 32) * 4; }
+inline int64_t xf_walk_lds_bytes(int rows, int Tq, int Tk, int hd) { return std::max(xf_walk_gemm_lds_bytes(rows), xf_walk_attn_lds_bytes(Tq, Tk, hd)); }
+inline bool xf_walk_available(int rows, int64_t lds_bytes, int64_t lds_limit = kWalkMaxLds) { return rows >= 1 && rows <= kWalkMaxRows && lds_bytes <= lds_limit; }
 // ops: host array (copied to the device through a pinned ring); the launch is ordered after the previous walk of this process on any
 // stream (two resident walks could starve each other of compute units while spinning at their barriers)
 void xf_walk_launch(svg_ctx* ctx, const WalkOp* ops, int n_ops, int rows, int64_t lds_bytes, hipStream_t s);
@@ -56,6 +65,9 @@ void xf_walk_launch(svg_ctx* ctx, const WalkOp* ops, int n_ops, int rows, int64_
 // columns per workgroup and stage (N <= 8 x workgroups: the host cuts wider matrices into column blocks)
 constexpr int kWalkSmallRows = 8;
 constexpr int kWalkSmallMaxK = 2048;
+// small-row launch: the padded X rows + 4 LayerNorm parameter vectors of a GEMM stage; a launch of sequences up to T tokens
+inline int64_t xf_walk_small_gemm_lds_bytes() { return (int64_t)kWalkSmallRows * (kWalkSmallMaxK * 4 + 64) + 4 * kWalkSmallMaxK * 4; }
+inline int64_t xf_walk_small_lds_bytes(int T, int hd) { return std::max(xf_walk_small_gemm_lds_bytes(), xf_walk_attn_lds_bytes(T, T, hd)); }
 int xf_walk_grid();                                     // workgroups of a launch on the current device (0: walk unavailable)
 void xf_walk_small_launch(svg_ctx* ctx, const WalkOp* ops, int n_ops, int64_t lds_bytes, hipStream_t s);
 void xf_walk_init_device();

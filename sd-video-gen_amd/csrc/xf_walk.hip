@@ -720,7 +720,7 @@ struct WalkDev {
 };
 std::mutex g_mu;
 WalkDev g_dev[16];
-constexpr int64_t kMaxLds = 150 * 1024;
+constexpr int64_t kMaxLds = kWalkMaxLds;
 constexpr int64_t kMinLds = 84 * 1024;                // above half a compute unit's LDS: exactly one workgroup per compute unit
 
 // The knobs, looked up once per device at svg_create (and again at svg_env_refresh), never on the forward path:
@@ -778,10 +778,6 @@ void launch(const WalkDev& D, int64_t lds, hipStream_t s, const WalkOp* ops, int
   }
 #endif
 }
-int walk_mt(int rows) {
-  const int mt = (rows + 15) / 16;
-  return mt <= 4 ? mt : (mt <= 6 ? 6 : (mt <= 8 ? 8 : 11));
-}
 const char* kGaveUp = "xf_walk: a layer-walking launch gave up at a device-wide barrier (a workgroup never became resident: something else is "
                       "holding compute units of this device).  The output of that forward is invalid (NaN-filled).  The layer-walking launch "
                       "is now OFF for this device in this process — later forwards run the per-GEMM kernels; re-issue the failed forward";
@@ -789,7 +785,7 @@ const char* kGaveUp = "xf_walk: a layer-walking launch gave up at a device-wide 
 // Every stage against what the kernel assumes about it.  The kernel reads its operands through exact-size descriptors (a wrong index
 // returns zeros instead of faulting), but a table that breaks these rules would still compute garbage or overrun LDS: refuse it on the host.
 void validate_table(const WalkOp* ops, int n_ops, int rows, int64_t lds, bool small, int n_wg) {
-  const int mt = walk_mt(rows);
+  const int mt = xf_walk_mt(rows);
   auto span_ok = [](int64_t elems) { return elems > 0 && elems * 4 < (int64_t)1 << 31; };
   for (int i = 0; i < n_ops; ++i) {
     const WalkOp& op = ops[i];
@@ -799,7 +795,7 @@ void validate_table(const WalkOp* ops, int n_ops, int rows, int64_t lds, bool sm
                   "xf_walk: stage %d: GEMM %d x %d x %d (ld %d) does not fit the kernel (tiles of 128 x 128, at most %d rows)", i, op.M, op.N, op.K, op.ld, mt * 16);
         SVG_CHECK(span_ok((int64_t)op.N * op.K) && span_ok((int64_t)(op.M - 1) * op.ld + op.K) && span_ok((int64_t)op.ksplit * op.M * op.N),
                   "xf_walk: stage %d: an operand of GEMM %d x %d x %d exceeds a 2 GB buffer descriptor", i, op.M, op.N, op.K);
-        SVG_CHECK((int64_t)4 * mt * 16 * 128 + 4096 <= lds, "xf_walk: stage %d: X tile of %d rows needs more than %lld bytes of LDS", i, mt * 16, (long long)lds);
+        SVG_CHECK(xf_walk_gemm_lds_bytes(rows) <= lds, "xf_walk: stage %d: X tile of %d rows needs more than %lld bytes of LDS", i, mt * 16, (long long)lds);
         break;
       case WK_RED:
         SVG_CHECK(op.M >= 1 && op.N % 4 == 0 && op.slab && op.Y && op.ksplit >= 1 && span_ok((int64_t)op.ksplit * op.M * op.N), "xf_walk: stage %d: reduce %d x %d x %d slabs", i, op.M, op.N, op.ksplit);
@@ -813,7 +809,7 @@ void validate_table(const WalkOp* ops, int n_ops, int rows, int64_t lds, bool sm
         SVG_CHECK(op.Tq >= 1 && op.Tq <= 32 && op.Tk >= 1 && op.Tk <= 32 && op.hd % 4 == 0 && op.heads >= 1 && op.B >= 1 && op.qs && op.ks && op.vs && op.Y &&
                       op.vs >= op.ks && op.q_span > 0 && op.kv_span > (int)(op.vs - op.ks),
                   "xf_walk: stage %d: attention Tq %d Tk %d head dim %d", i, op.Tq, op.Tk, op.hd);
-        SVG_CHECK(((int64_t)(op.Tq + 2 * op.Tk) * op.hd + 2 * 32 * 33 + 32) * 4 <= lds, "xf_walk: stage %d: attention slices exceed %lld bytes of LDS", i, (long long)lds);
+        SVG_CHECK(xf_walk_attn_lds_bytes(op.Tq, op.Tk, op.hd) <= lds, "xf_walk: stage %d: attention slices exceed %lld bytes of LDS", i, (long long)lds);
         break;
       case WK_EMBED:
         SVG_CHECK(op.M == op.B * op.T && op.N % 4 == 0 && op.d_txt % 4 == 0 && op.slab && op.Y && op.pe && op.bias && op.ksplit >= 1 && (op.d_txt == 0 || op.text),
@@ -827,7 +823,7 @@ void validate_table(const WalkOp* ops, int n_ops, int rows, int64_t lds, bool sm
         SVG_CHECK((!op.g1 || op.b1) && (!op.g2 || (op.g1 && op.b2)) && (!op.Yln || op.g1) && (!op.reuse_x || (i > 0 && ops[i - 1].kind == WK_GEMMF && ops[i - 1].X == op.X && ops[i - 1].K == op.K && !op.bar)) &&
                       (!op.perm || (op.B >= 1 && op.T >= 1 && op.B * op.T == op.M)) && (!op.pe || op.B >= 1),
                   "xf_walk: stage %d: small-row GEMM flags are inconsistent", i);
-        SVG_CHECK(span_ok((int64_t)op.N * op.K) && (int64_t)kWalkSmallRows * (kWalkSmallMaxK * 4 + 64) + 4 * kWalkSmallMaxK * 4 <= lds, "xf_walk: stage %d: operands of the small-row GEMM exceed a descriptor / LDS", i);
+        SVG_CHECK(span_ok((int64_t)op.N * op.K) && xf_walk_small_gemm_lds_bytes() <= lds, "xf_walk: stage %d: operands of the small-row GEMM exceed a descriptor / LDS", i);
         break;
       default: SVG_CHECK(false, "xf_walk: stage %d: unknown kind %d", i, op.kind);
     }
@@ -837,15 +833,6 @@ void validate_table(const WalkOp* ops, int n_ops, int rows, int64_t lds, bool sm
 }
 
 }  // namespace
-
-int64_t xf_walk_lds_bytes(int rows, int Tq, int Tk, int hd) {
-  const int mt = walk_mt(rows);
-  const int64_t gemm = (int64_t)4 * mt * 16 * 128 + 4096;
-  const int64_t attn = ((int64_t)(Tq + 2 * Tk) * hd + 2 * 32 * 33 + 32) * 4;
-  return std::max(gemm, attn);
-}
-
-bool xf_walk_available(int rows, int64_t lds_bytes) { return rows >= 1 && rows <= kWalkMaxRows && lds_bytes <= kMaxLds; }
 
 void xf_walk_init_device() {
   int dev = 0;
@@ -972,7 +959,7 @@ static void walk_launch_impl(const WalkOp* ops, int n_ops, int rows, int64_t lds
   if (D.last >= 0 && D.last != slot) HIP_OK(hipStreamWaitEvent(s, D.done[D.last], 0));
   HIP_OK(hipMemcpyAsync(D.dops[slot], D.hops[slot], sizeof(WalkOp) * n_ops, hipMemcpyHostToDevice, s));
   HIP_OK(hipMemsetAsync(D.sync[slot], 0, sizeof(WalkSync), s));
-  const int mt = walk_mt(rows);
+  const int mt = xf_walk_mt(rows);
   WalkOp* dops = D.dops[slot];
   WalkSync* sy = D.sync[slot];
   unsigned* ha = D.habort + slot;

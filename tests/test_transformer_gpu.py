@@ -419,3 +419,35 @@ def test_walk_small_rows_single_clip(ctx, shape):
             return e0.elapsed_time(e1) / 20
         return _with_walk(walk, f, small=small)
     print("[walk] %s, 6 rows: small-row walk %.3f ms | split-K walk %.3f ms | per-GEMM kernels %.3f ms" % (shape, timed(True), timed(False), timed(True, walk=False)))
+
+
+def test_each_form_of_the_forward_plan_end_to_end(ctx):
+    """The forward plan, the stage-table builders, the real arena and the launch wired together (tests/test_xf_plan_cpu.py pins the plan and
+    the tables on the host; this is what it cannot see).  A small model (d = 256 — the narrowest the small-row form takes — 1 + 1 layers, 6
+    tokens) on each form a shape can take: one clip (6 rows) on the per-GEMM kernels, the split-K walk and the small-row walk, two clips
+    (12 rows) on the first two.  Per form: the workspace high-water mark of a planning pass (printed, and the same on a second pass), the output
+    bit-equal between two consecutive calls, and within the file's tolerance of the CPU oracle."""
+    m = _walk_model(enc=1, dec=1, seed=13)
+    sd = {k: v.clone().cpu() for k, v in m.state_dict().items()}
+    mask = m.get_tgt_mask(6).cuda()
+    forms = {"per_gemm": dict(on=False), "walk": dict(on=True, small=False), "walk_small": dict(on=True, small=True)}
+    for B in (1, 2):
+        X = torch.randn(B, 6, 256, generator=torch.Generator().manual_seed(40 + B))
+        ref = TO.forward(sd, X, X, 4, TO.get_tgt_mask(6))
+        run = lambda: m(X.cuda(), X.cuda(), mask).cpu()          # no pe_row: PE by batch row, as the oracle
+
+        def planned():
+            with m._ctx.planning() as plan:
+                m(X.cuda(), X.cuda(), mask)
+            return plan.bytes
+        highs = {}
+        for name, kw in forms.items():
+            if name == "walk_small" and B * 6 > 8:
+                continue
+            out = _with_walk(fn=run, **kw)
+            assert torch.equal(out, _with_walk(fn=run, **kw)), name
+            highs[name] = _with_walk(fn=planned, **kw)
+            assert highs[name] > 0 and _with_walk(fn=planned, **kw) == highs[name]
+            err = rel_l2(out, ref)
+            print("[xf_plan] B=%d %s: workspace high-water mark %d bytes, rel-L2 vs oracle %.2e" % (B, name, highs[name], err))
+            assert err < TOL, name
