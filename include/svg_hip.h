@@ -176,8 +176,39 @@ typedef struct svg_optim_cfg {
 int svg_transformer_optim_step(svg_ctx* ctx, const svg_optim_cfg* cfg, double* grad_norm_out, void* stream);
 /* copies a parameter / its gradient / its Adam moments out (host or device `out`, numel floats; state_dict key names):
  * what torch.save(model.state_dict()) at trainer.py:469-480 needs after steps taken in the library. */
-enum svg_tensor_kind { SVG_TENSOR_PARAM = 0, SVG_TENSOR_GRAD = 1, SVG_TENSOR_EXP_AVG = 2, SVG_TENSOR_EXP_AVG_SQ = 3 };
+/* SVG_TENSOR_EMA: the averaged weights (below); SVG_ERR_INVALID while none exist. */
+enum svg_tensor_kind { SVG_TENSOR_PARAM = 0, SVG_TENSOR_GRAD = 1, SVG_TENSOR_EXP_AVG = 2, SVG_TENSOR_EXP_AVG_SQ = 3, SVG_TENSOR_EMA = 4 };
 int svg_transformer_tensor(svg_ctx* ctx, int kind, const char* name, float* out, int64_t numel, void* stream);
+
+/* ---- latent Transformer: continuing a training run ------------------------------------------- */
+/* The inverse of svg_transformer_tensor for SVG_TENSOR_EXP_AVG, SVG_TENSOR_EXP_AVG_SQ and SVG_TENSOR_EMA: numel floats from `data`
+ * (host or device memory) become that tensor of parameter `name` (state_dict key).  Synchronises the stream.
+ * If the context has no training state yet it is created, in the condition it has right after creation (zero gradients, zero
+ * moments, step count 0, no gradients to step on until the next svg_transformer_loss(backward != 0)); the first SVG_TENSOR_EMA
+ * creates the averaged weights, every tensor a copy of its parameter as it stands, before `name` is overwritten.
+ * SVG_TENSOR_PARAM and SVG_TENSOR_GRAD are refused: parameters go through svg_load_weight, which DROPS the training state
+ * (moments, step count, averaged weights and their decay).  The order of a resume is therefore
+ *   svg_load_weight (every tensor) -> svg_finalize -> svg_transformer_set_tensor (moments, averaged weights)
+ *   -> svg_transformer_set_optim_step_count -> svg_transformer_ema_configure -> svg_transformer_loss ...
+ * SVG_ERR_INVALID, with nothing changed: a null argument, a kind other than the three, an unknown name, numel other than the
+ * parameter's, or a model that is not finalized.  Allocation (first call only) happens under the library's device-wide lock,
+ * after a device-wide synchronisation, like every other change of what the training state owns. */
+int svg_transformer_set_tensor(svg_ctx* ctx, int kind, const char* name, const float* data, int64_t numel, void* stream);
+/* The number of optimizer steps taken: the counter that svg_transformer_adam_step and svg_transformer_optim_step advance by one
+ * and take their bias corrections 1 - beta^step from (0 without training state).  Setting it (0 <= step < 2^31; creates the
+ * training state if there is none) makes the next step number step + 1. */
+int svg_transformer_optim_step_count(svg_ctx* ctx, int64_t* out);
+int svg_transformer_set_optim_step_count(svg_ctx* ctx, int64_t step);
+/* Exponential moving average of the parameters, kept by the optimizer step itself.  0 < decay < 1 turns it on: from then on every
+ * svg_transformer_adam_step / svg_transformer_optim_step also does, per element and in f32, in the launch and the loop that forms
+ * the new parameter p_new,
+ *       e = e + (p_new - e) * (1.f - decay)
+ * (the form of the exp_avg update); p, exp_avg and exp_avg_sq get the bits they get without it.  If no averaged weights exist when
+ * it is turned on they are allocated as a copy of the parameters as they stand (device-wide synchronisation, once).  decay == 0
+ * turns the updates off and keeps the buffers and their values; any other value is SVG_ERR_INVALID.  Read them with
+ * svg_transformer_tensor(SVG_TENSOR_EMA), write them with svg_transformer_set_tensor.  They are part of the training state:
+ * svg_load_weight / svg_model_configure / svg_destroy free them and forget the decay. */
+int svg_transformer_ema_configure(svg_ctx* ctx, float decay);
 
 /* ---- CLIP text encoder ---------------------------------------------------------------------- */
 /* input_ids (B,T) int32 token ids (T <= max_pos; the reference pads to 77); out (B,T,d_model) f32 = last_hidden_state.

@@ -28,7 +28,7 @@ _lib = None
 
 _vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
 
-SVG_TENSOR_PARAM, SVG_TENSOR_GRAD, SVG_TENSOR_EXP_AVG, SVG_TENSOR_EXP_AVG_SQ = 0, 1, 2, 3   # enum svg_tensor_kind
+SVG_TENSOR_PARAM, SVG_TENSOR_GRAD, SVG_TENSOR_EXP_AVG, SVG_TENSOR_EXP_AVG_SQ, SVG_TENSOR_EMA = 0, 1, 2, 3, 4   # enum svg_tensor_kind
 SVG_BACKWARD_ACCUMULATE = 2     # svg_transformer_loss(backward=): add the gradients to what the slots hold
 
 
@@ -95,6 +95,10 @@ SIGNATURES = {
     "svg_transformer_grad_norm": [_vp, C.POINTER(C.c_double), _vp],
     "svg_transformer_optim_step": [_vp, C.POINTER(OptimCfg), C.POINTER(C.c_double), _vp],
     "svg_transformer_tensor": [_vp, _i, C.c_char_p, _vp, _i64, _vp],
+    "svg_transformer_set_tensor": [_vp, _i, C.c_char_p, _vp, _i64, _vp],
+    "svg_transformer_optim_step_count": [_vp, C.POINTER(_i64)],
+    "svg_transformer_set_optim_step_count": [_vp, _i64],
+    "svg_transformer_ema_configure": [_vp, _f],
     "svg_clip_text_forward": [_vp, _vp, _i, _i, _vp, _vp],
     "svg_minilm_encode": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
     "svg_i3d_forward": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
@@ -442,6 +446,25 @@ class Context:
         self.check(self.lib.svg_transformer_tensor(self.h, kind, name.encode(), out.data_ptr(), out.numel(), _stream()),
                    "svg_transformer_tensor(%s)" % name)
         return out
+
+    def transformer_set_tensor(self, name, value, kind):
+        """svg_transformer_set_tensor: `value` (any device, f32) becomes the Adam moment / averaged copy `kind` of parameter `name`"""
+        value = value.detach().to(torch.float32).contiguous()
+        torch.cuda.synchronize()      # as transformer_tensor
+        self.check(self.lib.svg_transformer_set_tensor(self.h, kind, name.encode(), value.data_ptr(), value.numel(), _stream()),
+                   "svg_transformer_set_tensor(%s)" % name)
+
+    def transformer_optim_step_count(self):
+        out = _i64()
+        self.check(self.lib.svg_transformer_optim_step_count(self.h, C.byref(out)), "svg_transformer_optim_step_count")
+        return int(out.value)
+
+    def transformer_set_optim_step_count(self, step):
+        self.check(self.lib.svg_transformer_set_optim_step_count(self.h, int(step)), "svg_transformer_set_optim_step_count")
+
+    def transformer_ema_configure(self, decay):
+        torch.cuda.synchronize()      # the first call copies the parameters: no step of another stream may still be writing them
+        self.check(self.lib.svg_transformer_ema_configure(self.h, float(decay)), "svg_transformer_ema_configure")
 
     def dropout_mask(self, seed, site, p, n):
         out = torch.empty(n, device="cuda", dtype=torch.float32)

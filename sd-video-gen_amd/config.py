@@ -62,6 +62,12 @@ def build_parser():
     p.add_argument("--clip_grad_norm", type=float, default=0.0)      # global gradient 2-norm bound, 0: no clipping
     p.add_argument("--weight_decay", type=float, default=0.0)
     p.add_argument("--optimizer", type=str, default="adam", choices=("adam", "adamw"))
+    # the run around the optimizer (all off by default): learning-rate schedule, averaged weights, the training-state file
+    p.add_argument("--lr_schedule", type=str, default="none", choices=("none", "linear", "cosine"))
+    p.add_argument("--warmup_steps", type=int, default=0)            # optimizer steps of linear warm-up from 0
+    p.add_argument("--ema_decay", type=float, default=0.0)           # 0: no averaged weights; else <stem>_ema.pt beside <stem>_test.pt
+    p.add_argument("--save_state", type=bool, default=False)         # <stem>_state.pt after every epoch: what --old_state continues from
+    p.add_argument("--old_state", type=str, default=None)            # with --resume True --old_name: ./checkpoints/<old_state>.pt
     return p
 
 
@@ -78,4 +84,6 @@ def parse_config_args(argv=None):
     if argv is None:
         argv = _OVERRIDE
     args = build_parser().parse_args(argv)
+    if args.old_state and not args.resume:
+        raise ValueError("--old_state continues a run whose weights --resume True --old_name NAME loads: it needs --resume True")
     return load_config(args.config), args

@@ -358,13 +358,16 @@ void xf_attention_bwd(const float* dout, const float* q, int ldq, const float* k
 // criterion of trainers/trainer.py:65-109 on pred (Tt,B,D) rows t >= t0 vs expected (B,Tt,D): losses[5] = {total, mse, l1, gdl, nce}, dpred
 void xf_criterion(const float* pred, const float* expected, float* dpred, float* part, float* part2, float* losses, int Tt, int B, int D, int t0,
                   int fh, int fw, float w_mse, float w_l1, float w_gdl, float alpha, float w_nce, float temperature, hipStream_t s);
+// ema != nullptr: ema[t] is the averaged copy of tensor t of the table and the same loop also does e += (p_new - e) * (1 - ema_decay);
+// nullptr launches the instantiation without that stream (p, m, v are the same bits either way)
 void xf_adam(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chunks, float lr, float beta1, float beta2, float eps, int step,
-             hipStream_t s);
+             float* const* ema, float ema_decay, hipStream_t s);
 // norm[0] = 2-norm of all gradients of the chunk table, in double; part: n_chunks doubles of scratch
 void xf_grad_norm(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chunks, double* part, double* norm, hipStream_t s);
 // Adam / AdamW on g * grad_scale * min(1, max_norm / (grad_scale * norm[0] + 1e-6)) (norm == nullptr: no clipping); g is not written
 void xf_adamw(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chunks, float lr, float beta1, float beta2, float eps, int step,
-              float weight_decay, int decoupled, float grad_scale, float max_norm, const double* norm, hipStream_t s);
+              float weight_decay, int decoupled, float grad_scale, float max_norm, const double* norm, float* const* ema, float ema_decay,
+              hipStream_t s);
 // seq-first MHA core on packed projections: q (Tq,B,ldq) k,v (Tk,B,ldk) -> o (Tq,B,d); mask (Tq,Tk) or null;
 // kpad (B,Tk) or null: additive key-padding bias per batch row
 void xf_attention(const float* q, int ldq, const float* k, const float* v, int ldk, const float* mask,

@@ -578,18 +578,29 @@ __global__ void loss_finish_kernel(const float* __restrict__ part, const float* 
 
 // ---- torch.optim.Adam (no weight decay, no amsgrad), all tensors in one launch ------------------------------------------------
 // chunk c covers elements [off, off + n) of tensor `ten`
+// kEma: the averaged weights ema[ten] ride along, e += (p_new - e) * (1 - ema_decay) on the value the loop has just formed (one more
+// read and one more write of 4 bytes per parameter instead of a pass of its own that reads p again).  The kEma = false instantiation
+// is the kernel without those statements; p, m and v are formed by the same expressions in both.
+template <bool kEma>
 __global__ void __launch_bounds__(256) adam_kernel(const XfAdamTensor* __restrict__ tens, const XfAdamChunk* __restrict__ chunks, float lr, float beta1,
-                                                    float beta2, float eps, float bc1, float bc2_sqrt) {
+                                                    float beta2, float eps, float bc1, float bc2_sqrt, float* const* __restrict__ ema,
+                                                    float ema_decay) {
   const XfAdamChunk ch = chunks[blockIdx.x];
   const XfAdamTensor tn = tens[ch.ten];
   const float step_size = lr / bc1;
+  float* em = nullptr;
+  if constexpr (kEma) em = ema[ch.ten];
   for (int64_t i = ch.off + threadIdx.x; i < ch.off + ch.n; i += 256) {
+    float e = 0.f;
+    if constexpr (kEma) e = em[i];                                          // ahead of the stores: one more load in flight
     const float g = tn.g[i];
     const float m = tn.m[i] + (g - tn.m[i]) * (1.f - beta1);              // exp_avg.lerp_(grad, 1 - beta1)
     const float v = tn.v[i] * beta2 + (1.f - beta2) * g * g;              // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
     tn.m[i] = m; tn.v[i] = v;
     const float denom = sqrtf(v) / bc2_sqrt + eps;
-    tn.p[i] = tn.p[i] - step_size * (m / denom);
+    const float pn = tn.p[i] - step_size * (m / denom);
+    tn.p[i] = pn;
+    if constexpr (kEma) em[i] = e + (pn - e) * (1.f - ema_decay);           // the form of the exp_avg line
   }
 }
 
@@ -651,13 +662,17 @@ __global__ void __launch_bounds__(256) grad_norm_finish_kernel(const double* __r
 // g' = g * s with s = grad_scale * min(1, max_norm / (grad_scale * norm + 1e-6)) (torch.nn.utils.clip_grad_norm_; norm == nullptr:
 // s = grad_scale), read from the device double the norm pass left: no host round trip.  The stored gradient is not written.
 // decay_mul != 1: p *= decay_mul first (AdamW, decay_mul = 1 - lr * wd);  wd_l2 != 0: g' += wd_l2 * p (Adam(weight_decay)).
-// From there on the statements of adam_kernel, so that s == 1 without decay gives its bits.
+// From there on the statements of adam_kernel, so that s == 1 without decay gives its bits; kEma as there.
+template <bool kEma>
 __global__ void __launch_bounds__(256) adamw_kernel(const XfAdamTensor* __restrict__ tens, const XfAdamChunk* __restrict__ chunks, float lr, float beta1,
                                                      float beta2, float eps, float bc1, float bc2_sqrt, float decay_mul, float wd_l2,
-                                                     float grad_scale, float max_norm, const double* __restrict__ norm) {
+                                                     float grad_scale, float max_norm, const double* __restrict__ norm,
+                                                     float* const* __restrict__ ema, float ema_decay) {
   const XfAdamChunk ch = chunks[blockIdx.x];
   const XfAdamTensor tn = tens[ch.ten];
   const float step_size = lr / bc1;
+  float* em = nullptr;
+  if constexpr (kEma) em = ema[ch.ten];
   float s = grad_scale;
   if (norm) {
     const double total = (double)grad_scale * norm[0];
@@ -665,6 +680,8 @@ __global__ void __launch_bounds__(256) adamw_kernel(const XfAdamTensor* __restri
   }
   const bool scaled = s != 1.f, decays = decay_mul != 1.f, l2 = wd_l2 != 0.f;
   for (int64_t i = ch.off + threadIdx.x; i < ch.off + ch.n; i += 256) {
+    float e = 0.f;
+    if constexpr (kEma) e = em[i];
     float g = tn.g[i];
     float p = tn.p[i];
     if (scaled) g = g * s;
@@ -674,7 +691,9 @@ __global__ void __launch_bounds__(256) adamw_kernel(const XfAdamTensor* __restri
     const float v = tn.v[i] * beta2 + (1.f - beta2) * g * g;              // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
     tn.m[i] = m; tn.v[i] = v;
     const float denom = sqrtf(v) / bc2_sqrt + eps;
-    tn.p[i] = p - step_size * (m / denom);
+    const float pn = p - step_size * (m / denom);
+    tn.p[i] = pn;
+    if constexpr (kEma) em[i] = e + (pn - e) * (1.f - ema_decay);           // the form of the exp_avg line
   }
 }
 
@@ -796,10 +815,11 @@ void xf_criterion(const float* pred, const float* expected, float* dpred, float*
 }
 
 void xf_adam(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chunks, float lr, float beta1, float beta2, float eps, int step,
-             hipStream_t s) {
+             float* const* ema, float ema_decay, hipStream_t s) {
   const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));          // torch computes the corrections in double
   const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-  hipLaunchKernelGGL(adam_kernel, dim3(n_chunks), dim3(256), 0, s, tens, chunks, lr, beta1, beta2, eps, bc1, bc2_sqrt);
+  if (ema) hipLaunchKernelGGL(adam_kernel<true>, dim3(n_chunks), dim3(256), 0, s, tens, chunks, lr, beta1, beta2, eps, bc1, bc2_sqrt, ema, ema_decay);
+  else hipLaunchKernelGGL(adam_kernel<false>, dim3(n_chunks), dim3(256), 0, s, tens, chunks, lr, beta1, beta2, eps, bc1, bc2_sqrt, ema, 0.f);
   check_launch("xf_adam");
 }
 
@@ -810,13 +830,18 @@ void xf_grad_norm(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chu
 }
 
 void xf_adamw(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chunks, float lr, float beta1, float beta2, float eps, int step,
-              float weight_decay, int decoupled, float grad_scale, float max_norm, const double* norm, hipStream_t s) {
+              float weight_decay, int decoupled, float grad_scale, float max_norm, const double* norm, float* const* ema, float ema_decay,
+              hipStream_t s) {
   const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));          // as xf_adam
   const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
   // torch.optim.AdamW: param.mul_(1 - lr * weight_decay) with the factor evaluated in double
   const float decay_mul = decoupled ? (float)(1.0 - (double)lr * (double)weight_decay) : 1.f;
   const float wd_l2 = decoupled ? 0.f : weight_decay;
-  hipLaunchKernelGGL(adamw_kernel, dim3(n_chunks), dim3(256), 0, s, tens, chunks, lr, beta1, beta2, eps, bc1, bc2_sqrt, decay_mul, wd_l2, grad_scale,
-                     max_norm, norm);
+  if (ema)
+    hipLaunchKernelGGL(adamw_kernel<true>, dim3(n_chunks), dim3(256), 0, s, tens, chunks, lr, beta1, beta2, eps, bc1, bc2_sqrt, decay_mul, wd_l2,
+                       grad_scale, max_norm, norm, ema, ema_decay);
+  else
+    hipLaunchKernelGGL(adamw_kernel<false>, dim3(n_chunks), dim3(256), 0, s, tens, chunks, lr, beta1, beta2, eps, bc1, bc2_sqrt, decay_mul, wd_l2,
+                       grad_scale, max_norm, norm, ema, 0.f);
   check_launch("xf_adamw");
 }

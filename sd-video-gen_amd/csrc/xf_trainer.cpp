@@ -11,13 +11,16 @@
 #include <cstdlib>
 
 struct XfTrain {
-  struct Slot { float* g = nullptr; float* m = nullptr; float* v = nullptr; int64_t n = 0; };
-  std::unordered_map<std::string, Slot> slots;   // by state_dict name: svg_transformer_tensor only
+  struct Slot { float* g = nullptr; float* m = nullptr; float* v = nullptr; float* e = nullptr; int64_t n = 0; };
+  std::unordered_map<std::string, Slot> slots;   // by state_dict name: svg_transformer_tensor / svg_transformer_set_tensor only
+  std::vector<std::string> names;                 // the tensors of d_tens, in its order
   XfTable<float*> g;                              // Slot::g by role: what backward writes through
   XfAdamTensor* d_tens = nullptr;
   XfAdamChunk* d_chunks = nullptr;
   int n_chunks = 0;
   int step = 0;
+  float** d_ema = nullptr;       // [tensors] Slot::e in the order of d_tens: the averaged weights (nullptr until first asked for)
+  float ema_decay = 0.f;         // > 0: every optimizer step also updates them
   bool has_grads = false;        // a backward pass has been enqueued since the state was created
   double* d_norm_part = nullptr; // [n_chunks] per-chunk sums of squares of the gradient-norm pass
   double* d_norm = nullptr;      // the global gradient 2-norm, where the clipped update reads it
@@ -252,6 +255,7 @@ void ensure_train(svg_ctx* ctx, XfModel* m) {
   HIP_OK(hipMemcpy(tr->d_tens, tens.data(), tens.size() * sizeof(XfAdamTensor), hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(tr->d_chunks, chunks.data(), chunks.size() * sizeof(XfAdamChunk), hipMemcpyHostToDevice));
   tr->n_chunks = (int)chunks.size();
+  tr->names = names;
   m->each_param(tr->g, [&](const std::string& name, std::initializer_list<int64_t>, float*& slot) { slot = tr->slots.at(name).g; });
   m->train = tr.release();
 }
@@ -408,6 +412,31 @@ void loss_pass(svg_ctx* ctx, XfModel* m, const svg_train_cfg& cfg, const float* 
   }
 }
 
+// The training state, and with `ema` the averaged weights (a copy of the parameters as they stand), for the entry points that put
+// state back or configure it.  Whatever is missing is allocated under the device-wide lock after a device-wide synchronisation: an
+// optimizer step still running on another stream has then written the parameters the copy reads.
+XfTrain* state_for_restore(svg_ctx* ctx, XfModel* m, bool ema) {
+  SVG_CHECK(m->ready, "transformer: svg_finalize has not been called");
+  if (m->train && (!ema || m->train->d_ema)) return m->train;
+  DeviceWideScope lk;
+  HIP_OK(hipDeviceSynchronize());
+  ensure_train(ctx, m);
+  XfTrain* tr = m->train;
+  if (!ema) return tr;
+  std::vector<float*> tab;
+  for (auto& n : tr->names) {
+    XfTrain::Slot& sl = tr->slots.at(n);
+    if (!sl.e) sl.e = (float*)tr->dalloc(sl.n * sizeof(float));
+    HIP_OK(hipMemcpy(sl.e, m->ws.get(n).f32, sl.n * sizeof(float), hipMemcpyDeviceToDevice));
+    tab.push_back(sl.e);
+  }
+  float** d = (float**)tr->dalloc(tab.size() * sizeof(float*));
+  HIP_OK(hipMemcpy(d, tab.data(), tab.size() * sizeof(float*), hipMemcpyHostToDevice));
+  HIP_OK(hipDeviceSynchronize());
+  tr->d_ema = d;
+  return tr;
+}
+
 }  // namespace
 
 // caller holds DeviceWideScope when m->train exists (svg_destroy, svg_model_configure, svg_load_weight)
@@ -449,7 +478,8 @@ extern "C" int svg_transformer_adam_step(svg_ctx* ctx, float lr, float beta1, fl
     SVG_CHECK(lr >= 0.f && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "adam step: bad hyper-parameters");
     XfTrain* tr = ctx->xf->train;
     tr->step += 1;
-    xf_adam(tr->d_tens, tr->d_chunks, tr->n_chunks, lr, beta1, beta2, eps, tr->step, (hipStream_t)stream);
+    xf_adam(tr->d_tens, tr->d_chunks, tr->n_chunks, lr, beta1, beta2, eps, tr->step, tr->ema_decay > 0.f ? tr->d_ema : nullptr, tr->ema_decay,
+            (hipStream_t)stream);
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }
@@ -490,7 +520,7 @@ extern "C" int svg_transformer_optim_step(svg_ctx* ctx, const svg_optim_cfg* cfg
     if (clip || grad_norm_out) grad_norm_pass(tr, grad_norm_out ? &norm : nullptr, s);
     tr->step += 1;
     xf_adamw(tr->d_tens, tr->d_chunks, tr->n_chunks, cfg->lr, cfg->beta1, cfg->beta2, cfg->eps, tr->step, cfg->weight_decay, cfg->decoupled != 0,
-             cfg->grad_scale, cfg->max_grad_norm, clip ? tr->d_norm : nullptr, s);
+             cfg->grad_scale, cfg->max_grad_norm, clip ? tr->d_norm : nullptr, tr->ema_decay > 0.f ? tr->d_ema : nullptr, tr->ema_decay, s);
     if (grad_norm_out) *grad_norm_out = (double)cfg->grad_scale * norm;
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
@@ -505,13 +535,64 @@ extern "C" int svg_transformer_tensor(svg_ctx* ctx, int kind, const char* name, 
     SVG_CHECK(numel == w.numel, "svg_transformer_tensor: %s has %lld elements, caller asked for %lld", name, (long long)w.numel, (long long)numel);
     const float* srcp = w.f32;
     if (kind != SVG_TENSOR_PARAM) {
-      SVG_CHECK(kind == SVG_TENSOR_GRAD || kind == SVG_TENSOR_EXP_AVG || kind == SVG_TENSOR_EXP_AVG_SQ, "svg_transformer_tensor: kind %d", kind);
+      SVG_CHECK(kind == SVG_TENSOR_GRAD || kind == SVG_TENSOR_EXP_AVG || kind == SVG_TENSOR_EXP_AVG_SQ || kind == SVG_TENSOR_EMA,
+                "svg_transformer_tensor: kind %d", kind);
       SVG_CHECK(m->train && m->train->slots.count(name), "svg_transformer_tensor: %s has no training state", name);
       const XfTrain::Slot& sl = m->train->slots.at(name);
-      srcp = kind == SVG_TENSOR_GRAD ? sl.g : (kind == SVG_TENSOR_EXP_AVG ? sl.m : sl.v);
+      SVG_CHECK(kind != SVG_TENSOR_EMA || m->train->d_ema,
+                "svg_transformer_tensor: no averaged weights yet (svg_transformer_ema_configure or svg_transformer_set_tensor(SVG_TENSOR_EMA) first)");
+      srcp = kind == SVG_TENSOR_GRAD ? sl.g : (kind == SVG_TENSOR_EXP_AVG ? sl.m : (kind == SVG_TENSOR_EXP_AVG_SQ ? sl.v : sl.e));
     }
     HIP_OK(hipMemcpyAsync(out, srcp, numel * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+extern "C" int svg_transformer_set_tensor(svg_ctx* ctx, int kind, const char* name, const float* data, int64_t numel, void* stream) {
+  try {
+    SVG_CHECK(ctx && ctx->xf && name && data, "svg_transformer_set_tensor: null argument");
+    XfModel* m = ctx->xf;
+    SVG_CHECK(kind == SVG_TENSOR_EXP_AVG || kind == SVG_TENSOR_EXP_AVG_SQ || kind == SVG_TENSOR_EMA,
+              "svg_transformer_set_tensor: kind %d cannot be set (parameters go through svg_load_weight, gradients come from svg_transformer_loss)", kind);
+    SVG_CHECK(m->ws.has(name) && strcmp(name, "positional_encoder.pos_encoding") != 0, "svg_transformer_set_tensor: no trained tensor named %s", name);
+    const Weight& w = m->ws.get(name);
+    SVG_CHECK(numel == w.numel, "svg_transformer_set_tensor: %s has %lld elements, caller gave %lld", name, (long long)w.numel, (long long)numel);
+    XfTrain* tr = state_for_restore(ctx, m, kind == SVG_TENSOR_EMA);
+    const XfTrain::Slot& sl = tr->slots.at(name);
+    float* dst = kind == SVG_TENSOR_EXP_AVG ? sl.m : (kind == SVG_TENSOR_EXP_AVG_SQ ? sl.v : sl.e);
+    HIP_OK(hipMemcpyAsync(dst, data, numel * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+extern "C" int svg_transformer_optim_step_count(svg_ctx* ctx, int64_t* out) {
+  try {
+    SVG_CHECK(ctx && ctx->xf && out, "svg_transformer_optim_step_count: null argument");
+    *out = ctx->xf->train ? ctx->xf->train->step : 0;
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+extern "C" int svg_transformer_set_optim_step_count(svg_ctx* ctx, int64_t step) {
+  try {
+    SVG_CHECK(ctx && ctx->xf, "svg_transformer_set_optim_step_count: model not configured");
+    SVG_CHECK(step >= 0 && step <= 0x7fffffff, "svg_transformer_set_optim_step_count: step %lld out of range", (long long)step);
+    state_for_restore(ctx, ctx->xf, false)->step = (int)step;
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+extern "C" int svg_transformer_ema_configure(svg_ctx* ctx, float decay) {
+  try {
+    SVG_CHECK(ctx && ctx->xf, "svg_transformer_ema_configure: model not configured");
+    SVG_CHECK(decay >= 0.f && decay < 1.f, "svg_transformer_ema_configure: decay %g is outside [0, 1)", decay);
+    if (decay == 0.f) {                                   // updates off; the buffers (if any) keep their values
+      if (ctx->xf->train) ctx->xf->train->ema_decay = 0.f;
+      return 0;
+    }
+    state_for_restore(ctx, ctx->xf, true)->ema_decay = decay;
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }

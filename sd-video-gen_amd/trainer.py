@@ -22,11 +22,21 @@ global gradient 2-norm, ``--weight_decay W`` and ``--optimizer adam|adamw`` choo
 and the update run in the library (``svg_transformer_optim_step``); with clipping on, the pre-clip norm is read back once per step
 and its epoch mean is logged as ``grad_norm_train``.
 
+The run around the optimizer (again all off by default): ``--lr_schedule linear|cosine --warmup_steps N`` drives ``opt.lr`` with a
+``WarmupSchedule`` (the multipliers of transformers' ``get_linear_schedule_with_warmup`` / ``get_cosine_schedule_with_warmup``,
+stepped once per optimizer step: the ``scheduler.step()`` the reference left commented at trainer.py:166; its sketch at :367),
+``--ema_decay D`` keeps averaged weights inside the update kernel and writes them as ``<stem>_ema.pt`` beside ``<stem>_test.pt``,
+``--save_state True`` writes ``<stem>_state.pt`` after every epoch (Adam moments, step count, averaged weights, scheduler
+position, dropout seed, finished epoch, best losses: plain tensors and numbers, ``torch.load(weights_only=True)``), and
+``--resume True --old_name W --old_state S`` continues from both files at the next epoch.  Given the same batches the continued
+run computes what the uninterrupted one would, bit for bit; the sampler's shuffling order is not restored.
+
 Deviations, logging only: the per-term losses logged are those of the F predicted positions (the reference logs the GDL of all
 positions, trainer.py:176) and the contrastive term is reported directly instead of as ``loss - mse - gdl`` (:178).
 """
 import contextlib
 import json
+import math
 import os
 import time
 
@@ -87,6 +97,49 @@ class AdamW(Adam):
         super().__init__(model, lr, betas, eps, weight_decay, max_grad_norm, accumulate)
 
 
+class WarmupSchedule:
+    """Learning-rate schedule on ``opt.lr`` with the members of a torch scheduler: linear warm-up from 0 over `warmup_steps`, then
+    linear decay to 0 at `total_steps` (kind "linear": the multiplier of transformers.get_linear_schedule_with_warmup) or half a
+    cosine (kind "cosine": get_cosine_schedule_with_warmup, num_cycles = 0.5).  Like torch's LambdaLR it applies the multiplier of
+    step 0 when it is created; ``step()`` goes behind every optimizer step."""
+
+    def __init__(self, opt, kind, warmup_steps, total_steps):
+        if kind not in ("linear", "cosine"):
+            raise ValueError("schedule kind must be 'linear' or 'cosine'")
+        if int(warmup_steps) < 0 or int(total_steps) < 0:
+            raise ValueError("warmup_steps and total_steps must be >= 0")
+        self.opt, self.kind, self.warmup_steps, self.total_steps = opt, kind, int(warmup_steps), int(total_steps)
+        self.base_lr = float(opt.lr)
+        self.last_step = 0
+        opt.lr = self.base_lr * self.multiplier(0)
+
+    def multiplier(self, step):
+        if step < self.warmup_steps:
+            return float(step) / float(max(1, self.warmup_steps))
+        if self.kind == "linear":
+            return max(0.0, float(self.total_steps - step) / float(max(1, self.total_steps - self.warmup_steps)))
+        progress = float(step - self.warmup_steps) / float(max(1, self.total_steps - self.warmup_steps))
+        return max(0.0, 0.5 * (1.0 + math.cos(math.pi * 0.5 * 2.0 * progress)))
+
+    def step(self):
+        self.last_step += 1
+        self.opt.lr = self.base_lr * self.multiplier(self.last_step)
+
+    def get_last_lr(self):
+        return [self.opt.lr]
+
+    def state_dict(self):
+        return {"kind": self.kind, "warmup_steps": self.warmup_steps, "total_steps": self.total_steps, "base_lr": self.base_lr,
+                "last_step": self.last_step}
+
+    def load_state_dict(self, sd):
+        if sd["kind"] not in ("linear", "cosine"):
+            raise ValueError("schedule kind must be 'linear' or 'cosine'")
+        self.kind, self.warmup_steps, self.total_steps = sd["kind"], int(sd["warmup_steps"]), int(sd["total_steps"])
+        self.base_lr, self.last_step = float(sd["base_lr"]), int(sd["last_step"])
+        self.opt.lr = self.base_lr * self.multiplier(self.last_step)
+
+
 class Trainer:
     def __init__(self, sd_utils=None):
         self.config, self.args = parse_config_args()
@@ -118,13 +171,13 @@ class Trainer:
         """the capturable side stream of the training step (a stub model on a host without a GPU runs without one)"""
         return torch.cuda.stream(self._stream) if self._stream is not None else contextlib.nullcontext()
 
-    def _loop(self, model, loss_fn, dataloader, frames_to_predict, opt):
+    def _loop(self, model, loss_fn, dataloader, frames_to_predict, opt, scheduler=None):
         sums = {"total": 0.0, "mse": 0.0, "l1": 0.0, "gdl": 0.0, "contrastive": 0.0}
         n = 0
         train = opt is not None
         accumulate = max(1, int(getattr(opt, "accumulate", 1))) if train else 1
         pending = 0                    # micro-batches whose gradients are summed in the library and not yet applied
-        norms = []
+        norms, lrs = [], []
         for index_list, batch in dataloader:
             new_batch = self.sd_utils.encode_batch(batch, use_sos=True)                  # trainer.py:123
             new_batch = torch.as_tensor(new_batch).to(self.device)
@@ -139,7 +192,7 @@ class Trainer:
                 terms = model.training_loss(cfg, new_batch, backward=(1 if pending == 0 else _lib.SVG_BACKWARD_ACCUMULATE) if train else 0)
                 pending += 1
                 if train and pending == accumulate:
-                    pending = self._step(opt, pending, norms)                              # :165
+                    pending = self._step(opt, pending, norms, scheduler, lrs)              # :165, :166
             if self._stream is not None:
                 self._stream.synchronize()
             for k in sums:
@@ -147,32 +200,41 @@ class Trainer:
             n += 1
         if train and pending:                                                              # ragged tail of the epoch: a step of its own
             with self._on_stream():
-                pending = self._step(opt, pending, norms)
+                pending = self._step(opt, pending, norms, scheduler, lrs)
             if self._stream is not None:
                 self._stream.synchronize()
         avg = {k: v / max(n, 1) for k, v in sums.items()}
         if norms:
             avg["grad_norm"] = sum(norms) / len(norms)
+        if lrs:
+            avg["lr"] = lrs[-1]
         return avg
 
     @staticmethod
-    def _step(opt, n, norms):
-        """one optimizer step on the mean of the n accumulated micro-batch gradients -> 0 (nothing pending)"""
+    def _step(opt, n, norms, scheduler=None, lrs=None):
+        """one optimizer step on the mean of the n accumulated micro-batch gradients -> 0 (nothing pending); a scheduler is stepped
+        once behind it (trainer.py:166) and the rate the step used is noted"""
+        if scheduler is not None and lrs is not None:
+            lrs.append(opt.lr)
         if getattr(opt, "accumulate", 1) > 1:
             opt.step(n)
         else:
             opt.step()
         if getattr(opt, "max_grad_norm", 0.0) > 0 and getattr(opt, "grad_norm", None) is not None:
             norms.append(opt.grad_norm)
+        if scheduler is not None:
+            scheduler.step()
         return 0
 
     def train_loop(self, model, opt, scheduler, loss_fn, dataloader, frames_to_predict):
         model.train()
-        avg = self._loop(model, loss_fn, dataloader, frames_to_predict, opt)
+        avg = self._loop(model, loss_fn, dataloader, frames_to_predict, opt, scheduler)
         rec = {"train_loss": avg["total"], "mse_train": avg["mse"], "L1_train": avg["l1"], "gdl_train": avg["gdl"],
                "contrastive_train": avg["contrastive"]}
         if "grad_norm" in avg:
             rec["grad_norm_train"] = avg["grad_norm"]          # pre-clip, mean over the epoch's optimizer steps (clipping on only)
+        if "lr" in avg:
+            rec["lr"] = avg["lr"]                              # the rate of the epoch's last optimizer step (with a scheduler only)
         self.log(rec)
         return avg["total"]
 
@@ -190,6 +252,70 @@ class Trainer:
         print(f"Training loss: {train_loss:.4f}")
         print(f"Validation loss: {validation_loss:.4f}")
         return train_loss, validation_loss
+
+    # ---- the training-state file ---------------------------------------------------------------------------------------------
+    def training_state(self, model, opt, scheduler, epoch, best_train_loss, best_val_loss):
+        """everything beside the weights that the next epoch depends on, as plain tensors / numbers / strings"""
+        return {"optimizer": model.optimizer_state(),
+                "hyper": dict(self.training_state_hyper(opt), lr=float(opt.lr)),
+                "scheduler": scheduler.state_dict() if scheduler is not None else None,
+                "seed": int(self.seed), "epoch": int(epoch), "best_train_loss": float(best_train_loss), "best_val_loss": float(best_val_loss)}
+
+    def load_training_state(self, state, model, opt, scheduler):
+        """after model.load_state_dict(): puts training_state() back -> (finished epoch, best_train_loss, best_val_loss).  The
+        optimizer's hyper-parameters stay those of this run's flags; a difference from the saved ones is printed."""
+        model.load_optimizer_state(state["optimizer"])
+        if scheduler is not None and state["scheduler"] is not None:
+            scheduler.load_state_dict(state["scheduler"])
+        elif (scheduler is None) != (state["scheduler"] is None):
+            print("note: the saved run %s a learning-rate schedule, this one %s" % (("had", "has none") if scheduler is None else ("had no", "has one")))
+        mine = self.training_state_hyper(opt)
+        for k, v in state["hyper"].items():
+            if k != "lr" and mine.get(k) != v:
+                print("note: %s was %s in the saved run and is %s now" % (k, v, mine.get(k)))
+        self.seed = int(state["seed"])
+        return int(state["epoch"]), float(state["best_train_loss"]), float(state["best_val_loss"])
+
+    @staticmethod
+    def training_state_hyper(opt):
+        return {"optimizer": "adamw" if opt.decoupled else "adam", "beta1": float(opt.betas[0]), "beta2": float(opt.betas[1]),
+                "eps": float(opt.eps), "weight_decay": float(opt.weight_decay), "max_grad_norm": float(opt.max_grad_norm),
+                "accumulate": int(opt.accumulate)}
+
+    def run_epochs(self, args, model, opt, scheduler, loss_fn, train_loader, test_loader, frames_to_predict, epochs, first_epoch=1,
+                   best_train_loss=1e10, best_val_loss=1e10):
+        """epochs first_epoch .. epochs of trainer.py:449-480: fit, log, checkpoints <stem>_{train,test}.pt; with --ema_decay the
+        averaged weights as <stem>_ema.pt wherever <stem>_test.pt is written, with --save_state <stem>_state.pt after every epoch"""
+        stem = "./checkpoints/" + args.config + "_" + str(self.index)
+        tag = args.config + "_" + str(self.index)
+        for epoch in range(first_epoch, epochs + 1):
+            print("-" * 25, f"Epoch {epoch}", "-" * 25)
+            t0 = time.time()
+            train_loss, validation_loss = self.fit(model=model, opt=opt, scheduler=scheduler, loss_fn=loss_fn, train_dataloader=train_loader,
+                                                   val_dataloader=test_loader, frames_to_predict=frames_to_predict)
+            self.log({"epoch": epoch, "seconds": time.time() - t0})
+            wrote_test = True
+            if args.save_best:                                   # trainer.py:469-477
+                wrote_test = False
+                if train_loss < best_train_loss:
+                    best_train_loss = train_loss
+                    torch.save(model.state_dict(), stem + "_train.pt")
+                    print("model saved as " + tag + "_train.pt (best train loss)")
+                if validation_loss < best_val_loss:
+                    best_val_loss = validation_loss
+                    torch.save(model.state_dict(), stem + "_test.pt")
+                    print("model saved as " + tag + "_test.pt (best test loss)")
+                    wrote_test = True
+            else:                                                # :478-480
+                torch.save(model.state_dict(), stem + "_test.pt")
+                print("model saved as " + tag + "_test.pt")
+            if wrote_test and args.ema_decay > 0:
+                torch.save(model.ema_state_dict(), stem + "_ema.pt")
+                print("averaged weights saved as " + tag + "_ema.pt")
+            if args.save_state:
+                torch.save(self.training_state(model, opt, scheduler, epoch, best_train_loss, best_val_loss), stem + "_state.pt")
+                print("training state saved as " + tag + "_state.pt")
+        return best_train_loss, best_val_loss
 
 
 def _first(v):
@@ -223,6 +349,33 @@ def make_optimizer(args, model, lr):
                                                           accumulate=args.grad_accum)
 
 
+def make_scheduler(args, opt, epochs, batches_per_epoch):
+    """--lr_schedule none -> None (the reference's loop); else a WarmupSchedule over epochs x optimizer steps per epoch, an epoch's
+    ragged tail being a step of its own (the sketch at trainer.py:367: get_linear_schedule_with_warmup(opt, 15, epochs*len(loader)))"""
+    if args.lr_schedule == "none":
+        return None
+    steps_per_epoch = -(-int(batches_per_epoch) // max(1, int(args.grad_accum)))
+    return WarmupSchedule(opt, args.lr_schedule, args.warmup_steps, int(epochs) * steps_per_epoch)
+
+
+def prepare_run(trainer, args, model, lr, epochs, batches_per_epoch):
+    """what stands between a freshly built model and its first epoch: --resume's weights (trainer.py:360-362), the optimizer, the
+    schedule, --old_state's training state and the averaged weights -> (opt, scheduler, first epoch, best train loss, best val loss).
+    The order is the library's: uploading weights drops its training state, so the weights come first and the state after them."""
+    if args.resume:
+        model.load_state_dict(torch.load("./checkpoints/" + args.old_name + ".pt", weights_only=True))
+    opt = make_optimizer(args, model, lr)
+    scheduler = make_scheduler(args, opt, epochs, batches_per_epoch)
+    first_epoch, best_train_loss, best_val_loss = 1, 1e10, 1e10
+    if args.old_state:
+        state = torch.load("./checkpoints/" + args.old_state + ".pt", weights_only=True)
+        done, best_train_loss, best_val_loss = trainer.load_training_state(state, model, opt, scheduler)
+        first_epoch = done + 1
+    if args.ema_decay > 0:                                   # restored averaged weights are kept; otherwise they start as the weights
+        model.ema_configure(args.ema_decay)
+    return opt, scheduler, first_epoch, best_train_loss, best_val_loss
+
+
 def main():
     config, args = parse_config_args()
     frames_per_clip, frames_to_predict = _first(config.FRAMES_PER_CLIP), _first(config.FRAMES_TO_PREDICT)
@@ -234,9 +387,6 @@ def main():
                         num_encoder_layers=_first(config.NUM_ENCODER_LAYERS), num_decoder_layers=_first(config.NUM_DECODER_LAYERS),
                         dropout_p=_first(config.DROPOUT_P))
     print("number of parameters: ", sum(p.numel() for p in model.parameters() if p.requires_grad))
-    if args.resume:
-        model.load_state_dict(torch.load("./checkpoints/" + args.old_name + ".pt", weights_only=True))
-    opt = make_optimizer(args, model, lr)
     loss_fn = trainer.criterion(use_mse=_first(config.USE_MSE), use_L1=_first(getattr(config, "USE_L1", False)), use_gdl=_first(config.USE_GDL),
                                 lambda_gdl=_first(config.LAMBDA_GDL), alpha=_first(config.ALPHA),
                                 use_contrastive=_first(getattr(config, "USE_CONTRASTIVE", False)),
@@ -244,26 +394,9 @@ def main():
     if loss_fn is None:
         raise ValueError("Invalid loss function combination")
     train_loader, test_loader = make_loaders(args, config, frames_per_clip, frames_to_predict, stride, batch_size, epoch_ratio, num_workers)
-    stem = "./checkpoints/" + args.config + "_" + str(trainer.index)
-    best_train_loss = best_val_loss = 1e10
-    for epoch in range(1, epochs + 1):
-        print("-" * 25, f"Epoch {epoch}", "-" * 25)
-        t0 = time.time()
-        train_loss, validation_loss = trainer.fit(model=model, opt=opt, scheduler=None, loss_fn=loss_fn, train_dataloader=train_loader,
-                                                  val_dataloader=test_loader, frames_to_predict=frames_to_predict)
-        trainer.log({"epoch": epoch, "seconds": time.time() - t0})
-        if args.save_best:                                   # trainer.py:469-477
-            if train_loss < best_train_loss:
-                best_train_loss = train_loss
-                torch.save(model.state_dict(), stem + "_train.pt")
-                print("model saved as " + args.config + "_" + str(trainer.index) + "_train.pt (best train loss)")
-            if validation_loss < best_val_loss:
-                best_val_loss = validation_loss
-                torch.save(model.state_dict(), stem + "_test.pt")
-                print("model saved as " + args.config + "_" + str(trainer.index) + "_test.pt (best test loss)")
-        else:                                                # :478-480
-            torch.save(model.state_dict(), stem + "_test.pt")
-            print("model saved as " + args.config + "_" + str(trainer.index) + "_test.pt")
+    opt, scheduler, first_epoch, best_train_loss, best_val_loss = prepare_run(trainer, args, model, lr, epochs, len(train_loader))
+    trainer.run_epochs(args, model, opt, scheduler, loss_fn, train_loader, test_loader, frames_to_predict, epochs, first_epoch,
+                       best_train_loss, best_val_loss)
 
 
 if __name__ == "__main__":

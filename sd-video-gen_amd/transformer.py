@@ -95,6 +95,60 @@ class LibraryTraining:
         self._lib_ahead = False
         self._uploaded_version = self._weights_version()      # the copy in the library IS these parameters: no re-upload
 
+    # ---- what a continued run needs: the optimizer's state, and the averaged weights -------------------------------------
+    def _trained_names(self):
+        return [n for n, _ in self.named_parameters() if not n.startswith("sent_transformer.")]
+
+    def optimizer_state(self):
+        """{"step": optimizer steps taken, "exp_avg": {name: tensor}, "exp_avg_sq": {...}, "ema": {...} or None (no averaged weights)}
+        read from the library, as CPU tensors under state_dict keys"""
+        ctx = self._sync_weights()
+        prm = dict(self.named_parameters())
+        names = self._trained_names()
+        read = lambda kind: {n: ctx.transformer_tensor(n, prm[n], kind) for n in names}
+        try:
+            moments = read(_lib.SVG_TENSOR_EXP_AVG), read(_lib.SVG_TENSOR_EXP_AVG_SQ)
+        except ValueError:                  # SVG_ERR_INVALID: no training state yet -- what it is created with
+            moments = tuple({n: torch.zeros(tuple(prm[n].shape)) for n in names} for _ in range(2))
+        try:
+            ema = read(_lib.SVG_TENSOR_EMA)
+        except ValueError:                  # no averaged weights
+            ema = None
+        return {"step": ctx.transformer_optim_step_count(), "exp_avg": moments[0], "exp_avg_sq": moments[1], "ema": ema}
+
+    def load_optimizer_state(self, state):
+        """puts optimizer_state() back: the weights first (uploading them drops the library's training state), then the moments,
+        the averaged weights (if any) and the step count.  Call it after load_state_dict(); ema_configure() after it."""
+        names = self._trained_names()
+        for key in ("exp_avg", "exp_avg_sq"):
+            if set(state[key]) != set(names):
+                raise ValueError("optimizer state: %s does not hold exactly this model's parameters" % key)
+        if state.get("ema") is not None and set(state["ema"]) != set(names):
+            raise ValueError("optimizer state: ema does not hold exactly this model's parameters")
+        ctx = self._sync_weights()
+        for key, kind in (("exp_avg", _lib.SVG_TENSOR_EXP_AVG), ("exp_avg_sq", _lib.SVG_TENSOR_EXP_AVG_SQ), ("ema", _lib.SVG_TENSOR_EMA)):
+            if state.get(key) is None:
+                continue
+            for n in names:
+                ctx.transformer_set_tensor(n, state[key][n], kind)
+        ctx.transformer_set_optim_step_count(int(state["step"]))
+
+    def ema_configure(self, decay):
+        """0 < decay < 1: every optimizer step from now on also moves the averaged weights, e += (p_new - e) * (1 - decay), inside
+        the update kernel (they start as a copy of the current parameters); 0: updates off, values kept.  The averaged weights
+        belong to the library's training state: configure after the weights are final (load_state_dict re-uploads and drops it)."""
+        self._sync_weights().transformer_ema_configure(decay)
+
+    def ema_state_dict(self):
+        """the averaged weights under state_dict keys (loadable into a fresh model); buffers and the text variant's frozen
+        sent_transformer.* entries are the module's own"""
+        ctx = self._sync_weights()
+        prm = dict(self.named_parameters())
+        out = self.state_dict()
+        for n in self._trained_names():
+            out[n] = ctx.transformer_tensor(n, prm[n], _lib.SVG_TENSOR_EMA).to(out[n].device)
+        return out
+
     def grad_of(self, name):
         """gradient of parameter `name` from the last training_loss(backward=True), as a CPU tensor"""
         return self._ctx.transformer_tensor(name, dict(self.named_parameters())[name], _lib.SVG_TENSOR_GRAD)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Device-event timings of the optimizer tail of the training step at the `bench.py --train` shape (the config's own batch):
 
-    python tools/train_optim_bench.py [--config 1_16_kitti_L1_64] [--reps 30] [--rounds 3] [--out FILE]
+    python tools/train_optim_bench.py [--config 1_16_kitti_L1_64] [--reps 30] [--rounds 3] [--ema] [--out FILE]
 
   adam            svg_transformer_adam_step (adam_kernel: 7 streams of 4 bytes per parameter)
   optim_plain     svg_transformer_optim_step without decay / clipping / scaling (adamw_kernel alone, the same 7 streams)
@@ -10,6 +10,11 @@
   grad_norm       svg_transformer_grad_norm, events around the call (norm pass + finish + the 8-byte copy back)
   loss_bw1 / 2    one svg_transformer_loss call with backward = 1 / SVG_BACKWARD_ACCUMULATE
   step_accum1 / 4 optimizer step over 1 / 4 micro-batches (loss calls + update), per micro-batch
+  --ema adds, in the same process and the same rounds:
+  adam_ema / adamw_ema / adamw_clip_ema   the same three steps with svg_transformer_ema_configure(0.999): the kernels' EMA
+                  instantiation, 9 streams of 4 bytes per parameter
+  lerp_pass       what an unfused EMA would add to a step: e.lerp_(p, 1 - decay) over one flat f32 tensor of the model's size
+                  (torch's element-wise kernel: 3 streams of 4 bytes per parameter, no chunk table)
 
 Every figure is the mean over `reps` enqueue-only calls between two events on the capturable side stream (the loss calls replay
 their hipGraph there), after a warm-up of each shape; the rounds alternate all measurements so that the spread is visible."""
@@ -27,6 +32,7 @@ def main():
     ap.add_argument("--config", default="1_16_kitti_L1_64")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--ema", action="store_true", help="also time the optimizer steps with averaged weights on, and a stand-alone lerp pass")
     ap.add_argument("--out", default=None, help="also write the JSON record to this file")
     args = ap.parse_args()
     import torch
@@ -80,6 +86,17 @@ def main():
         "step_accum4": (lambda: accum(4), 4),
     }
 
+    work_ema = {}
+    if args.ema:
+        decay = 0.999
+        flat_p, flat_e = torch.randn(n_par, device="cuda"), torch.randn(n_par, device="cuda")
+        work["lerp_pass"] = (lambda: flat_e.lerp_(flat_p, 1.0 - decay), 1)
+        work_ema = {"adam_ema": work["adam"], "adamw_ema": work["adamw"], "adamw_clip_ema": work["adamw_clip"]}
+
+    def ema_on(on):
+        side.synchronize()
+        model.ema_configure(decay if on else 0.0)       # (synchronises the device; the first call allocates the averaged weights)
+
     def timed(fn, reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         with torch.cuda.stream(side):
@@ -96,10 +113,22 @@ def main():
             for _ in range(3):
                 fn()
     side.synchronize()
-    ms = {k: [] for k in work}
+    if work_ema:
+        ema_on(True)
+        with torch.cuda.stream(side):
+            for fn, _ in work_ema.values():
+                for _ in range(3):
+                    fn()
+        ema_on(False)
+    ms = {k: [] for k in list(work) + list(work_ema)}
     for _ in range(args.rounds):
         for k, (fn, per) in work.items():
             ms[k].append(timed(fn, max(3, args.reps // per)) / per)
+        if work_ema:
+            ema_on(True)
+            for k, (fn, per) in work_ema.items():
+                ms[k].append(timed(fn, max(3, args.reps // per)) / per)
+            ema_on(False)
     med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
     gb = n_par * 4 / 1e9
     rec = {"config": args.config, "parameters": n_par, "batch": [B, T], "reps": args.reps, "library": _lib.source_hash(),
@@ -109,6 +138,15 @@ def main():
            "norm_pass_ms_by_difference": med["adamw_clip"] - med["adamw"], "norm_pass_TBps_by_difference": gb / max(med["adamw_clip"] - med["adamw"], 1e-9),
            "grad_norm_call_TBps": gb / med["grad_norm"],
            "accumulate_extra_ms": med["loss_bw2"] - med["loss_bw1"]}
+    if args.ema:
+        spread = lambda k: (max(ms[k]) - min(ms[k])) / med[k]
+        rec.update({"ema_decay": decay, "adam_ema_TBps": 9 * gb / med["adam_ema"], "adamw_ema_TBps": 9 * gb / med["adamw_ema"],
+                    "lerp_pass_TBps": 3 * gb / med["lerp_pass"],
+                    "fused_ema_extra_ms": {"adam": med["adam_ema"] - med["adam"], "adamw": med["adamw_ema"] - med["adamw"]},
+                    "unfused_sum_ms": {"adam": med["adam"] + med["lerp_pass"], "adamw": med["adamw"] + med["lerp_pass"]},
+                    "fused_not_slower_than_unfused": {"adam": med["adam_ema"] <= med["adam"] + med["lerp_pass"],
+                                                      "adamw": med["adamw_ema"] <= med["adamw"] + med["lerp_pass"]},
+                    "round_spread_rel": {k: round(spread(k), 4) for k in ("adam", "adamw", "adam_ema", "adamw_ema", "lerp_pass")}})
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
