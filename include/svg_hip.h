@@ -441,6 +441,42 @@ int svg_op_xattn_fused(svg_ctx* ctx, const uint16_t* x, const uint16_t* a, const
                        const float* wo, const float* bo, uint16_t* out, int M, int rows_per_sample, int L, void* stream);
 /* dropout mask of one site of the training step: out[i] = 1/(1-p) (kept) or 0, i < n (tests regenerate the masks with it) */
 int svg_op_dropout_mask(svg_ctx* ctx, uint64_t seed, int site, float p, float* out, int64_t n, void* stream);
+/* The training-step kernels of the latent Transformer one by one (test hooks: each is its launcher, nothing is added).  f32 device
+ * buffers; a dropout site is (seed, site, p) as in svg_op_dropout_mask, which draws the same mask; p = 0: no dropout.
+ * svg_op_xf_gemm_tn: dW[N][K] (+)= dY[M][N]^T X[M][K], db[N] (+)= column sums of dY (db may be NULL); ldy / ldx: row strides of dY / X.
+ * svg_op_xf_gemm_nn: out[M][K] = gate(dY[M][N] W[N][K]) + add; gate (M,K) or NULL: x * (gate > 0 ? gate_scale : 0); add (M,K) or NULL,
+ *   may be `out` itself; *splits (or NULL) receives the number of contraction chunks the launch used (the slabs come from the arena).
+ * svg_op_xf_relu_drop: r = dropout(max(h, 0)).
+ * svg_op_xf_add_ln_train: y = LayerNorm(x + dropout(r)) gamma + beta over rows of d <= 3072 (r may be NULL); keeps xhat (M,d), rstd (M).
+ * svg_op_xf_ln_bwd: dz = rstd (g dy - mean(g dy) - xhat mean(g dy xhat)); dz_drop (or NULL) = dz * the site's mask; dgamma / dbeta (d)
+ *   (+)= column sums of dy xhat / dy.
+ * svg_op_xf_attention_train: q (Tq,B,ldq), k / v (Tk,B,ldk), heads * hd columns each; mask (Tq,Tk) additive or NULL; P (B,heads,Tq,Tk)
+ *   = softmax(q k^T / sqrt(hd) + mask), o (Tq,B,heads*hd) = dropout(P) v.  T <= 32.
+ * svg_op_xf_attention_bwd: dq (Tq,B,lddq), dk / dv (Tk,B,lddk) from dout (Tq,B,heads*hd), q, k, v and the kept P.
+ * svg_op_xf_embed_post_train: emb (B*T, d - d_txt) -> y (T,B,d) = dropout(v * scale + pe[pe_row[b]]), the last d_txt channels from text (B,d_txt).
+ * svg_op_xf_embed_post_bwd: de (B*T, d_img) = dy (T,B,d)[:, :, :d_img] * mask * scale.
+ * svg_op_xf_criterion: pred (Tt,B,D) rows t >= t0 against expected (B,Tt,D), D = 4 fh fw; dpred (Tt,B,D) device (rows < t0: zero),
+ *   losses: FIVE HOST floats {total, mse, l1, gdl, contrastive}; synchronises the stream. */
+int svg_op_xf_gemm_tn(svg_ctx* ctx, const float* dY, int ldy, const float* X, int ldx, float* dW, float* db, int M, int N, int K,
+                      int accumulate, void* stream);
+int svg_op_xf_gemm_nn(svg_ctx* ctx, const float* dY, int ldy, const float* W, float* out, int M, int N, int K, const float* gate,
+                      float gate_scale, const float* add, int* splits, void* stream);
+int svg_op_xf_relu_drop(svg_ctx* ctx, const float* h, float* r, int64_t n, uint64_t seed, int site, float p, void* stream);
+int svg_op_xf_add_ln_train(svg_ctx* ctx, const float* x, const float* r, uint64_t seed, int site, float p, const float* gamma,
+                           const float* beta, float* y, float* xhat, float* rstd, int M, int d, float eps, void* stream);
+int svg_op_xf_ln_bwd(svg_ctx* ctx, const float* dy, const float* xhat, const float* rstd, const float* gamma, float* dz, float* dz_drop,
+                     uint64_t seed, int site, float p, float* dgamma, float* dbeta, int M, int d, int accumulate, void* stream);
+int svg_op_xf_attention_train(svg_ctx* ctx, const float* q, int ldq, const float* k, const float* v, int ldk, const float* mask, float* o,
+                              float* P, int Tq, int Tk, int B, int heads, int hd, uint64_t seed, int site, float p, void* stream);
+int svg_op_xf_attention_bwd(svg_ctx* ctx, const float* dout, const float* q, int ldq, const float* k, const float* v, int ldk,
+                            const float* P, float* dq, int lddq, float* dk, float* dv, int lddk, int Tq, int Tk, int B, int heads, int hd,
+                            uint64_t seed, int site, float p, void* stream);
+int svg_op_xf_embed_post_train(svg_ctx* ctx, const float* emb, const float* pe, const int32_t* pe_row, const float* text, int d_txt,
+                               float* y, int B, int T, int d, float scale, uint64_t seed, int site, float p, void* stream);
+int svg_op_xf_embed_post_bwd(svg_ctx* ctx, const float* dy, float* de, int B, int T, int d, int d_img, float scale, uint64_t seed, int site,
+                             float p, void* stream);
+int svg_op_xf_criterion(svg_ctx* ctx, const float* pred, const float* expected, float* dpred, float* losses, int Tt, int B, int D, int t0,
+                        int fh, int fw, float w_mse, float w_l1, float w_gdl, float alpha, float w_nce, float temperature, void* stream);
 /* MX block-scaled fp8 (BASELINE configs[4]): OCP e4m3 elements with one E8M0 scale per 32 consecutive K elements.
  * svg_op_quant_mx: x (rows,K) bf16 -> q (rows,K) e4m3 bytes, scales (rows,K/32) bytes; shared exponent floor(log2(amax)) - 8,
  * round to nearest even, saturating at +-448 (OCP MX v1.0).  K % 32 == 0. */

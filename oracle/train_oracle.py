@@ -22,11 +22,18 @@ import torch.nn.functional as F
 from . import transformer_oracle as TO
 
 
-def gradient_difference_loss(x, y, alpha=1):
-    """trainers/trainer.py:65-86.  x, y (T, B, D_lat) -> scalar."""
+def _feat_hw(feat):
+    """feat: the side of a square feature map, or (h, w)"""
+    return tuple(feat) if isinstance(feat, (tuple, list)) else (feat, feat)
+
+
+def gradient_difference_loss(x, y, alpha=1, feat=None):
+    """trainers/trainer.py:65-86.  x, y (T, B, D_lat) -> scalar.  feat: (h, w) of a map that is not square (the reference takes the
+    square root of D_lat / 4; the library's criterion takes feat_h and feat_w)."""
     v = int((x.shape[-1] // 4) ** 0.5)
-    fx = x.reshape(x.shape[0], x.shape[1], 4, v, v)
-    fy = y.reshape(y.shape[0], x.shape[1], 4, v, v)
+    h, w = (v, v) if feat is None else _feat_hw(feat)
+    fx = x.reshape(x.shape[0], x.shape[1], 4, h, w)
+    fy = y.reshape(y.shape[0], x.shape[1], 4, h, w)
     vx = fx[:, :, :, 1:, :] - fx[:, :, :, :-1, :]
     vy = fy[:, :, :, 1:, :] - fy[:, :, :, :-1, :]
     hx = fx[:, :, :, :, 1:] - fx[:, :, :, :, :-1]
@@ -50,10 +57,11 @@ def bi_patch_nce(pred_f, gt_f, temperature=0.07):
 
 def criterion(x, y, frames_to_predict, feat, w_mse=0.0, w_l1=0.0, w_gdl=0.0, alpha=1, w_contrastive=0.0, temperature=0.07):
     """trainers/trainer.py:91-109 on x = pred[-F:], y = y_expected[-F:] (F, B, D_lat).  -> (total, dict of the terms)."""
-    terms = {"mse": F.mse_loss(x, y), "l1": F.l1_loss(x, y), "gdl": gradient_difference_loss(x, y, alpha)}
+    fh, fw = _feat_hw(feat)
+    terms = {"mse": F.mse_loss(x, y), "l1": F.l1_loss(x, y), "gdl": gradient_difference_loss(x, y, alpha, None if fh == fw else (fh, fw))}
     if w_contrastive:
-        px = x.permute(1, 0, 2).reshape(-1, frames_to_predict, 4, feat, feat)
-        py = y.permute(1, 0, 2).reshape(-1, frames_to_predict, 4, feat, feat)
+        px = x.permute(1, 0, 2).reshape(-1, frames_to_predict, 4, fh, fw)
+        py = y.permute(1, 0, 2).reshape(-1, frames_to_predict, 4, fh, fw)
         terms["contrastive"] = bi_patch_nce(px, py, temperature)
     else:
         terms["contrastive"] = torch.zeros(())

@@ -126,6 +126,16 @@ SIGNATURES = {
     "svg_op_ff_fused": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "svg_op_xattn_fused": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp],
     "svg_op_dropout_mask": [_vp, C.c_uint64, _i, _f, _vp, _i64, _vp],
+    "svg_op_xf_gemm_tn": [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp],
+    "svg_op_xf_gemm_nn": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _f, _vp, C.POINTER(_i), _vp],
+    "svg_op_xf_relu_drop": [_vp, _vp, _vp, _i64, C.c_uint64, _i, _f, _vp],
+    "svg_op_xf_add_ln_train": [_vp, _vp, _vp, C.c_uint64, _i, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp],
+    "svg_op_xf_ln_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _i, _f, _vp, _vp, _i, _i, _i, _vp],
+    "svg_op_xf_attention_train": [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_uint64, _i, _f, _vp],
+    "svg_op_xf_attention_bwd": [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint64, _i, _f, _vp],
+    "svg_op_xf_embed_post_train": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _f, C.c_uint64, _i, _f, _vp],
+    "svg_op_xf_embed_post_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _f, C.c_uint64, _i, _f, _vp],
+    "svg_op_xf_criterion": [_vp, _vp, _vp, _vp, C.POINTER(_f), _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp],
     "svg_op_conv3x3_mx": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "svg_op_quant_mx": [_vp, _vp, _vp, _vp, _i64, _i, _vp],
     "svg_op_gemm_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],

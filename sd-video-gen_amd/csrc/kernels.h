@@ -341,6 +341,7 @@ void xf_drop_mask(const XfDrop d, float* out, int64_t n, hipStream_t s);
 void xf_gemm_tn(const float* dY, int ldy, const float* X, int ldx, float* dW, float* db, int M, int N, int K, int accumulate, hipStream_t s);
 // out[M][K] = gate(dY[M][N] W[N][K]) + add;  gate (or null): x * (gate[i] > 0 ? gate_scale : 0);  slabs: xf_gemm_nn_slab_floats() floats
 int64_t xf_gemm_nn_slab_floats(int M, int N, int K);
+int xf_gemm_nn_splits(int N, int K);          // Z: the contraction is cut into Z chunks of a multiple of 64 (tail chunks may be empty)
 void xf_gemm_nn(const float* dY, int ldy, const float* W, float* slabs, float* out, int M, int N, int K, const float* gate, float gate_scale,
                 const float* add, hipStream_t s);
 void xf_relu_drop(const float* h, float* r, int64_t n, const XfDrop d, hipStream_t s);

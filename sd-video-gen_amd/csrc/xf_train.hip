@@ -699,6 +699,9 @@ __global__ void __launch_bounds__(256) adamw_kernel(const XfAdamTensor* __restri
 
 constexpr int kAttnTrainLds = 150 * 1024;   // + 2 x 4.3 KiB of static score tiles: under the 160 KiB of a CU
 
+// the GEMM kernels move float4s: every operand starts on a 16-byte boundary (null: an operand that is not there)
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 int grid_for(int64_t n, int per_block) { return (int)std::min<int64_t>(4096, (n + per_block - 1) / per_block); }
 
 }  // namespace
@@ -716,7 +719,10 @@ void xf_drop_mask(const XfDrop d, float* out, int64_t n, hipStream_t s) {
 }
 
 void xf_gemm_tn(const float* dY, int ldy, const float* X, int ldx, float* dW, float* db, int M, int N, int K, int accumulate, hipStream_t s) {
+  SVG_CHECK(M > 0 && N > 0 && K > 0, "xf_gemm_tn: empty problem %d x %d x %d", M, N, K);
   SVG_CHECK(N % 4 == 0 && K % 4 == 0 && ldy % 4 == 0 && ldx % 4 == 0, "xf_gemm_tn: N %d / K %d / strides must be multiples of 4", N, K);
+  SVG_CHECK(ldy >= N && ldx >= K, "xf_gemm_tn: row strides %d / %d are shorter than the rows %d / %d", ldy, ldx, N, K);
+  SVG_CHECK(aligned16(dY) && aligned16(X) && aligned16(dW) && aligned16(db), "xf_gemm_tn: an operand does not start on a 16-byte boundary");
   hipLaunchKernelGGL(xf_gemm_tn_kernel, dim3(cdiv(K, 128), cdiv(N, 128)), dim3(256), 0, s, dY, ldy, X, ldx, dW, db, M, N, K, accumulate);
   check_launch("xf_gemm_tn");
 }
@@ -730,7 +736,11 @@ int64_t xf_gemm_nn_slab_floats(int M, int N, int K) { return (int64_t)xf_gemm_nn
 
 void xf_gemm_nn(const float* dY, int ldy, const float* W, float* slabs, float* out, int M, int N, int K, const float* gate, float gate_scale,
                 const float* add, hipStream_t s) {
+  SVG_CHECK(M > 0 && N > 0 && K > 0, "xf_gemm_nn: empty problem %d x %d x %d", M, N, K);
   SVG_CHECK(N % 4 == 0 && K % 4 == 0 && ldy % 4 == 0, "xf_gemm_nn: N %d / K %d / stride must be multiples of 4", N, K);
+  SVG_CHECK(ldy >= N, "xf_gemm_nn: row stride %d is shorter than the row %d", ldy, N);
+  SVG_CHECK(aligned16(dY) && aligned16(W) && aligned16(slabs) && aligned16(out) && aligned16(gate) && aligned16(add),
+            "xf_gemm_nn: an operand does not start on a 16-byte boundary");
   const int Z = xf_gemm_nn_splits(N, K);
   const int chunk = (cdiv(N, Z) + 63) / 64 * 64;
   for (int m0 = 0; m0 < M; m0 += 96) {
@@ -757,6 +767,7 @@ void xf_relu_drop(const float* h, float* r, int64_t n, const XfDrop d, hipStream
 
 void xf_add_ln_train(const float* x, const float* r, const XfDrop dr, const float* g, const float* b, float* y, float* xhat, float* rstd, int M,
                      int d, float eps, hipStream_t s) {
+  SVG_CHECK(M > 0 && d > 0, "xf_add_ln_train: empty problem %d x %d", M, d);
   SVG_CHECK(d <= 3072, "xf_add_ln_train: d %d > 3072", d);
   hipLaunchKernelGGL(add_ln_train_kernel, dim3(M), dim3(256), 0, s, x, r, dr, g, b, y, xhat, rstd, d, eps);
   check_launch("xf_add_ln_train");
@@ -764,6 +775,7 @@ void xf_add_ln_train(const float* x, const float* r, const XfDrop dr, const floa
 
 void xf_ln_bwd(const float* dy, const float* xhat, const float* rstd, const float* g, float* dz, float* dz_drop, const XfDrop dr, float* dgamma,
                float* dbeta, int M, int d, int accumulate, hipStream_t s) {
+  SVG_CHECK(M > 0 && d > 0, "xf_ln_bwd: empty problem %d x %d", M, d);
   SVG_CHECK(d <= 3072, "xf_ln_bwd: d %d > 3072", d);
   hipLaunchKernelGGL(ln_bwd_kernel, dim3(M), dim3(256), 0, s, dy, xhat, rstd, g, dz, dz_drop, dr, d);
   hipLaunchKernelGGL(ln_bwd_params_kernel, dim3(cdiv(d, 64)), dim3(256), 0, s, dy, xhat, dgamma, dbeta, M, d, accumulate);
@@ -772,18 +784,23 @@ void xf_ln_bwd(const float* dy, const float* xhat, const float* rstd, const floa
 
 void xf_embed_post_train(const float* emb, const float* pe, const int32_t* pe_row, const float* text, int d_txt, float* y, int B, int T, int d,
                          float scale, const XfDrop dr, hipStream_t s) {
+  SVG_CHECK(B > 0 && T > 0 && d_txt >= 0 && d_txt < d, "xf_embed_post_train: B %d, T %d, %d text channels of %d", B, T, d_txt, d);
+  SVG_CHECK(d_txt == 0 || text != nullptr, "xf_embed_post_train: %d text channels without a text embedding", d_txt);
   hipLaunchKernelGGL(embed_post_train_kernel, dim3(grid_for((int64_t)B * T * d, 256)), dim3(256), 0, s, emb, pe, pe_row, text, d_txt, y, B, T, d,
                      scale, dr);
   check_launch("xf_embed_post_train");
 }
 void xf_embed_post_bwd(const float* dy, float* de, int B, int T, int d, int d_img, float scale, const XfDrop dr, hipStream_t s) {
+  SVG_CHECK(B > 0 && T > 0 && d_img > 0 && d_img <= d, "xf_embed_post_bwd: B %d, T %d, %d image channels of %d", B, T, d_img, d);
   hipLaunchKernelGGL(embed_post_bwd_kernel, dim3(grid_for((int64_t)B * T * d_img, 256)), dim3(256), 0, s, dy, de, B, T, d, d_img, scale, dr);
   check_launch("xf_embed_post_bwd");
 }
 
 void xf_attention_train(const float* q, int ldq, const float* k, const float* v, int ldk, const float* mask, float* o, float* P, int Tq, int Tk,
                         int B, int heads, int hd, const XfDrop dr, hipStream_t s) {
+  SVG_CHECK(Tq > 0 && Tk > 0 && B > 0 && heads > 0 && hd > 0, "xf_attention_train: empty problem (T %d/%d, B %d, %d heads of %d)", Tq, Tk, B, heads, hd);
   SVG_CHECK(Tq <= TMAX && Tk <= TMAX, "xf_attention_train: T %d/%d > %d", Tq, Tk, TMAX);
+  SVG_CHECK(ldq >= heads * hd && ldk >= heads * hd, "xf_attention_train: row strides %d / %d are shorter than %d heads of %d", ldq, ldk, heads, hd);
   const size_t lds = (size_t)(Tq + 2 * Tk) * hd * sizeof(float);
   SVG_CHECK(lds <= kAttnTrainLds, "xf_attention_train: %d + 2 x %d tokens of head dim %d do not fit the LDS staging (%zu > %d bytes)", Tq, Tk, hd, lds, kAttnTrainLds);
   hipLaunchKernelGGL(attn_train_fwd_kernel, dim3(B, heads), dim3(256), lds, s, q, ldq, k, v, ldk, mask, o, P, Tq, Tk, B, heads, hd, dr);
@@ -791,7 +808,10 @@ void xf_attention_train(const float* q, int ldq, const float* k, const float* v,
 }
 void xf_attention_bwd(const float* dout, const float* q, int ldq, const float* k, const float* v, int ldk, const float* P, float* dq, int lddq,
                       float* dk, float* dv, int lddk, int Tq, int Tk, int B, int heads, int hd, const XfDrop dr, hipStream_t s) {
+  SVG_CHECK(Tq > 0 && Tk > 0 && B > 0 && heads > 0 && hd > 0, "xf_attention_bwd: empty problem (T %d/%d, B %d, %d heads of %d)", Tq, Tk, B, heads, hd);
   SVG_CHECK(Tq <= TMAX && Tk <= TMAX, "xf_attention_bwd: T %d/%d > %d", Tq, Tk, TMAX);
+  SVG_CHECK(ldq >= heads * hd && ldk >= heads * hd && lddq >= heads * hd && lddk >= heads * hd,
+            "xf_attention_bwd: a row stride (%d / %d / %d / %d) is shorter than %d heads of %d", ldq, ldk, lddq, lddk, heads, hd);
   const size_t lds = (size_t)(2 * Tq + 2 * Tk) * hd * sizeof(float);
   SVG_CHECK(lds <= kAttnTrainLds, "xf_attention_bwd: 2 x %d + 2 x %d tokens of head dim %d do not fit the LDS staging (%zu > %d bytes)", Tq, Tk, hd, lds, kAttnTrainLds);
   hipLaunchKernelGGL(attn_train_bwd_kernel, dim3(B, heads), dim3(256), lds, s, dout, q, ldq, k, v, ldk, P, dq, lddq, dk, dv, lddk, Tq, Tk, B, heads,
@@ -801,7 +821,11 @@ void xf_attention_bwd(const float* dout, const float* q, int ldq, const float* k
 
 void xf_criterion(const float* pred, const float* expected, float* dpred, float* part, float* part2, float* losses, int Tt, int B, int D, int t0,
                   int fh, int fw, float w_mse, float w_l1, float w_gdl, float alpha, float w_nce, float temperature, hipStream_t s) {
-  SVG_CHECK(D == 4 * fh * fw, "criterion: D_lat %d is not 4 x %d x %d", D, fh, fw);
+  SVG_CHECK(fh > 0 && fw > 0 && D == 4 * fh * fw, "criterion: D_lat %d is not 4 x %d x %d", D, fh, fw);
+  SVG_CHECK(B > 0 && t0 >= 0 && t0 < Tt, "criterion: B %d, rows %d .. %d of the prediction", B, t0, Tt);
+  // nce_kernel keeps 8 hw + 4 floats in LDS; xf_train_init_device() asks for hw = 4096
+  SVG_CHECK(w_nce == 0.f || (fh * fw <= 4096 && part2 != nullptr && temperature > 0.f),
+            "criterion: the contrastive term takes feature maps of up to 4096 positions (%d x %d) and a temperature > 0 (%g)", fh, fw, temperature);
   const int rows = Tt * B;
   hipLaunchKernelGGL(loss_rows_kernel, dim3(rows), dim3(256), 0, s, pred, expected, dpred, part, Tt, B, D, t0, fh, fw, w_mse, w_l1, w_gdl, alpha);
   const int hw = fh * fw;
