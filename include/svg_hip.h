@@ -365,6 +365,31 @@ int svg_op_groupnorm_f32(svg_ctx* ctx, const float* x, const float* gamma, const
  * the fp8 = 1 model key (reference call sites: the conv1 / conv2 of diffusers' ResnetBlock2D behind utils/sd_utils.py:253). */
 int svg_op_conv3x3_mx(svg_ctx* ctx, const uint16_t* x, const float* w_oihw, const float* bias, const uint16_t* residual,
                       uint16_t* out, uint8_t* q_out, uint8_t* s_out, int B, int H, int W, int Cin, int Cout, int mode, void* stream);
+/* The same conv on a descriptor, with every operand the UNet gives it and the packed weights read back (test hook; nothing is added to
+ * the kernels).  With Npad = Cout rounded up to 4, (Ho, Wo) the output image and Cp = Cin rounded up to 128:
+ *   out[b][y][x][n] = conv[b][y][x][n] + bias[n] + bias_bn[b * ld + n] + residual[b][y][x][n],   ld = bias_bn_ld, or Npad when that is 0
+ * x (B,H,W,Cin) 16-bit; w_oihw (Cout,Cin,3,3) f32 and bias (Cout, or NULL) f32 in host or device memory; bias_bn (device f32, or NULL):
+ * one row per sample, the time-embedding row of a resnet's conv1; residual (or NULL) and out: (B,Ho,Wo,Npad) 16-bit, the columns
+ * Cout .. Npad - 1 come from zero weights and a zero bias.  mode 0: stride 1; 3: nearest-2x upsample in front (Ho = 2H, Wo = 2W).
+ * gn_part (device f32, or NULL): (B * Ho/16 * Wo/16) * Npad * 2 floats, the GroupNorm column sums with svg_gemm_desc::gn_part's contract
+ * for conv_halo: gn_part[(tile_m * Npad + n) * 2 + {0,1}], tile_m = (b * Ho/16 + y/16) * Wo/16 + x/16.
+ * Read-backs (device, each may be NULL): q_out (B*H*W, Cp) and s_out (B*H*W, Cp/32) as svg_op_conv3x3_mx; w8_out: the packed weights,
+ * e4m3 [Npad][tap = 3 ky + kx][Cp]; w8s_out: their scales, E8M0 [tap][Cp/128][Npad][4] (byte i: channels 32 i .. 32 i + 31 of the
+ * 128-channel chunk).  Padding (channels >= Cin, rows >= Cout, and any all-zero block): zero bytes with scale byte 127.
+ * path (int[3], or NULL) receives what the launcher used: {column tile (128 / 160), tn_major, workgroups}.  A shape conv_halo_fp8 does
+ * not take (see svg_op_conv3x3_mx) returns an error without launching anything. */
+typedef struct svg_conv_mx_desc {
+  const uint16_t* x;
+  const float *w_oihw, *bias;
+  const float* bias_bn;
+  int bias_bn_ld;
+  const uint16_t* residual;
+  uint16_t* out;
+  int B, H, W, Cin, Cout, mode;
+  float* gn_part;
+  uint8_t *q_out, *s_out, *w8_out, *w8s_out;
+} svg_conv_mx_desc;
+int svg_op_conv3x3_mx_ex(svg_ctx* ctx, const svg_conv_mx_desc* desc, int* path, void* stream);
 /* C[M,N] = [A | A2] * W[N,K]^T + bias with the A operand given as two tensors (A: M x k_split, A2: M x (K - k_split)): the
  * torch.cat([hidden, skip], dim=1) in front of a resnet's 1x1 shortcut, never materialised.  k_split % 64 == 0. */
 /* C[batch*M,N] = A W^T + bias + residual, and the LayerNorm statistics of its rows (rs = rstd, rm = rstd * mean, eps 1e-5) as the
@@ -481,10 +506,18 @@ int svg_op_xf_criterion(svg_ctx* ctx, const float* pred, const float* expected, 
  * svg_op_quant_mx: x (rows,K) bf16 -> q (rows,K) e4m3 bytes, scales (rows,K/32) bytes; shared exponent floor(log2(amax)) - 8,
  * round to nearest even, saturating at +-448 (OCP MX v1.0).  K % 32 == 0. */
 int svg_op_quant_mx(svg_ctx* ctx, const uint16_t* x, uint8_t* q, uint8_t* scales, int64_t rows, int K, void* stream);
+/* The activation quantiser of the MX fp8 conv path on caller buffers (test hook): x (P,C) 16-bit -> q (P,Cp) e4m3 bytes and scales
+ * (P,Cp/32) bytes, Cp = C rounded up to 128; same conversion as svg_op_quant_mx, except that an all-zero block and the padding
+ * channels C .. Cp - 1 get scale byte 127 (zero bytes).  C % 32 == 0. */
+int svg_op_quant_act_mx(svg_ctx* ctx, const uint16_t* x, uint8_t* q, uint8_t* scales, int64_t P, int C, void* stream);
 /* C[M,N] = act(Q(A)[M,K] Q(W)[N,K]^T + bias + residual) on v_mfma_scale_f32_16x16x128_f8f6f4 (f32 accumulate), both operands
  * quantised on the fly by the routine above; act 0 none, 1 SiLU, 2 GELU.  K % 128 == 0, N % 4 == 0. */
 int svg_op_gemm_fp8(svg_ctx* ctx, const uint16_t* A, const uint16_t* W, const float* bias, const uint16_t* residual, void* C,
                     int M, int N, int K, int act, int out_f32, void* stream);
+/* svg_op_gemm_fp8 with the row strides of C (ldc >= N) and of the residual (ldr >= N), multiples of 4 elements, as the models' linear()
+ * passes them; path (int[1], or NULL) receives the column tile of the kernel instantiation that was launched (64 / 128).  Test hook. */
+int svg_op_gemm_fp8_ex(svg_ctx* ctx, const uint16_t* A, const uint16_t* W, const float* bias, const uint16_t* residual, void* C,
+                       int M, int N, int K, int act, int out_f32, int ldc, int ldr, int* path, void* stream);
 /* GroupNorm (+SiLU) on NHWC bf16. */
 int svg_op_groupnorm(svg_ctx* ctx, const uint16_t* x, const float* gamma, const float* beta,
                      uint16_t* out, int B, int HW, int C, int groups, float eps, int silu,
@@ -612,6 +645,10 @@ int svg_op_conv3x3_mx_f16(svg_ctx* ctx, const uint16_t* x, const float* w_oihw, 
 int svg_op_quant_mx_f16(svg_ctx* ctx, const uint16_t* x, uint8_t* q, uint8_t* scales, int64_t rows, int K, void* stream);
 int svg_op_gemm_fp8_f16(svg_ctx* ctx, const uint16_t* A, const uint16_t* W, const float* bias, const uint16_t* residual, void* C,
                         int M, int N, int K, int act, int out_f32, void* stream);
+int svg_op_quant_act_mx_f16(svg_ctx* ctx, const uint16_t* x, uint8_t* q, uint8_t* scales, int64_t P, int C, void* stream);
+int svg_op_conv3x3_mx_ex_f16(svg_ctx* ctx, const svg_conv_mx_desc* desc, int* path, void* stream);
+int svg_op_gemm_fp8_ex_f16(svg_ctx* ctx, const uint16_t* A, const uint16_t* W, const float* bias, const uint16_t* residual, void* C,
+                           int M, int N, int K, int act, int out_f32, int ldc, int ldr, int* path, void* stream);
 int svg_op_groupnorm_f16(svg_ctx* ctx, const uint16_t* x, const float* gamma, const float* beta, uint16_t* out, int B, int HW,
                          int C, int groups, float eps, int silu, void* stream);
 int svg_op_conv3x3_f32s_f16(svg_ctx* ctx, const uint16_t* x, const float* w_oihw, const float* bias, const uint16_t* residual,

@@ -76,6 +76,13 @@ class GnDesc(C.Structure):
                 ("force", _i), ("kind", _i), ("maxch", _i), ("vw", _i), ("q", _vp), ("sc", _vp), ("stats", _vp)]
 
 
+class ConvMxDesc(C.Structure):
+    """struct svg_conv_mx_desc (include/svg_hip.h): the descriptor of svg_op_conv3x3_mx_ex."""
+    _fields_ = [("x", _vp), ("w_oihw", _vp), ("bias", _vp), ("bias_bn", _vp), ("bias_bn_ld", _i), ("residual", _vp), ("out", _vp),
+                ("B", _i), ("H", _i), ("W", _i), ("Cin", _i), ("Cout", _i), ("mode", _i),
+                ("gn_part", _vp), ("q_out", _vp), ("s_out", _vp), ("w8_out", _vp), ("w8s_out", _vp)]
+
+
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/svg_hip.h
 SIGNATURES = {
     "svg_create": [_i, C.POINTER(_vp)],
@@ -137,8 +144,11 @@ SIGNATURES = {
     "svg_op_xf_embed_post_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _f, C.c_uint64, _i, _f, _vp],
     "svg_op_xf_criterion": [_vp, _vp, _vp, _vp, C.POINTER(_f), _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp],
     "svg_op_conv3x3_mx": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "svg_op_conv3x3_mx_ex": [_vp, C.POINTER(ConvMxDesc), C.POINTER(_i), _vp],
     "svg_op_quant_mx": [_vp, _vp, _vp, _vp, _i64, _i, _vp],
     "svg_op_gemm_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "svg_op_quant_act_mx": [_vp, _vp, _vp, _vp, _i64, _i, _vp],
+    "svg_op_gemm_fp8_ex": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_i), _vp],
     "svg_op_groupnorm": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "svg_op_conv3x3_f32s": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, C.POINTER(_i),
                             C.POINTER(_i), _vp],
@@ -169,7 +179,7 @@ SIGNATURES = {
     "svg_debug_captures_active": [],
 }
 # fp16-storage twins of the 16-bit operator hooks (svg_op_<name>_f16: same arguments)
-for _n in ("gemm", "gemm_ex", "gemm_plan", "conv3x3", "conv3x3_gn", "conv3x3_mx", "gemm_lnstats", "gemm_cat", "ff_fused", "xattn_fused", "quant_mx", "gemm_fp8", "groupnorm", "layernorm",
+for _n in ("gemm", "gemm_ex", "gemm_plan", "conv3x3", "conv3x3_gn", "conv3x3_mx", "conv3x3_mx_ex", "gemm_fp8_ex", "quant_act_mx", "gemm_lnstats", "gemm_cat", "ff_fused", "xattn_fused", "quant_mx", "gemm_fp8", "groupnorm", "layernorm",
            "attention", "attention_ex", "vae_attention", "conv3x3_f32s", "groupnorm_f32", "groupnorm_ex", "groupnorm_mx", "gn_fold_weights", "ln_stats",
            "softmax_rows", "rowsum"):
     SIGNATURES["svg_op_%s_f16" % _n] = SIGNATURES["svg_op_" + _n]

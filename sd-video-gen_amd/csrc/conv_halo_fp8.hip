@@ -461,7 +461,8 @@ void pack_conv3x3_mx(const float* w_oihw, uint8_t* q, uint8_t* sc, int O, int I,
 }
 
 // g: the GemmArgs conv3x3() builds for the fp16 conv (M, N, H, W, Ho, Wo, Cin, epilogue); operands in MX fp8
-void conv_halo_fp8(svg_ctx* ctx, const uint8_t* A8, const uint8_t* As, const uint8_t* W8, const uint8_t* Ws, int Npad, const GemmArgs& g0, hipStream_t s) {
+void conv_halo_fp8(svg_ctx* ctx, const uint8_t* A8, const uint8_t* As, const uint8_t* W8, const uint8_t* Ws, int Npad, const GemmArgs& g0, hipStream_t s,
+                   Fp8ConvPath* path) {
   const int B = g0.M / (g0.Ho * g0.Wo);
   const bool s1 = g0.amode == A_CONV_S1 && g0.Ho == g0.H && g0.Wo == g0.W, up = g0.amode == A_CONV_UP2 && g0.Ho == 2 * g0.H && g0.Wo == 2 * g0.W;
   SVG_CHECK((s1 || up) && conv_halo_fp8_supported(B, g0.Ho, g0.Wo, g0.Cin, g0.N) && !g0.out_f32 &&
@@ -492,6 +493,7 @@ void conv_halo_fp8(svg_ctx* ctx, const uint8_t* A8, const uint8_t* As, const uin
 #endif
   if (bn == 160) hipLaunchKernelGGL((conv_halo_fp8_kernel<160>), grid, dim3(512), fp8_halo_smem<160>(), s, a);
   else hipLaunchKernelGGL((conv_halo_fp8_kernel<128>), grid, dim3(512), fp8_halo_smem<128>(), s, a);
+  if (path) { path->bn = bn == 160 ? 160 : 128; path->tn_major = a.g.tn_major; path->workgroups = (int)grid.x; }
   check_launch("conv_halo_fp8");
 #ifdef FP8_STAMP
   {

@@ -190,7 +190,7 @@ void quant_mx_f32(const float* x, int ldx, uint8_t* q, uint8_t* sc, int64_t rows
 bool gemm_fp8_supported(int M, int N, int K) { return K % 128 == 0 && N % 4 == 0 && (int64_t)M * K < (1LL << 31) && (int64_t)N * K < (1LL << 31); }
 
 // g: M, N, K and the epilogue fields of a dense GemmArgs (bias, residual, act != GEGLU, C, ldc, out_f32); operands in MX fp8
-void gemm_fp8(svg_ctx* ctx, const uint8_t* A, const uint8_t* As, const uint8_t* W, const uint8_t* Ws, const GemmArgs& g, hipStream_t s) {
+void gemm_fp8(svg_ctx* ctx, const uint8_t* A, const uint8_t* As, const uint8_t* W, const uint8_t* Ws, const GemmArgs& g, hipStream_t s, int* bn_used) {
   SVG_CHECK(gemm_fp8_supported(g.M, g.N, g.K) && g.act != ACT_GEGLU && g.batch == 1 && !g.ln_rs && !g.gn_part,
             "gemm_fp8: M %d N %d K %d (K %% 128, no GEGLU / folded LayerNorm / GroupNorm sums) unsupported", g.M, g.N, g.K);
   if (!SVG_LAUNCHING(ctx)) return;
@@ -200,6 +200,7 @@ void gemm_fp8(svg_ctx* ctx, const uint8_t* A, const uint8_t* As, const uint8_t* 
   snprintf(tag, sizeof(tag), "fp8_M%d_N%d_K%d_act%d_res%d", g.M, g.N, g.K, g.act, g.residual ? 1 : 0);
   ProfScope ps(ctx, PK_GEMM, s, 2.0 * g.M * (double)g.N * g.K, (double)g.M * g.K + (double)g.N * g.K + 2.0 * g.M * g.N, tag);
   if (g.N <= 64) launch_fp8<64>(a, s); else launch_fp8<128>(a, s);
+  if (bn_used) *bn_used = g.N <= 64 ? 64 : 128;
   check_launch("gemm_fp8");
 }
 

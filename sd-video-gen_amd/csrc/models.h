@@ -348,6 +348,8 @@ void conv3x3(svg_ctx* ctx, const h16* x, const ConvW& cw, void* out, int B, int 
 bool conv3x3_fp8_ok(const ConvW& cw, int B, int H, int W, bool up2 = false);
 void conv3x3_fp8(svg_ctx* ctx, const uint8_t* x8, const uint8_t* xs, const ConvW& cw, h16* out, int B, int H, int W, int amode, hipStream_t s,
                  const ConvOpts& o = {});
+// the launch descriptor conv3x3_fp8 hands to conv_halo_fp8, before the GroupNorm sums are attached (o.emit is not looked at)
+GemmArgs conv3x3_fp8_args(const ConvW& cw, h16* out, int B, int H, int W, int amode, const ConvOpts& o);
 // The optional operands of a linear: C[M,N] = act(A[M,K] W^T + b) [+ residual]
 struct LinearOpts {
   int act = ACT_NONE;

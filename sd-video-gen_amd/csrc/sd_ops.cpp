@@ -114,6 +114,42 @@ int SVG_OP(svg_op_conv3x3_mx)(svg_ctx* ctx, const uint16_t* x, const float* w_oi
   API_END(ctx)
 }
 
+// the same conv on a descriptor (svg_hip.h: svg_conv_mx_desc) with everything conv3x3_fp8 takes — the per-sample bias rows and the
+// GroupNorm column sums included — and the packed weights read back; path = {column tile, tn_major, workgroups} as conv_halo_fp8
+// launched it.  Test hook.
+int SVG_OP(svg_op_conv3x3_mx_ex)(svg_ctx* ctx, const svg_conv_mx_desc* d, int* path, void* stream) {
+  API_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  SVG_CHECK(d != nullptr, "conv3x3_mx_ex: no descriptor");
+  SVG_CHECK(d->x && d->w_oihw && d->out, "conv3x3_mx_ex: x, w_oihw and out are required");
+  SVG_CHECK(d->Cout > 0 && d->Cin > 0 && d->Cin % 64 == 0, "conv3x3_mx_ex: Cin %% 64 must be 0");
+  SVG_CHECK(d->mode == 0 || d->mode == 3, "conv3x3_mx_ex: mode 0 (stride 1) or 3 (nearest-2x upsample in front)");
+  const int amode = d->mode == 3 ? A_CONV_UP2 : A_CONV_S1;
+  const ConvDims od = conv_out_dims(amode, d->H, d->W);
+  SVG_CHECK(conv_halo_fp8_supported(d->B, od.Ho, od.Wo, d->Cin, (int)align_up(d->Cout, 4)), "conv3x3_mx_ex: %d x %dx%d x %d -> %d is not a shape of conv_halo_fp8",
+            d->B, od.Ho, od.Wo, d->Cin, d->Cout);
+  Fp8ConvPath p;
+  run_planned(ctx, [&]() {
+    const ConvW cw = stage_conv(ctx, d->w_oihw, d->bias, d->Cin, d->Cout, true, s);
+    const int64_t P = (int64_t)d->B * d->H * d->W;
+    uint8_t* q = ctx->arena.get<uint8_t>(P * cw.Cp);
+    uint8_t* qs = ctx->arena.get<uint8_t>(P * (cw.Cp / 32));
+    quant_act_mx(ctx, (const h16*)d->x, d->Cin, q, qs, P, s);
+    ConvOpts o; o.bias_bn = d->bias_bn; o.bias_bn_ld = d->bias_bn_ld; o.residual = (const h16*)d->residual;
+    GemmArgs g = conv3x3_fp8_args(cw, (h16*)d->out, d->B, d->H, d->W, amode, o);
+    g.gn_part = d->gn_part;
+    conv_halo_fp8(ctx, q, qs, cw.w8, cw.w8s, cw.Opad, g, s, &p);
+    if (SVG_LAUNCHING(ctx)) {
+      if (d->q_out) HIP_OK(hipMemcpyAsync(d->q_out, q, (size_t)P * cw.Cp, hipMemcpyDeviceToDevice, s));
+      if (d->s_out) HIP_OK(hipMemcpyAsync(d->s_out, qs, (size_t)P * (cw.Cp / 32), hipMemcpyDeviceToDevice, s));
+      if (d->w8_out) HIP_OK(hipMemcpyAsync(d->w8_out, cw.w8, (size_t)cw.Opad * 9 * cw.Cp, hipMemcpyDeviceToDevice, s));
+      if (d->w8s_out) HIP_OK(hipMemcpyAsync(d->w8s_out, cw.w8s, (size_t)9 * (cw.Cp / 128) * cw.Opad * 4, hipMemcpyDeviceToDevice, s));
+    }
+  });
+  if (path) { path[0] = p.bn; path[1] = p.tn_major; path[2] = p.workgroups; }
+  API_END(ctx)
+}
+
 // conv3x3 (stride 1) whose epilogue leaves the GroupNorm column sums, followed by the GroupNorm that consumes them
 int SVG_OP(svg_op_conv3x3_gn)(svg_ctx* ctx, const uint16_t* x, const float* w_oihw, const float* bias, const float* gamma, const float* beta,
                       uint16_t* conv_out, uint16_t* gn_out, int B, int H, int W, int Cin, int Cout, int groups, float eps, int silu,
@@ -350,6 +386,14 @@ int SVG_OP(svg_op_quant_mx)(svg_ctx* ctx, const uint16_t* x, uint8_t* q, uint8_t
   API_END(ctx)
 }
 
+// the conv path's activation quantiser on caller buffers: x (P,C) 16-bit -> q (P,Cp) e4m3 bytes + scales (P,Cp/32), Cp = C rounded up to 128.  Test hook.
+int SVG_OP(svg_op_quant_act_mx)(svg_ctx* ctx, const uint16_t* x, uint8_t* q, uint8_t* scales, int64_t P, int C, void* stream) {
+  API_BEGIN
+  SVG_CHECK(x && q && scales && P > 0 && C > 0 && C % 32 == 0, "quant_act_mx op: P %lld C %d unsupported (C %% 32 must be 0)", (long long)P, C);
+  quant_act_mx(ctx, (const h16*)x, C, q, scales, P, (hipStream_t)stream);
+  API_END(ctx)
+}
+
 // C = act(Q(A) Q(W)^T + bias + residual) with both operands quantised to MX fp8 on the fly (test hook / benchmark of the fp8 GEMM)
 int SVG_OP(svg_op_gemm_fp8)(svg_ctx* ctx, const uint16_t* A, const uint16_t* W, const float* bias, const uint16_t* residual, void* C, int M, int N,
                     int K, int act, int out_f32, void* stream) {
@@ -366,6 +410,29 @@ int SVG_OP(svg_op_gemm_fp8)(svg_ctx* ctx, const uint16_t* A, const uint16_t* W, 
     g.M = M; g.N = N; g.K = K; g.bias = bias; g.residual = (const h16*)residual; g.ldr = N; g.act = act; g.out_f32 = out_f32; g.C = C; g.ldc = N;
     gemm_fp8(ctx, aq, as, wq, wsc, g, s);
   });
+  API_END(ctx)
+}
+
+// the same with the output and residual row strides linear() passes (ldc >= N, ldr >= N); path[0] = the column tile gemm_fp8 launched.  Test hook.
+int SVG_OP(svg_op_gemm_fp8_ex)(svg_ctx* ctx, const uint16_t* A, const uint16_t* W, const float* bias, const uint16_t* residual, void* C, int M, int N,
+                       int K, int act, int out_f32, int ldc, int ldr, int* path, void* stream) {
+  API_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  SVG_CHECK(A && W && C && M > 0 && N > 0 && K > 0 && ldc >= N && (!residual || ldr >= N) && ldc % 4 == 0 && ldr % 4 == 0,
+            "gemm_fp8_ex: M %d N %d K %d ldc %d ldr %d unsupported", M, N, K, ldc, ldr);
+  int bn = -1;
+  run_planned(ctx, [&]() {
+    uint8_t* aq = ctx->arena.get<uint8_t>((int64_t)M * K);
+    uint8_t* as = ctx->arena.get<uint8_t>((int64_t)M * (K / 32));
+    uint8_t* wq = ctx->arena.get<uint8_t>((int64_t)N * K);
+    uint8_t* wsc = ctx->arena.get<uint8_t>((int64_t)N * (K / 32));
+    quant_mx_h16(ctx, (const h16*)A, K, aq, as, M, K, s);
+    quant_mx_h16(ctx, (const h16*)W, K, wq, wsc, N, K, s);
+    GemmArgs g;
+    g.M = M; g.N = N; g.K = K; g.bias = bias; g.residual = (const h16*)residual; g.ldr = ldr; g.act = act; g.out_f32 = out_f32; g.C = C; g.ldc = ldc;
+    gemm_fp8(ctx, aq, as, wq, wsc, g, s, &bn);
+  });
+  if (path) path[0] = bn;
   API_END(ctx)
 }
 

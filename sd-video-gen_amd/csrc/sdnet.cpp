@@ -121,8 +121,7 @@ bool conv3x3_fp8_ok(const ConvW& cw, int B, int H, int W, bool up2) {
   return cw.w8 != nullptr && conv_halo_fp8_supported(B, up2 ? 2 * H : H, up2 ? 2 * W : W, cw.Cin, cw.Opad);
 }
 
-void conv3x3_fp8(svg_ctx* ctx, const uint8_t* x8, const uint8_t* xs, const ConvW& cw, h16* out, int B, int H, int W, int amode, hipStream_t s,
-                 const ConvOpts& o) {
+GemmArgs conv3x3_fp8_args(const ConvW& cw, h16* out, int B, int H, int W, int amode, const ConvOpts& o) {
   SVG_CHECK((amode == A_CONV_S1 || amode == A_CONV_UP2) && !o.out_f32 && !o.residual_f32, "conv3x3_fp8: stride 1 (mode %d), 16-bit output and residual only", amode);
   SVG_CHECK(conv3x3_fp8_ok(cw, B, H, W, amode == A_CONV_UP2), "conv3x3_fp8: %d x %dx%d x %d -> %d does not qualify", B, H, W, cw.Cin, cw.Opad);
   const ConvDims d = conv_out_dims(amode, H, W);
@@ -133,7 +132,13 @@ void conv3x3_fp8(svg_ctx* ctx, const uint8_t* x8, const uint8_t* xs, const ConvW
   g.bias_bn = o.bias_bn; g.bias_bn_ld = o.bias_bn_ld; g.rows_per_batch = d.Ho * d.Wo;
   g.residual = o.residual; g.ldr = cw.Opad;
   g.C = out; g.ldc = cw.Opad;
-  attach_gn_emit(g, o.emit, d.Ho * d.Wo, 256);   // one partial per 16 x 16 pixel block, like the fp16 halo conv
+  return g;
+}
+
+void conv3x3_fp8(svg_ctx* ctx, const uint8_t* x8, const uint8_t* xs, const ConvW& cw, h16* out, int B, int H, int W, int amode, hipStream_t s,
+                 const ConvOpts& o) {
+  GemmArgs g = conv3x3_fp8_args(cw, out, B, H, W, amode, o);
+  attach_gn_emit(g, o.emit, g.Ho * g.Wo, 256);   // one partial per 16 x 16 pixel block, like the fp16 halo conv
   conv_halo_fp8(ctx, x8, xs, cw.w8, cw.w8s, cw.Opad, g, s);
 }
 
