@@ -3,8 +3,6 @@
 #include "xf_walk.h"
 #include "../../include/svg_hip.h"
 
-using namespace SDNS;   // ddim_step: storage-independent f32 kernel
-
 void destroy_models(svg_ctx* ctx) {
   if (ctx->xf) { xf_train_free(ctx->xf); ctx->xf->ws.clear(); delete ctx->xf; ctx->xf = nullptr; }
   if (ctx->vae) { ctx->vae->ws.clear(); delete ctx->vae; ctx->vae = nullptr; }
@@ -12,74 +10,6 @@ void destroy_models(svg_ctx* ctx) {
   if (ctx->clip) { ctx->clip->ws.clear(); delete ctx->clip; ctx->clip = nullptr; }
   if (ctx->minilm) { ctx->minilm->ws.clear(); delete ctx->minilm; ctx->minilm = nullptr; }
   if (ctx->i3d) { ctx->i3d->ws.clear(); delete ctx->i3d; ctx->i3d = nullptr; }
-}
-
-// ---- DDIM table, as diffusers' DDIMScheduler builds it: betas = linspace(sqrt(b0), sqrt(b1), 1000, f32)**2,
-// alphas_cumprod = cumprod(1 - betas) in f32
-const std::vector<float>& sd_alphas_cumprod() {
-  static const std::vector<float> table = [] {
-    std::vector<float> alphas_cumprod(1000);
-    const double b0 = sqrt(0.00085), b1 = sqrt(0.012);
-    float prod = 1.f;
-    for (int i = 0; i < 1000; ++i) {
-      const double step = (b1 - b0) / 999.0;
-      float sb = (float)(i * step + b0);
-      if (i == 999) sb = (float)b1;
-      float beta = sb * sb;
-      float alpha = 1.f - beta;
-      prod = prod * alpha;
-      alphas_cumprod[i] = prod;
-    }
-    return alphas_cumprod;
-  }();
-  return table;
-}
-
-// The LMS schedule in double from the f32 alphas_cumprod.  The coefficient c_k integrates the Lagrange basis polynomial
-// prod_{j != k} (tau - sigma_{i-j}) / (sigma_{i-k} - sigma_{i-j}) (degree <= 3) over [sigma_i, sigma_{i+1}]: expanded in
-// u = tau - sigma_i (roots r_j = sigma_{i-j} - sigma_i, so nothing of the size of sigma^4 is subtracted) and integrated term by
-// term over [0, sigma_{i+1} - sigma_i] -- exact up to rounding, where diffusers runs scipy.integrate.quad(epsrel = 1e-4).
-void lms_coefs(int num_steps, int i, LmsCoef* out) {
-  SVG_CHECK(num_steps >= 1 && num_steps <= 1000 && i >= 0 && i < num_steps, "lms: step %d of %d out of range", i, num_steps);
-  const std::vector<float>& abar = sd_alphas_cumprod();
-  // numpy.linspace(999, 0, n): arange(n) * (-999 / (n - 1)) + 999 with the last element set to 0 (and [999] for n = 1)
-  auto timestep = [&](int j) -> double {
-    if (num_steps == 1) return 999.0;
-    if (j == num_steps - 1) return 0.0;
-    const double step = -999.0 / (num_steps - 1);
-    volatile double prod = j * step;      // rounded on its own, as numpy does (never a fused multiply-add)
-    return prod + 999.0;
-  };
-  auto sigma_at = [&](int j) -> double {
-    if (j >= num_steps) return 0.0;
-    const double t = timestep(j);
-    const int lo = (int)floor(t), hi = (int)ceil(t);
-    const double fr = t - floor(t);
-    auto train = [&](int k) { const double a = abar[k]; return sqrt((1.0 - a) / a); };
-    return (1.0 - fr) * train(lo) + fr * train(hi);
-  };
-  out->t = timestep(i);
-  out->sigma = sigma_at(i);
-  out->sigma_next = sigma_at(i + 1);
-  out->order = std::min(i + 1, 4);
-  const double h = out->sigma_next - out->sigma;
-  double r[4];
-  for (int j = 0; j < out->order; ++j) r[j] = sigma_at(i - j) - out->sigma;
-  for (int k = 0; k < 4; ++k) out->c[k] = 0.0;
-  for (int k = 0; k < out->order; ++k) {
-    double p[4] = {1.0, 0.0, 0.0, 0.0};    // prod_{j != k} (u - r_j), ascending powers of u
-    int deg = 0;
-    double den = 1.0;
-    for (int j = 0; j < out->order; ++j) {
-      if (j == k) continue;
-      for (int m = ++deg; m > 0; --m) p[m] = p[m - 1] - r[j] * p[m];
-      p[0] = -r[j] * p[0];
-      den *= r[k] - r[j];
-    }
-    double integral = 0.0;
-    for (int m = deg; m >= 0; --m) integral = integral * h + p[m] / (m + 1);   // sum_m p_m h^m / (m + 1)
-    out->c[k] = integral * h / den;
-  }
 }
 
 static WeightStore* store_of(svg_ctx* ctx, int model, bool create) {
@@ -201,7 +131,7 @@ int svg_ddim_loop(svg_ctx* ctx, float* z, int N, int h, int w, const float* text
   try {
     SVG_CHECK(ctx && ctx->unet, "unet: model not configured");
     xf_walk_check(ctx, false);                       // an earlier layer-walking forward that gave up: walk off + logged; raised to the Transformer's caller
-    ctx->unet->ddim_loop(ctx, z, N, h, w, text_emb, ctx_len, num_steps, start_step, guidance, noise, hist, (hipStream_t)stream);
+    ctx->unet->sample_loop(ctx, kSamplerDdim, z, N, h, w, text_emb, ctx_len, num_steps, start_step, guidance, noise, hist, (hipStream_t)stream);
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }
@@ -224,9 +154,9 @@ int svg_dpmpp_step(svg_ctx* ctx, const float* x, const float* eps, const float* 
     SVG_CHECK(ctx && ctx->unet && ctx->unet->ready, "unet: model not finalized");
     SVG_CHECK(x && eps && x_out && n >= 0, "svg_dpmpp_step: null tensor or negative size");
     SVG_CHECK(!m_prev || t_next < 0 || t_last >= 0, "svg_dpmpp_step: a second-order step needs the previous timestep t_last");
-    float row[kDpmRow];
-    ctx->unet->dpmpp_coefs(t, t_next, m_prev ? t_last : -1, row);
-    dpmpp_step(x, eps, nullptr, 0.f, m_prev, x_out, m_out, n, row, (hipStream_t)stream);
+    float row[kSamplerRow];
+    dpmpp_coefs(t, t_next, m_prev ? t_last : -1, row);
+    dpmpp_step(x, eps, nullptr, 0.f, m_prev, x_out, m_out, n, sampler_row(row), (hipStream_t)stream);
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }
@@ -248,17 +178,18 @@ int svg_lms_step(svg_ctx* ctx, const float* x, const float* eps, float* dhist, f
     SVG_CHECK(x && eps && dhist && x_out && n >= 0, "svg_lms_step: null tensor or negative size");
     LmsCoef lc;
     lms_coefs(num_steps, i, &lc);
-    const float c[4] = {(float)lc.c[0], (float)lc.c[1], (float)lc.c[2], (float)lc.c[3]};
-    lms_step(x, eps, nullptr, 0.f, dhist, x_out, n, i, lc.order, c, (hipStream_t)stream);
+    float row[kSamplerRow];
+    lms_row(lc, i, row);
+    lms_step(x, eps, nullptr, 0.f, dhist, x_out, n, sampler_row(row), (hipStream_t)stream);
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }
 int svg_ddim_step(svg_ctx* ctx, const float* x, const float* eps, float* prev, int64_t n, int t, int t_prev, void* stream) {
   try {
     SVG_CHECK(ctx && ctx->unet && ctx->unet->ready, "unet: model not finalized");
-    float sa, s1a, sap, s1ap;
-    ctx->unet->ddim_coefs(t, t_prev, &sa, &s1a, &sap, &s1ap);
-    ddim_step(x, eps, nullptr, 0.f, prev, n, sa, s1a, sap, s1ap, (hipStream_t)stream);
+    float row[kSamplerRow];
+    ddim_coefs(t, t_prev, row);
+    ddim_step(x, eps, nullptr, 0.f, prev, n, sampler_row(row), (hipStream_t)stream);
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }

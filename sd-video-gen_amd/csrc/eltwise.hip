@@ -199,127 +199,6 @@ __global__ void timestep_embed_kernel(const float* __restrict__ t, h16* __restri
   }
 }
 
-// DDIMScheduler.step (eta 0, clip_sample) with the classifier-free-guidance combine in front
-// (sd_utils.py:256-260)
-__global__ void ddim_step_kernel(const float* __restrict__ z, const float* __restrict__ eu, const float* __restrict__ ec, float guidance,
-                                 float* __restrict__ zo, int64_t n, float sa, float s1a, float sap, float s1ap) {
-  GRID_STRIDE(i, n) {
-    float e = eu[i];
-    if (ec) e = e + guidance * (ec[i] - e);
-    float x0 = (z[i] - s1a * e) / sa;
-    x0 = fminf(fmaxf(x0, -1.f), 1.f);
-    zo[i] = sap * x0 + s1ap * e;
-  }
-}
-// The same step with its scalars read from a device table row chosen by a device counter, so that a captured graph of one DDIM
-// step replays for every timestep without new kernel arguments: tab[i] = {t, sqrt(a_t), sqrt(1 - a_t), sqrt(a_prev), sqrt(1 - a_prev)}
-__global__ void ddim_step_tab_kernel(const float* __restrict__ z, const float* __restrict__ eu, const float* __restrict__ ec, float guidance,
-                                     float* __restrict__ zo, int64_t n, const float* __restrict__ tab, const int* __restrict__ idx) {
-  const float* r = tab + 5 * idx[0];
-  const float sa = r[1], s1a = r[2], sap = r[3], s1ap = r[4];
-  GRID_STRIDE(i, n) {
-    float e = eu[i];
-    if (ec) e = e + guidance * (ec[i] - e);
-    float x0 = (z[i] - s1a * e) / sa;
-    x0 = fminf(fmaxf(x0, -1.f), 1.f);
-    zo[i] = sap * x0 + s1ap * e;
-  }
-}
-__global__ void ddim_tvec_kernel(float* __restrict__ tvec, int nb, const float* __restrict__ tab, int row, const int* __restrict__ idx) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nb) tvec[i] = tab[row * idx[0]];
-}
-// DPM-Solver++(2M) (diffusers DPMSolverMultistepScheduler: dpmsolver++, order 2, midpoint, no thresholding) with the CFG combine in
-// front: m = (x - sig_s e) / a_s;  D = m + k (m - m_prev) (k = 1 / 2r, 0 at first order);  x' = last ? m : cx x + cd D;  m_prev <- m.
-// x / x_out and m_prev / m_out may alias (in-place loop): every element is read before it is written, by the same thread, so those
-// pointers are deliberately not __restrict__.  m_prev is not read at first order (k == 0): it may be null or uninitialised then.
-__device__ __forceinline__ void dpmpp_elem(const float* x, const float* __restrict__ eu, const float* __restrict__ ec, float guidance,
-                                           const float* mp, float* xo, float* mo, int64_t i, float inv_a, float sig, float cx, float cd,
-                                           float k, bool last) {
-  float e = eu[i];
-  if (ec) e = e + guidance * (ec[i] - e);
-  const float xi = x[i];
-  const float m = (xi - sig * e) * inv_a;
-  float d = m;
-  if (k != 0.f) d = m + k * (m - mp[i]);
-  const float out = last ? m : cx * xi + cd * d;
-  if (mo) mo[i] = m;
-  xo[i] = out;
-}
-__global__ void dpmpp_step_kernel(const float* x, const float* __restrict__ eu, const float* __restrict__ ec, float guidance, const float* mp,
-                                  float* xo, float* mo, int64_t n, float inv_a, float sig, float cx, float cd, float k, int last) {
-  GRID_STRIDE(i, n) dpmpp_elem(x, eu, ec, guidance, mp, xo, mo, i, inv_a, sig, cx, cd, k, last != 0);
-}
-// the same step with its row read from a device table through the DDIM loop's step counter: tab[i] = kDpmRow floats
-// {t, 1/a_s, sig_s, sig_s'/sig_s, a_s'(1 - e^-h), 1/2r, last, 0}
-__global__ void dpmpp_step_tab_kernel(const float* x, const float* __restrict__ eu, const float* __restrict__ ec, float guidance, const float* mp,
-                                      float* xo, float* mo, int64_t n, const float* __restrict__ tab, const int* __restrict__ idx) {
-  const float* r = tab + kDpmRow * idx[0];
-  const float inv_a = r[1], sig = r[2], cx = r[3], cd = r[4], k = r[5];
-  const bool last = r[6] != 0.f;
-  GRID_STRIDE(i, n) dpmpp_elem(x, eu, ec, guidance, mp, xo, mo, i, inv_a, sig, cx, cd, k, last);
-}
-// LMS (diffusers 0.2.3 LMSDiscreteScheduler.step, order <= 4) with the CFG combine in front.  The derivative of step i is the
-// combined eps itself ((x - (x - sigma eps)) / sigma up to f32 rounding); it goes to slot i & 3 of the ring dh (4 x n floats), the
-// up to three older ones come from the slots (i-1) & 3 ... (i-3) & 3, never the slot written:  x' = x + sum_k c_k d_{i-k}, k < order.
-// W = 4: one 16-byte access per operand, W = 1: the scalar tail.  x / x_out may alias (read before written by the same thread).
-// Every product is an explicit fmaf, so that the tabled, the direct, the 16-byte and the scalar form round alike.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-template <int W> struct LmsVec { typedef float T; };
-template <> struct LmsVec<4> { typedef f32x4 T; };
-template <int W>
-__device__ __forceinline__ void lms_elem(const float* x, const float* __restrict__ eu, const float* __restrict__ ec, float guidance, float* dh,
-                                         float* xo, int64_t n, int64_t i, int slot, int order, float c0, float c1, float c2, float c3) {
-  typedef typename LmsVec<W>::T V;
-  const V xv = *(const V*)(x + i);
-  V e = *(const V*)(eu + i);
-  if (ec) e = __builtin_elementwise_fma(V(guidance), *(const V*)(ec + i) - e, e);
-  *(V*)(dh + (int64_t)slot * n + i) = e;
-  V acc = V(c0) * e;
-  if (order > 1) acc = __builtin_elementwise_fma(V(c1), *(const V*)(dh + (int64_t)((slot + 3) & 3) * n + i), acc);
-  if (order > 2) acc = __builtin_elementwise_fma(V(c2), *(const V*)(dh + (int64_t)((slot + 2) & 3) * n + i), acc);
-  if (order > 3) acc = __builtin_elementwise_fma(V(c3), *(const V*)(dh + (int64_t)((slot + 1) & 3) * n + i), acc);
-  *(V*)(xo + i) = xv + acc;
-}
-// nv: the number of 4-float groups taken with 16-byte accesses (0 when n % 4 or a pointer forbids them); the rest is the scalar tail
-__global__ void lms_step_kernel(const float* x, const float* __restrict__ eu, const float* __restrict__ ec, float guidance, float* dh, float* xo,
-                                int64_t n, int64_t nv, int slot, int order, float c0, float c1, float c2, float c3) {
-  GRID_STRIDE(v, nv) lms_elem<4>(x, eu, ec, guidance, dh, xo, n, 4 * v, slot, order, c0, c1, c2, c3);
-  GRID_STRIDE(j, n - 4 * nv) lms_elem<1>(x, eu, ec, guidance, dh, xo, n, 4 * nv + j, slot, order, c0, c1, c2, c3);
-}
-// the same step with its row read from a device table through the loop's step counter: tab[i] = kLmsRow floats
-// {t, 1/sqrt(sigma_i^2 + 1), order, i, c0, c1, c2, c3}; the ring slot follows from i, so a replayed graph needs no new arguments
-__global__ void lms_step_tab_kernel(const float* x, const float* __restrict__ eu, const float* __restrict__ ec, float guidance, float* dh,
-                                    float* xo, int64_t n, int64_t nv, const float* __restrict__ tab, const int* __restrict__ idx) {
-  const float* r = tab + kLmsRow * idx[0];
-  const int order = (int)r[2], slot = (int)r[3] & 3;
-  const float c0 = r[4], c1 = r[5], c2 = r[6], c3 = r[7];
-  GRID_STRIDE(v, nv) lms_elem<4>(x, eu, ec, guidance, dh, xo, n, 4 * v, slot, order, c0, c1, c2, c3);
-  GRID_STRIDE(j, n - 4 * nv) lms_elem<1>(x, eu, ec, guidance, dh, xo, n, 4 * nv + j, slot, order, c0, c1, c2, c3);
-}
-// the UNet input of an LMS step: o0 (and o1, the second half of a guided batch) <- x * c, c = 1 / sqrt(sigma_i^2 + 1)
-template <int W>
-__device__ __forceinline__ void lms_input_elem(const float* x, float* o0, float* o1, int64_t i, float c) {
-  typedef typename LmsVec<W>::T V;
-  const V v = *(const V*)(x + i) * V(c);
-  *(V*)(o0 + i) = v;
-  if (o1) *(V*)(o1 + i) = v;
-}
-__global__ void lms_input_kernel(const float* x, float* o0, float* o1, int64_t n, int64_t nv, float c) {
-  GRID_STRIDE(v, nv) lms_input_elem<4>(x, o0, o1, 4 * v, c);
-  GRID_STRIDE(j, n - 4 * nv) lms_input_elem<1>(x, o0, o1, 4 * nv + j, c);
-}
-__global__ void lms_input_tab_kernel(const float* x, float* o0, float* o1, int64_t n, int64_t nv, const float* __restrict__ tab,
-                                     const int* __restrict__ idx) {
-  const float c = tab[kLmsRow * idx[0] + 1];
-  GRID_STRIDE(v, nv) lms_input_elem<4>(x, o0, o1, 4 * v, c);
-  GRID_STRIDE(j, n - 4 * nv) lms_input_elem<1>(x, o0, o1, 4 * nv + j, c);
-}
-__global__ void ddim_bump_kernel(int* __restrict__ idx) { idx[0] += 1; }
-__global__ void add_noise_kernel(const float* __restrict__ x0, const float* __restrict__ nz, float* __restrict__ out, int64_t n, float sa, float s1a) {
-  GRID_STRIDE(i, n) out[i] = sa * x0[i] + s1a * nz[i];
-}
-
 }  // namespace
 
 void img_to_act(const uint8_t* img, h16* out, int N, int sh, int sw, int H, int W, hipStream_t s) {
@@ -410,71 +289,6 @@ void timestep_embed(const float* t, h16* out, int N, int dim, hipStream_t s) {
   hipLaunchKernelGGL(timestep_embed_kernel, grid_for((int64_t)N * dim / 2), dim3(256), 0, s, t, out, N, dim);
   check_launch("timestep_embed");
 }
-void ddim_step(const float* z, const float* eu, const float* ec, float guidance, float* zo, int64_t n, float sa, float s1a,
-               float sap, float s1ap, hipStream_t s) {
-  hipLaunchKernelGGL(ddim_step_kernel, grid_for(n), dim3(256), 0, s, z, eu, ec, guidance, zo, n, sa, s1a, sap, s1ap);
-  check_launch("ddim_step");
-}
-void ddim_step_tab(const float* z, const float* eu, const float* ec, float guidance, float* zo, int64_t n, const float* tab, const int* idx,
-                   hipStream_t s) {
-  hipLaunchKernelGGL(ddim_step_tab_kernel, grid_for(n), dim3(256), 0, s, z, eu, ec, guidance, zo, n, tab, idx);
-  check_launch("ddim_step_tab");
-}
-void ddim_tvec(float* tvec, int nb, const float* tab, const int* idx, hipStream_t s, int row) {
-  hipLaunchKernelGGL(ddim_tvec_kernel, dim3((nb + 63) / 64), dim3(64), 0, s, tvec, nb, tab, row, idx);
-  check_launch("ddim_tvec");
-}
-void dpmpp_step(const float* x, const float* eu, const float* ec, float guidance, const float* m_prev, float* x_out, float* m_out, int64_t n,
-                const float* row, hipStream_t s) {
-  SVG_CHECK(m_prev || row[5] == 0.f, "dpmpp_step: a second-order step needs m_prev");
-  hipLaunchKernelGGL(dpmpp_step_kernel, grid_for(n), dim3(256), 0, s, x, eu, ec, guidance, m_prev, x_out, m_out, n, row[1], row[2], row[3],
-                     row[4], row[5], row[6] != 0.f ? 1 : 0);
-  check_launch("dpmpp_step");
-}
-void dpmpp_step_tab(const float* x, const float* eu, const float* ec, float guidance, float* m, float* x_out, int64_t n, const float* tab,
-                    const int* idx, hipStream_t s) {
-  hipLaunchKernelGGL(dpmpp_step_tab_kernel, grid_for(n), dim3(256), 0, s, x, eu, ec, guidance, m, x_out, m, n, tab, idx);
-  check_launch("dpmpp_step_tab");
-}
-namespace {
-// 4-float groups an LMS kernel may take with 16-byte accesses: all of them when every pointer it indexes is 16-byte aligned
-// (`stride4`: the kernel also indexes p + k * n, so n % 4 must be 0 too), else none
-inline int64_t lms_groups(int64_t n, bool stride4, std::initializer_list<const void*> ptrs) {
-  if (stride4 && n % 4 != 0) return 0;
-  for (const void* p : ptrs)
-    if ((uintptr_t)p & 15) return 0;
-  return n / 4;
-}
-inline dim3 lms_grid(int64_t n, int64_t nv) { return grid_for(std::max<int64_t>(nv, n - 4 * nv)); }
-}  // namespace
-void lms_input(const float* x, float* o0, float* o1, int64_t n, float c, hipStream_t s) {
-  const int64_t nv = lms_groups(n, false, {x, o0, o1});
-  hipLaunchKernelGGL(lms_input_kernel, lms_grid(n, nv), dim3(256), 0, s, x, o0, o1, n, nv, c);
-  check_launch("lms_input");
-}
-void lms_input_tab(const float* x, float* o0, float* o1, int64_t n, const float* tab, const int* idx, hipStream_t s) {
-  const int64_t nv = lms_groups(n, false, {x, o0, o1});
-  hipLaunchKernelGGL(lms_input_tab_kernel, lms_grid(n, nv), dim3(256), 0, s, x, o0, o1, n, nv, tab, idx);
-  check_launch("lms_input_tab");
-}
-void lms_step(const float* x, const float* eu, const float* ec, float guidance, float* dhist, float* x_out, int64_t n, int i, int order,
-              const float* c, hipStream_t s) {
-  SVG_CHECK(i >= 0 && order >= 1 && order <= 4 && order <= i + 1, "lms_step: order %d at step %d", order, i);
-  const int64_t nv = lms_groups(n, true, {x, eu, ec, dhist, x_out});
-  hipLaunchKernelGGL(lms_step_kernel, lms_grid(n, nv), dim3(256), 0, s, x, eu, ec, guidance, dhist, x_out, n, nv, i & 3, order, c[0], c[1],
-                     c[2], c[3]);
-  check_launch("lms_step");
-}
-void lms_step_tab(const float* x, const float* eu, const float* ec, float guidance, float* dhist, float* x_out, int64_t n, const float* tab,
-                  const int* idx, hipStream_t s) {
-  const int64_t nv = lms_groups(n, true, {x, eu, ec, dhist, x_out});
-  hipLaunchKernelGGL(lms_step_tab_kernel, lms_grid(n, nv), dim3(256), 0, s, x, eu, ec, guidance, dhist, x_out, n, nv, tab, idx);
-  check_launch("lms_step_tab");
-}
-void ddim_bump(int* idx, hipStream_t s) {
-  hipLaunchKernelGGL(ddim_bump_kernel, dim3(1), dim3(1), 0, s, idx);
-  check_launch("ddim_bump");
-}
 
 namespace {
 __global__ void fill_f32_kernel(float* __restrict__ p, int64_t n, float v) {
@@ -484,10 +298,6 @@ __global__ void fill_f32_kernel(float* __restrict__ p, int64_t n, float v) {
 void fill_f32(float* p, int64_t n, float v, hipStream_t s) {
   hipLaunchKernelGGL(fill_f32_kernel, grid_for(n), dim3(256), 0, s, p, n, v);
   check_launch("fill_f32");
-}
-void add_noise(const float* x0, const float* nz, float* out, int64_t n, float sa, float s1a, hipStream_t s) {
-  hipLaunchKernelGGL(add_noise_kernel, grid_for(n), dim3(256), 0, s, x0, nz, out, n, sa, s1a);
-  check_launch("add_noise");
 }
 
 }  // namespace SDNS

@@ -276,37 +276,6 @@ void f32_to_h16_x8(const float* x, h16* y, int64_t n, hipStream_t s);
 // timestep sinusoid (flip_sin_to_cos, shift 0): t f32[N] -> bf16 (N,dim) = [cos | sin]
 void timestep_embed(const float* t, h16* out, int N, int dim, hipStream_t s);
 void silu_h16(const h16* x, h16* y, int64_t n, hipStream_t s);
-// DDIM: z <- step(z, eps) with clip_sample; coefficients from the device table `coef` row `*step_idx`
-void ddim_step(const float* z, const float* eps_u, const float* eps_c, float guidance, float* z_out,
-               int64_t n, float sqrt_at, float sqrt_1mat, float sqrt_ap, float sqrt_1map, hipStream_t s);
-// the step with (t, coefficients) read from row idx[0] of a device table of 5-float rows; tvec[i] = tab[idx][0]; idx[0] += 1
-void ddim_step_tab(const float* z, const float* eps_u, const float* eps_c, float guidance, float* z_out, int64_t n, const float* tab,
-                   const int* idx, hipStream_t s);
-void ddim_tvec(float* tvec, int nb, const float* tab, const int* idx, hipStream_t s, int row = 5);   // row: floats per table row
-void ddim_bump(int* idx, hipStream_t s);
-// DPM-Solver++(2M): one table row of kDpmRow floats {t, 1/a_s, sig_s, sig_s'/sig_s, a_s'(1 - e^-h), 1/2r (0: first order), last, 0}
-constexpr int kDpmRow = 8;
-// x_out <- step(x, eps) with the host row `row`; m_out <- the x0 prediction (may be null); m_prev is read only when row[5] != 0.
-// x / x_out and m_prev / m_out may be the same buffers.
-void dpmpp_step(const float* x, const float* eps_u, const float* eps_c, float guidance, const float* m_prev, float* x_out, float* m_out,
-                int64_t n, const float* row, hipStream_t s);
-// the step with its row read from row idx[0] of a device table (the DDIM loop's counter); m: m_prev in, m out
-void dpmpp_step_tab(const float* x, const float* eps_u, const float* eps_c, float guidance, float* m, float* x_out, int64_t n,
-                    const float* tab, const int* idx, hipStream_t s);
-// LMS (order <= 4): one table row of kLmsRow floats {t, 1/sqrt(sigma_i^2 + 1), order, i, c0, c1, c2, c3}
-constexpr int kLmsRow = 8;
-// the UNet input of an LMS step: o0 (and o1 unless null) <- x * c; x / o0 may be the same buffer
-void lms_input(const float* x, float* o0, float* o1, int64_t n, float c, hipStream_t s);
-// the same with c = 1/sqrt(sigma^2 + 1) read from row idx[0] of a device table
-void lms_input_tab(const float* x, float* o0, float* o1, int64_t n, const float* tab, const int* idx, hipStream_t s);
-// x_out <- x + sum_{k < order} c[k] d_{i-k}, d_i = the CFG-combined eps (eps_c null: eps_u), stored to slot i & 3 of the ring
-// dhist (4 x n floats); the older derivatives are read from the slots (i-1) & 3 ...; x / x_out may be the same buffer
-void lms_step(const float* x, const float* eps_u, const float* eps_c, float guidance, float* dhist, float* x_out, int64_t n, int i, int order,
-              const float* c, hipStream_t s);
-// the step with i, order and c read from row idx[0] of a device table (the DDIM loop's counter)
-void lms_step_tab(const float* x, const float* eps_u, const float* eps_c, float guidance, float* dhist, float* x_out, int64_t n,
-                  const float* tab, const int* idx, hipStream_t s);
-void add_noise(const float* x0, const float* noise, float* out, int64_t n, float sa, float s1a, hipStream_t s);
 void fill_f32(float* p, int64_t n, float v, hipStream_t s);
 
 }  // namespace SDNS

@@ -1,6 +1,7 @@
 // Model graphs executed by the library: latent Transformer, SD VAE, SD UNet, DDIM loop.
 #pragma once
 #include "kernels.h"
+#include "sampler.h"
 #include <algorithm>
 #include <initializer_list>
 #include <memory>
@@ -170,25 +171,10 @@ struct UnetIface {
   virtual void finalize(svg_ctx* ctx, int64_t* n_params) = 0;
   virtual void forward(svg_ctx* ctx, const float* x, int N, int h, int w, const float* timesteps, const float* ctx_emb, int ctx_len,
                        float* eps_out, hipStream_t s) = 0;
-  virtual void ddim_loop(svg_ctx* ctx, float* z, int N, int h, int w, const float* text_emb, int ctx_len, int num_steps,
-                         int start_step, float guidance, const float* noise, float* hist, hipStream_t s) = 0;
-  virtual void ddim_coefs(int t, int t_prev, float* sa, float* s1a, float* sap, float* s1ap) const = 0;
-  // the img2img loop of ddim_loop under another update rule (kSampler*; ddim_loop == sample_loop(kSamplerDdim, ...))
+  // the img2img loop under the update rule `sampler` (kSampler* of sampler_plan.h, which also holds every schedule coefficient)
   virtual void sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, int w, const float* text_emb, int ctx_len, int num_steps,
                            int start_step, float guidance, const float* noise, float* hist, hipStream_t s) = 0;
-  // one DPM-Solver++(2M) table row (kDpmRow floats) for the step t -> t_next (< 0: alpha_bar = 1); t_last < 0: first order
-  virtual void dpmpp_coefs(int t, int t_next, int t_last, float* row) const = 0;
 };
-// sampler ids of svg_sample_loop (SVG_SAMPLER_* of include/svg_hip.h)
-enum { kSamplerDdim = 0, kSamplerDpmpp2m = 1, kSamplerLms = 2 };
-// The f32 alphas_cumprod of the scaled-linear schedule (0.00085 .. 0.012, 1000 train steps) as diffusers builds it: one table for
-// the DDIM / DPM++ coefficients of the UNet and for the LMS sigmas (host only, no device call).
-const std::vector<float>& sd_alphas_cumprod();
-// Step i of an n-step LMS schedule (diffusers 0.2.3 LMSDiscreteScheduler): timestep linspace(999, 0, n)[i], sigma_i and sigma_{i+1}
-// interpolated between the train sigmas sqrt((1 - abar) / abar) (sigma_n = 0), order min(i + 1, 4), and the integrals over
-// [sigma_i, sigma_{i+1}] of the Lagrange basis on sigma_i ... sigma_{i-order+1}, exact in double (c[k] = 0 for k >= order).
-struct LmsCoef { double t, sigma, sigma_next; int order; double c[4]; };
-void lms_coefs(int num_steps, int i, LmsCoef* out);
 VaeIface* new_vae_bf16();
 VaeIface* new_vae_f16();
 UnetIface* new_unet_bf16();
@@ -279,8 +265,6 @@ struct UnetModel : UnetIface {
   std::vector<std::vector<ResW>> down_res; std::vector<std::vector<XfBlockW>> down_attn; std::vector<ConvW> down_s;
   ResW mid0, mid1; XfBlockW mid_attn;
   std::vector<std::vector<ResW>> up_res; std::vector<std::vector<XfBlockW>> up_attn; std::vector<ConvW> up_s;
-  // DDIM tables (scaled_linear 0.00085..0.012, 1000 train steps)
-  std::vector<float> alphas_cumprod;   // = sd_alphas_cumprod()
   void configure(const char* kv) override;
   void finalize(svg_ctx* ctx, int64_t* n_params) override;
   // one UNet call (planned by the caller); cache: cross-attention K / V^T reuse across the steps of a DDIM loop
@@ -288,12 +272,8 @@ struct UnetModel : UnetIface {
            float* eps_out, hipStream_t s, KvCache* cache = nullptr, int64_t fp8_sites = -1);   // fp8_sites: MX-fp8 placement mask of this call (-1: all)
   void forward(svg_ctx* ctx, const float* x, int N, int h, int w, const float* timesteps, const float* ctx_emb, int ctx_len,
                float* eps_out, hipStream_t s) override;
-  void ddim_loop(svg_ctx* ctx, float* z, int N, int h, int w, const float* text_emb, int ctx_len, int num_steps,
-                 int start_step, float guidance, const float* noise, float* hist, hipStream_t s) override;
-  void ddim_coefs(int t, int t_prev, float* sa, float* s1a, float* sap, float* s1ap) const override;
   void sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, int w, const float* text_emb, int ctx_len, int num_steps,
                    int start_step, float guidance, const float* noise, float* hist, hipStream_t s) override;
-  void dpmpp_coefs(int t, int t_next, int t_last, float* row) const override;
 };
 
 // Request for the GroupNorm column sums of an output (GemmArgs::gn_part): the caller provides `buf` (gn_part_floats() floats, at

@@ -240,43 +240,8 @@ void UnetModel::finalize(svg_ctx* ctx, int64_t* n_params) {
   norm_out = load_norm(ctx, ws, "conv_norm_out", c0);
   conv_out = load_conv3x3(ctx, ws, "conv_out", c0, out_ch, s);
   temb_all = load_stacked(ctx, ws, tc.prefixes, tc.couts, temb_dim, true, s);
-  alphas_cumprod = sd_alphas_cumprod();
   if (n_params) *n_params = total;
   ready = true;
-}
-
-void UnetModel::ddim_coefs(int t, int t_prev, float* sa, float* s1a, float* sap, float* s1ap) const {
-  SVG_CHECK(t >= 0 && t < 1000, "ddim: timestep %d out of range", t);
-  const float a_t = alphas_cumprod[t];
-  const float a_p = (t_prev >= 0) ? alphas_cumprod[t_prev] : 1.0f;   // set_alpha_to_one
-  *sa = sqrtf(a_t); *s1a = sqrtf(1.f - a_t); *sap = sqrtf(a_p); *s1ap = sqrtf(1.f - a_p);
-}
-
-// DPM-Solver++(2M) on the DDIM timestep set, in double from the f32 alphas_cumprod: with a = sqrt(abar), sig = sqrt(1 - abar),
-// lambda = log a - log sig and h = lambda_s' - lambda_s:  x' = (sig_s'/sig_s) x + a_s'(1 - e^-h) D,  D = m + (m - m_prev) / 2r,
-// r = (lambda_s - lambda_last) / h (D = m at first order);  sig_s' == 0 (t_next < 0, set_alpha_to_one) is the final step: x' = m.
-void UnetModel::dpmpp_coefs(int t, int t_next, int t_last, float* row) const {
-  SVG_CHECK(t >= 0 && t < 1000 && t_next < t, "dpmpp: timesteps %d -> %d out of range", t, t_next);
-  SVG_CHECK(t_last < 0 || (t_last > t && t_last < 1000), "dpmpp: previous timestep %d is not in (%d, 1000)", t_last, t);
-  auto lam = [](double ab) { return 0.5 * log(ab) - 0.5 * log1p(-ab); };
-  const double ab = alphas_cumprod[t];
-  const double a = sqrt(ab), sig = sqrt(1.0 - ab);
-  for (int j = 0; j < kDpmRow; ++j) row[j] = 0.f;
-  row[0] = (float)t;
-  row[1] = (float)(1.0 / a);
-  row[2] = (float)sig;
-  if (t_next < 0) {                 // lower_order_final: x' = m
-    row[6] = 1.f;
-    return;
-  }
-  const double abn = alphas_cumprod[t_next];
-  const double h = lam(abn) - lam(ab);
-  row[3] = (float)(sqrt(1.0 - abn) / sig);
-  row[4] = (float)(-sqrt(abn) * expm1(-h));
-  if (t_last >= 0) {
-    const double r = (lam(ab) - lam(alphas_cumprod[t_last])) / h;
-    row[5] = (float)(0.5 / r);
-  }
 }
 
 namespace {
@@ -632,45 +597,27 @@ void UnetModel::run(svg_ctx* ctx, const float* x, int N, int h, int w, const flo
   if (cache && SVG_LAUNCHING(ctx)) cache->valid = true;   // every block's K / V^T of this context is now stored
 }
 
-void UnetModel::ddim_loop(svg_ctx* ctx, float* z, int N, int h, int w, const float* text_emb, int ctx_len, int num_steps,
-                          int start_step, float guidance, const float* noise, float* hist, hipStream_t s) {
-  sample_loop(ctx, kSamplerDdim, z, N, h, w, text_emb, ctx_len, num_steps, start_step, guidance, noise, hist, s);
-}
-
-// The img2img loop of either sampler: the same timesteps, add_noise, CFG combine, K / V^T cache, fp8 placement and step graph; only
-// the update kernel and its table differ.  DPM++(2M) keeps the previous step's x0 prediction in `mprev` (one latent-sized buffer).
-// LMS (the reference's text-to-image sampler, denoise_img_latents) shares the loop but not the schedule: timesteps linspace(999, 0, n),
-// z = unit-normal draws scaled by sigma_0 on entry, the UNet input is z / sqrt(sigma_i^2 + 1) (lms_input, in place of the guided
-// path's two copies), and the last four derivatives live in the ring `dhist`.  It always starts at step 0 and ignores `noise`.
+// The img2img loop of every sampler: the same add_noise, CFG combine, K / V^T cache, fp8 placement and step graph; the schedule, the
+// update kernel and the state it keeps between steps come from the plan (sampler_plan.h).  DPM++(2M) keeps the previous step's x0
+// prediction, LMS (the reference's text-to-image sampler, denoise_img_latents) the ring of the last four derivatives.  LMS shares the
+// loop but not the schedule: timesteps linspace(999, 0, n), z = unit-normal draws scaled by sigma_0 on entry, and the UNet input is
+// z / sqrt(sigma_i^2 + 1) (lms_input, in place of the guided path's two copies).  It always starts at step 0 and ignores `noise`.
 void UnetModel::sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, int w, const float* text_emb, int ctx_len, int num_steps,
                             int start_step, float guidance, const float* noise, float* hist, hipStream_t s) {
   SVG_CHECK(ready, "unet: svg_finalize has not been called");
-  SVG_CHECK(sampler == kSamplerDdim || sampler == kSamplerDpmpp2m || sampler == kSamplerLms, "sample_loop: unknown sampler %d", sampler);
-  const bool dpm = sampler == kSamplerDpmpp2m, lms = sampler == kSamplerLms;
-  const int row = lms ? kLmsRow : dpm ? kDpmRow : 5;      // floats per table row
-  SVG_CHECK(num_steps >= 1 && num_steps <= 1000 && start_step >= 0 && start_step <= num_steps, "ddim: bad steps %d/%d", start_step, num_steps);
-  SVG_CHECK(!lms || start_step == 0, "lms: start_step must be 0 (got %d): the multistep rule has no history to start from", start_step);
+  const SamplerPlan plan = sampler_plan(sampler, num_steps, start_step);
   SVG_CHECK(start_step == 0 || noise, "ddim: start_step > 0 needs the add_noise draws");
-  std::vector<LmsCoef> lc(lms ? num_steps : 0);
-  for (int i = 0; i < (int)lc.size(); ++i) lms_coefs(num_steps, i, &lc[i]);
-  auto lms_row = [&](int i, float* r) {    // {t, 1/sqrt(sigma^2 + 1), order, i, c0..c3}
-    r[0] = (float)lc[i].t; r[1] = (float)(1.0 / sqrt(lc[i].sigma * lc[i].sigma + 1.0)); r[2] = (float)lc[i].order; r[3] = (float)i;
-    for (int k = 0; k < 4; ++k) r[4 + k] = (float)lc[i].c[k];
-  };
-  const int ratio = 1000 / num_steps;
   const int64_t n = (int64_t)N * in_ch * h * w;
   const bool cfg = guidance != 0.f;
   const int NB = cfg ? 2 * N : N;
   // the e4m3 placement of this loop (see kFp8SitesGuided): handed to every UNet call of the loop as an argument
   const int64_t sites = cfg ? svg_env_i64("SVG_FP8_SITES_GUIDED", kFp8SitesGuided) : -1;
-  const int64_t emb_n = (int64_t)N * ctx_len * ctx_dim;
-  auto timestep_at = [&](int i) { return (num_steps - 1 - i) * ratio; };   // (arange(n)*ratio)[::-1]
 
-  // One DDIM step as a hipGraph: the first step runs as direct launches (it fills the cross-attention K / V^T cache), the second is
+  // One step as a hipGraph: the first step runs as direct launches (it fills the cross-attention K / V^T cache), the second is
   // CAPTURED on the caller's stream and the remaining ones replay it.  Everything a step needs that changes from step to step —
-  // the timestep of the embedding and the four scheduler coefficients — is read from a device table row selected by a device
-  // counter (ddim_step_tab / ddim_tvec / ddim_bump), so a replay needs no new kernel arguments.  The graph bakes arena pointers:
-  // it lives for this call only (the arena is planned just above and cannot move until the loop ends).  Off: SVG_DDIM_GRAPH=0,
+  // the timestep of the embedding and the scheduler coefficients — is read from the plan's table on the device, its row selected by
+  // a device counter (sampler_tvec / sampler_row_at / sampler_bump), so a replay needs no new kernel arguments.  The graph bakes arena
+  // pointers: it lives for this call only (the arena is planned just above and cannot move until the loop ends).  Off: SVG_DDIM_GRAPH=0,
   // the legacy null stream (not capturable), the profiler's event brackets, and the latent history (a per-step copy target).
   const int graph_env = (int)svg_env_i64("SVG_DDIM_GRAPH", 1);      // cached; the tests toggle it in-process and call svg_env_refresh
   const bool use_graph = graph_env && s != nullptr && !ctx->prof && !hist && (num_steps - start_step) >= 3;
@@ -678,50 +625,33 @@ void UnetModel::sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, i
   // planned once for the whole loop: every step has the same shapes
   auto body = [&]() {
     kv.valid = false;   // the context is constant over the loop: K / V^T of the cross-attentions are computed once
+    const bool own_input = cfg || plan.scaled_input;   // the UNet reads zin: both halves of a guided batch, or the scaled copy, never z itself
     float* tvec = ctx->arena.get<float>(NB);
-    float* zin = (cfg || lms) ? ctx->arena.get<float>((cfg ? 2 : 1) * n) : nullptr;   // LMS: the scaled input, never z itself
+    float* zin = own_input ? ctx->arena.get<float>((cfg ? 2 : 1) * n) : nullptr;
     float* eps = ctx->arena.get<float>((int64_t)NB * n / N);
-    float* tab = ctx->arena.get<float>((int64_t)row * num_steps);
+    float* tab = ctx->arena.get<float>((int64_t)plan.table.size());
     int* idx = ctx->arena.get<int>(1);
-    float* mprev = dpm ? ctx->arena.get<float>(n) : nullptr;   // DPM++: the previous step's x0 prediction
-    float* dhist = lms ? ctx->arena.get<float>(4 * n) : nullptr;   // LMS: the ring of the last four derivatives
+    float* state = plan.state_buffers ? ctx->arena.get<float>(plan.state_buffers * n) : nullptr;
     if (SVG_LAUNCHING(ctx)) {
-      if (start_step > 0 && start_step < num_steps) {
-        const float a = alphas_cumprod[timestep_at(start_step)];
-        add_noise(z, noise, z, n, sqrtf(a), sqrtf(1.f - a), s);
-      }
-      if (lms) lms_input(z, z, nullptr, n, (float)lc[0].sigma, s);   // x <- sigma_0 x
+      if (plan.add_noise) add_noise(z, noise, z, n, plan.noise_sa, plan.noise_s1a, s);
+      if (plan.scaled_input) lms_input(z, z, nullptr, n, sampler_scale(plan.z_scale), s);   // x <- sigma_0 x
       if (hist) HIP_OK(hipMemcpyAsync(hist, z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
       if (use_graph) {
-        std::vector<float> h((size_t)row * num_steps);
-        for (int i = 0; i < num_steps; ++i) {
-          const int t = timestep_at(i);
-          if (lms) {
-            lms_row(i, &h[(size_t)row * i]);
-          } else if (dpm) {
-            dpmpp_coefs(t, t - ratio, i > start_step ? timestep_at(i - 1) : -1, &h[(size_t)row * i]);
-          } else {
-            h[5 * i] = (float)t;
-            ddim_coefs(t, t - ratio, &h[5 * i + 1], &h[5 * i + 2], &h[5 * i + 3], &h[5 * i + 4]);
-          }
-        }
         // pageable host memory: the copy is staged before the call returns
-        HIP_OK(hipMemcpyAsync(tab, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_OK(hipMemcpyAsync(tab, plan.table.data(), plan.table.size() * sizeof(float), hipMemcpyHostToDevice, s));
         const int first = start_step;
         HIP_OK(hipMemcpyAsync(idx, &first, sizeof(int), hipMemcpyHostToDevice, s));
         HIP_OK(hipStreamSynchronize(s));
       }
     }
     auto one_step = [&](int i, bool tabled) {
-      const int t = timestep_at(i);
+      const SamplerRowArg row = tabled ? sampler_row_at(tab, idx) : sampler_row(plan.row(i));
       ctx->arena.push();
       if (SVG_LAUNCHING(ctx)) {
-        if (tabled) ddim_tvec(tvec, NB, tab, idx, s, row);
-        else fill_f32(tvec, NB, lms ? (float)lc[i].t : (float)t, s);
-        if (lms) {
-          float r[kLmsRow];
-          if (tabled) lms_input_tab(z, zin, cfg ? zin + n : nullptr, n, tab, idx, s);
-          else { lms_row(i, r); lms_input(z, zin, cfg ? zin + n : nullptr, n, r[1], s); }
+        if (tabled) sampler_tvec(tvec, NB, tab, idx, s);
+        else fill_f32(tvec, NB, plan.timestep(i), s);
+        if (plan.scaled_input) {
+          lms_input(z, zin, cfg ? zin + n : nullptr, n, row, s);
         } else if (cfg) {
           HIP_OK(hipMemcpyAsync(zin, z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
           HIP_OK(hipMemcpyAsync(zin + n, z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -730,32 +660,12 @@ void UnetModel::sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, i
       // guidance == 0: noise_pred = uncond + 0*(text - uncond) == uncond — only the uncond half is needed
       std::unique_ptr<ProfScope> step_scope;
       if (SVG_LAUNCHING(ctx)) step_scope.reset(new ProfScope(ctx, PK_UNET_STEP, s, 0, 0));
-      run(ctx, (cfg || lms) ? zin : z, NB, h, w, tvec, text_emb, ctx_len, eps, s, &kv, sites);
+      run(ctx, own_input ? zin : z, NB, h, w, tvec, text_emb, ctx_len, eps, s, &kv, sites);
       if (SVG_LAUNCHING(ctx)) {
-        if (tabled) {
-          if (lms) lms_step_tab(z, eps, cfg ? eps + n : nullptr, guidance, dhist, z, n, tab, idx, s);
-          else if (dpm) dpmpp_step_tab(z, eps, cfg ? eps + n : nullptr, guidance, mprev, z, n, tab, idx, s);
-          else ddim_step_tab(z, eps, cfg ? eps + n : nullptr, guidance, z, n, tab, idx, s);
-          ddim_bump(idx, s);
-        } else if (lms) {
-          float r[kLmsRow];
-          lms_row(i, r);
-          ProfScope ps(ctx, PK_ELT, s, 0, 0);
-          lms_step(z, eps, cfg ? eps + n : nullptr, guidance, dhist, z, n, i, lc[i].order, r + 4, s);
-          if (hist) HIP_OK(hipMemcpyAsync(hist + (int64_t)(i - start_step + 1) * n, z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-        } else if (dpm) {
-          float r[kDpmRow];
-          dpmpp_coefs(t, t - ratio, i > start_step ? timestep_at(i - 1) : -1, r);
-          ProfScope ps(ctx, PK_ELT, s, 0, 0);
-          dpmpp_step(z, eps, cfg ? eps + n : nullptr, guidance, mprev, z, mprev, n, r, s);
-          if (hist) HIP_OK(hipMemcpyAsync(hist + (int64_t)(i - start_step + 1) * n, z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-        } else {
-          float sa, s1a, sap, s1ap;
-          ddim_coefs(t, t - ratio, &sa, &s1a, &sap, &s1ap);
-          ProfScope ps(ctx, PK_ELT, s, 0, 0);
-          ddim_step(z, eps, cfg ? eps + n : nullptr, guidance, z, n, sa, s1a, sap, s1ap, s);
-          if (hist) HIP_OK(hipMemcpyAsync(hist + (int64_t)(i - start_step + 1) * n, z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-        }
+        ProfScope ps(ctx, PK_ELT, s, 0, 0);              // (a tabled step is never profiled: use_graph)
+        sampler_step(sampler, z, eps, cfg ? eps + n : nullptr, guidance, state, n, row, s);
+        if (tabled) sampler_bump(idx, s);
+        if (hist) HIP_OK(hipMemcpyAsync(hist + (int64_t)(i - start_step + 1) * n, z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
       }
       step_scope.reset();
       ctx->arena.pop();
@@ -800,7 +710,6 @@ void UnetModel::sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, i
     HIP_OK(ge);
     HIP_OK(se);
   };
-  (void)emb_n;
   run_planned(ctx, body);
 }
 
