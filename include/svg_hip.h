@@ -502,6 +502,31 @@ int svg_op_xf_embed_post_bwd(svg_ctx* ctx, const float* dy, float* de, int B, in
                              float p, void* stream);
 int svg_op_xf_criterion(svg_ctx* ctx, const float* pred, const float* expected, float* dpred, float* losses, int Tt, int B, int D, int t0,
                         int fh, int fw, float w_mse, float w_l1, float w_gdl, float alpha, float w_nce, float temperature, void* stream);
+/* The kernels of the FVD evaluation one by one (test hooks: each is the launcher the I3D forward / svg_frechet_distance calls, nothing
+ * is added).  Device buffers; activations f32 channels-last (B,T,H,W,C).
+ * svg_op_conv3d: Unit3D without its BatchNorm arithmetic: x (B,T,H,W,Cin_pad), Cin_pad % 4 == 0; w / bias as svg_op_pack_conv3d leaves
+ *   them (bias may be NULL); TF 'SAME' padding: the output sizes and front pads are computed inside from (size, k, stride) by the rule
+ *   the model uses, out_thw receives {To, Ho, Wo}; y (B,To,Ho,Wo,ldc) of y_elems floats, of which channels [coff, coff + Cout) are
+ *   written; k / stride: {t, h, w}.
+ * svg_op_pack_conv3d: w (Cout,Cin,taps) in PyTorch's layout -> wout (Cout,taps,Cin_pad) (padded channels 0), bout (Cout); with gamma /
+ *   beta / mean / var: BatchNorm (eval) folded in (wout = w gamma / sqrt(var + eps), bout = beta - mean gamma / sqrt(var + eps));
+ *   otherwise bout = cbias, or 0 when that is NULL too.
+ * svg_op_maxpool3d_same: MaxPool3dSamePadding, sizes and pads as for the conv (the zero padding takes part in the max); C % 4 == 0.
+ * svg_op_avgpool_thw: x (B,T,HW,C) -> y (B,T-kt+1,C), the mean over kt frames x the whole plane.  svg_op_time_mean: x (B,To,C) -> y (B,C).
+ * svg_op_ncthw_to_nthwc: x (B,C,T,H,W) -> y (B,T,H,W,Cp), channels C .. Cp-1 zero.
+ * svg_op_fd_moments: x (n,d) f32 -> mean f64[d], cov f64[d][d] (unbiased); n >= 2, even d <= 2048 as svg_frechet_distance.
+ * svg_op_sym_eig: symmetric A f64 (d,d), d even -> eig f64[d] (unordered), V f64 (d,d) whose column k is the eigenvector of eig[k]. */
+int svg_op_conv3d(svg_ctx* ctx, const float* x, int B, int T, int H, int W, int Cin_pad, const float* w, const float* bias, float* y,
+                  int64_t y_elems, int Cout, int ldc, int coff, const int* k, const int* stride, int relu, int* out_thw, void* stream);
+int svg_op_pack_conv3d(svg_ctx* ctx, const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
+                       const float* cbias, float* wout, float* bout, int Cout, int Cin, int Cin_pad, int taps, float eps, void* stream);
+int svg_op_maxpool3d_same(svg_ctx* ctx, const float* x, float* y, int64_t y_elems, int B, int T, int H, int W, int C, const int* k,
+                          const int* stride, int* out_thw, void* stream);
+int svg_op_avgpool_thw(svg_ctx* ctx, const float* x, float* y, int B, int T, int HW, int C, int kt, void* stream);
+int svg_op_time_mean(svg_ctx* ctx, const float* x, float* y, int B, int To, int C, void* stream);
+int svg_op_ncthw_to_nthwc(svg_ctx* ctx, const float* x, float* y, int B, int C, int T, int H, int W, int Cp, void* stream);
+int svg_op_fd_moments(svg_ctx* ctx, const float* x, int n, int d, double* mean, double* cov, void* stream);
+int svg_op_sym_eig(svg_ctx* ctx, const double* A, int d, double* eig, double* V, void* stream);
 /* MX block-scaled fp8 (BASELINE configs[4]): OCP e4m3 elements with one E8M0 scale per 32 consecutive K elements.
  * svg_op_quant_mx: x (rows,K) bf16 -> q (rows,K) e4m3 bytes, scales (rows,K/32) bytes; shared exponent floor(log2(amax)) - 8,
  * round to nearest even, saturating at +-448 (OCP MX v1.0).  K % 32 == 0. */

@@ -81,6 +81,12 @@ def seeded_i3d_weights(seed, num_classes=400):
     return sd
 
 
+def seeded_clips(seed, T, B=1):
+    """(B,3,T,224,224) f32 uniform in [-1,1): seeded network inputs of any clip length"""
+    g = torch.Generator().manual_seed(seed * 1009 + T)
+    return torch.rand(B, 3, T, 224, 224, generator=g) * 2 - 1
+
+
 def _same_pad(x, kernel, stride):
     """compute_pad of Unit3D / MaxPool3dSamePadding (pytorch_i3d.py:10-36,72-95): zero padding, front = total // 2"""
     pads = []
@@ -129,11 +135,12 @@ def i3d_forward(sd, x, upto=None):
 
 
 # ---- fvd_2.py ------------------------------------------------------------------------------------------------------------------
-def preprocess(videos_u8, resolution=224):
-    """(b,t,h,w,c) uint8 tensor -> (b,c,t,224,224) f32 in [-1,1] (fvd_2.py:7-14,109-136)"""
+def preprocess(videos_u8, resolution=224, dtype=torch.float32):
+    """(b,t,h,w,c) uint8 tensor -> (b,c,t,224,224) f32 in [-1,1] (fvd_2.py:7-14,109-136); dtype: the arithmetic (the per-kernel tests
+    take the same formula in float64)"""
     out = []
     for video in videos_u8:
-        v = video.permute(0, 3, 1, 2).float() / 255.0
+        v = video.permute(0, 3, 1, 2).to(dtype) / 255.0
         t, c, h, w = v.shape
         scale = resolution / min(h, w)
         size = (resolution, math.ceil(w * scale)) if h < w else (math.ceil(h * scale), resolution)

@@ -143,6 +143,14 @@ SIGNATURES = {
     "svg_op_xf_embed_post_train": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _f, C.c_uint64, _i, _f, _vp],
     "svg_op_xf_embed_post_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _f, C.c_uint64, _i, _f, _vp],
     "svg_op_xf_criterion": [_vp, _vp, _vp, _vp, C.POINTER(_f), _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp],
+    "svg_op_conv3d": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _i, C.POINTER(_i), _vp],
+    "svg_op_pack_conv3d": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
+    "svg_op_maxpool3d_same": [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp],
+    "svg_op_avgpool_thw": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "svg_op_time_mean": [_vp, _vp, _vp, _i, _i, _i, _vp],
+    "svg_op_ncthw_to_nthwc": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "svg_op_fd_moments": [_vp, _vp, _i, _i, _vp, _vp, _vp],
+    "svg_op_sym_eig": [_vp, _vp, _i, _vp, _vp, _vp],
     "svg_op_conv3x3_mx": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "svg_op_conv3x3_mx_ex": [_vp, C.POINTER(ConvMxDesc), C.POINTER(_i), _vp],
     "svg_op_quant_mx": [_vp, _vp, _vp, _vp, _i64, _i, _vp],

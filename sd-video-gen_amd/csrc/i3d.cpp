@@ -21,6 +21,8 @@ void avgpool_thw(const float* x, float* y, int B, int T, int HW, int C, int kt, 
 void time_mean(const float* x, float* y, int B, int To, int C, hipStream_t s);
 void ncthw_to_nthwc(const float* x, float* y, int B, int C, int T, int H, int W, int Cp, hipStream_t s);
 void fvd_preprocess(const uint8_t* v, float* out, int B, int T, int H, int W, int res, hipStream_t s);
+void fd_moments(const float* x, int n, int d, double* mean, double* cov, hipStream_t s);
+void sym_eig(double* A, double* V, int d, double* cs, hipStream_t s);
 void frechet_distance(const float* x1, int n1, const float* x2, int n2, int d, double* ws, double* out, hipStream_t s);
 
 namespace {
@@ -208,6 +210,101 @@ int svg_frechet_distance(svg_ctx* ctx, const float* x1, int n1, const float* x2,
     });
     HIP_OK(hipMemcpyAsync(out_host, out_dev, sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+// ---- the kernels one by one (test hooks: each is the launcher the model calls; sizes and pads come from same_pad above) ----------------
+int svg_op_conv3d(svg_ctx* ctx, const float* x, int B, int T, int H, int W, int Cin_pad, const float* w, const float* bias, float* y, int64_t y_elems,
+                  int Cout, int ldc, int coff, const int* k, const int* stride, int relu, int* out_thw, void* stream) {
+  try {
+    SVG_CHECK(ctx && x && w && y && k && stride && out_thw, "svg_op_conv3d: null argument");
+    SVG_CHECK(B >= 1 && T >= 1 && H >= 1 && W >= 1 && Cin_pad >= 4 && Cin_pad % 4 == 0, "svg_op_conv3d: input (%d,%d,%d,%d,%d) (channels: a multiple of 4)", B, T,
+              H, W, Cin_pad);
+    SVG_CHECK(Cout >= 1 && coff >= 0 && coff + Cout <= ldc, "svg_op_conv3d: channels [%d, %d + %d) of %d", coff, coff, Cout, ldc);
+    for (int i = 0; i < 3; ++i) SVG_CHECK(k[i] >= 1 && stride[i] >= 1, "svg_op_conv3d: kernel %d / stride %d on axis %d", k[i], stride[i], i);
+    int To, Ho, Wo, pt, ph, pw;
+    same_pad(T, k[0], stride[0], &To, &pt);
+    same_pad(H, k[1], stride[1], &Ho, &ph);
+    same_pad(W, k[2], stride[2], &Wo, &pw);
+    SVG_CHECK(To >= 1 && Ho >= 1 && Wo >= 1 && (int64_t)B * To * Ho * Wo * ldc <= y_elems, "svg_op_conv3d: output (%d,%d,%d,%d,%d) against %lld elements of y", B,
+              To, Ho, Wo, ldc, (long long)y_elems);
+    Conv3dArgs a{x, B, T, H, W, Cin_pad, w, bias, y, To, Ho, Wo, Cout, ldc, coff, k[0], k[1], k[2], stride[0], stride[1], stride[2], pt, ph, pw, relu ? 1 : 0};
+    conv3d_launch(a, (hipStream_t)stream);
+    out_thw[0] = To; out_thw[1] = Ho; out_thw[2] = Wo;
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+int svg_op_pack_conv3d(svg_ctx* ctx, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, const float* cbias,
+                       float* wout, float* bout, int Cout, int Cin, int Cin_pad, int taps, float eps, void* stream) {
+  try {
+    SVG_CHECK(ctx && w && wout && bout, "svg_op_pack_conv3d: null argument");
+    SVG_CHECK(!gamma || (beta && mean && var && !cbias), "svg_op_pack_conv3d: BatchNorm takes gamma, beta, mean and var, and no conv bias");
+    SVG_CHECK(Cout >= 1 && Cin >= 1 && Cin_pad >= Cin && taps >= 1, "svg_op_pack_conv3d: Cout %d Cin %d (stored %d) taps %d", Cout, Cin, Cin_pad, taps);
+    pack_conv3d(w, gamma, beta, mean, var, cbias, wout, bout, Cout, Cin, Cin_pad, taps, eps, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+int svg_op_maxpool3d_same(svg_ctx* ctx, const float* x, float* y, int64_t y_elems, int B, int T, int H, int W, int C, const int* k, const int* stride,
+                          int* out_thw, void* stream) {
+  try {
+    SVG_CHECK(ctx && x && y && k && stride && out_thw, "svg_op_maxpool3d_same: null argument");
+    SVG_CHECK(B >= 1 && T >= 1 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0, "svg_op_maxpool3d_same: input (%d,%d,%d,%d,%d) (channels: a multiple of 4)", B, T, H, W, C);
+    for (int i = 0; i < 3; ++i) SVG_CHECK(k[i] >= 1 && stride[i] >= 1, "svg_op_maxpool3d_same: kernel %d / stride %d on axis %d", k[i], stride[i], i);
+    int o[3], pf[3];
+    same_pad(T, k[0], stride[0], &o[0], &pf[0]);
+    same_pad(H, k[1], stride[1], &o[1], &pf[1]);
+    same_pad(W, k[2], stride[2], &o[2], &pf[2]);
+    SVG_CHECK(o[0] >= 1 && o[1] >= 1 && o[2] >= 1 && (int64_t)B * o[0] * o[1] * o[2] * C <= y_elems, "svg_op_maxpool3d_same: output (%d,%d,%d,%d,%d) against %lld elements of y",
+              B, o[0], o[1], o[2], C, (long long)y_elems);
+    maxpool3d_same(x, y, B, T, H, W, C, o[0], o[1], o[2], k, stride, pf, (hipStream_t)stream);
+    for (int i = 0; i < 3; ++i) out_thw[i] = o[i];
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+int svg_op_avgpool_thw(svg_ctx* ctx, const float* x, float* y, int B, int T, int HW, int C, int kt, void* stream) {
+  try {
+    SVG_CHECK(ctx && x && y && B >= 1 && HW >= 1 && C >= 1 && kt >= 1 && T >= kt, "svg_op_avgpool_thw: bad arguments (B %d T %d HW %d C %d kt %d)", B, T, HW, C, kt);
+    avgpool_thw(x, y, B, T, HW, C, kt, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+int svg_op_time_mean(svg_ctx* ctx, const float* x, float* y, int B, int To, int C, void* stream) {
+  try {
+    SVG_CHECK(ctx && x && y && B >= 1 && To >= 1 && C >= 1, "svg_op_time_mean: bad arguments (B %d To %d C %d)", B, To, C);
+    time_mean(x, y, B, To, C, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+int svg_op_ncthw_to_nthwc(svg_ctx* ctx, const float* x, float* y, int B, int C, int T, int H, int W, int Cp, void* stream) {
+  try {
+    SVG_CHECK(ctx && x && y && B >= 1 && C >= 1 && T >= 1 && H >= 1 && W >= 1 && Cp >= C, "svg_op_ncthw_to_nthwc: bad arguments (%d,%d,%d,%d,%d) -> %d channels", B,
+              C, T, H, W, Cp);
+    ncthw_to_nthwc(x, y, B, C, T, H, W, Cp, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+int svg_op_fd_moments(svg_ctx* ctx, const float* x, int n, int d, double* mean, double* cov, void* stream) {
+  try {
+    SVG_CHECK(ctx && x && mean && cov, "svg_op_fd_moments: null argument");
+    SVG_CHECK(n >= 2 && d >= 2 && d % 2 == 0 && d <= 2048, "svg_op_fd_moments: n=%d d=%d (>= 2 samples, even d <= 2048)", n, d);
+    fd_moments(x, n, d, mean, cov, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+int svg_op_sym_eig(svg_ctx* ctx, const double* A, int d, double* eig, double* V, void* stream) {
+  try {
+    SVG_CHECK(ctx && A && eig && V, "svg_op_sym_eig: null argument");
+    SVG_CHECK(d >= 2 && d % 2 == 0 && d <= 2048, "svg_op_sym_eig: d=%d (even, 2 .. 2048)", d);
+    hipStream_t s = (hipStream_t)stream;
+    run_planned(ctx, [&]() {
+      double* wk = ctx->arena.get<double>((int64_t)d * d + 2 * d);      // the matrix (diagonalised in place) + the rotation / pair tables
+      if (SVG_LAUNCHING(ctx)) {
+        HIP_OK(hipMemcpyAsync(wk, A, (size_t)d * d * sizeof(double), hipMemcpyDeviceToDevice, s));
+        sym_eig(wk, V, d, wk + (int64_t)d * d, s);
+        HIP_OK(hipMemcpy2DAsync(eig, sizeof(double), wk, (size_t)(d + 1) * sizeof(double), sizeof(double), d, hipMemcpyDeviceToDevice, s));
+      }
+    });
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }

@@ -357,25 +357,37 @@ void fvd_preprocess(const uint8_t* v, float* out, int B, int T, int H, int W, in
   check_launch("fvd_preprocess");
 }
 
+// mean[d], cov[d][d] (unbiased) of the rows of x (n,d) f32, in f64
+void fd_moments(const float* x, int n, int d, double* mean, double* cov, hipStream_t s) {
+  const dim3 g1((d + 127) / 128), g2((d + 127) / 128, d);
+  hipLaunchKernelGGL(col_mean_kernel, g1, dim3(128), 0, s, x, mean, n, d);
+  hipLaunchKernelGGL(cov_kernel, g2, dim3(128), 0, s, x, mean, cov, n, d);
+  check_launch("fd_moments");
+}
+// symmetric A (d x d f64, d even) -> its eigenvalues on A's diagonal (in place), V's columns the eigenvectors.  cs: 2 d doubles of scratch
+// (d doubles of rotations + d ints of pairs)
+void sym_eig(double* A, double* V, int d, double* cs, hipStream_t s) {
+  constexpr int sweeps = 40;      // an upper bound: the kernel stops when the off-diagonal mass is below 1e-30 of the diagonal's (10-12 sweeps full rank, ~20 rank-deficient)
+  hipLaunchKernelGGL(jacobi_eig_kernel, dim3(1), dim3(1024), 0, s, A, V, d, sweeps, cs);
+  check_launch("sym_eig");
+}
+
 // Fréchet distance of two embedding sets (n1,d), (n2,d) f32 -> out[0] f64.  ws: 6 d^2 + 8 d doubles of device scratch.
 void frechet_distance(const float* x1, int n1, const float* x2, int n2, int d, double* ws, double* out, hipStream_t s) {
   double* m1 = ws; double* m2 = m1 + d; double* sq = m2 + d; double* cs = sq + d;       // cs: d doubles of rotations + d ints of pairs
   double* S1 = cs + 2 * d; double* S2 = S1 + (int64_t)d * d; double* Wk = S2 + (int64_t)d * d; double* V = Wk + (int64_t)d * d;
   double* R = V + (int64_t)d * d; double* T2 = R + (int64_t)d * d;
   const dim3 g1((d + 127) / 128), g2((d + 127) / 128, d);
-  constexpr int sweeps = 40;      // an upper bound: the kernel stops when the off-diagonal mass is below 1e-30 of the diagonal's (10-12 sweeps full rank, ~20 rank-deficient)
-  hipLaunchKernelGGL(col_mean_kernel, g1, dim3(128), 0, s, x1, m1, n1, d);
-  hipLaunchKernelGGL(col_mean_kernel, g1, dim3(128), 0, s, x2, m2, n2, d);
-  hipLaunchKernelGGL(cov_kernel, g2, dim3(128), 0, s, x1, m1, S1, n1, d);
-  hipLaunchKernelGGL(cov_kernel, g2, dim3(128), 0, s, x2, m2, S2, n2, d);
+  fd_moments(x1, n1, d, m1, S1, s);
+  fd_moments(x2, n2, d, m2, S2, s);
   // sqrt(S1) = V f(L) V^T  (fvd_2.py:22-26 takes it from the SVD: for a symmetric PSD matrix the same factors)
   HIP_OK(hipMemcpyAsync(Wk, S1, (size_t)d * d * sizeof(double), hipMemcpyDeviceToDevice, s));
-  hipLaunchKernelGGL(jacobi_eig_kernel, dim3(1), dim3(1024), 0, s, Wk, V, d, sweeps, cs);
+  sym_eig(Wk, V, d, cs, s);
   hipLaunchKernelGGL(diag_sqrt_kernel, g1, dim3(128), 0, s, Wk, sq, d, 1e-10);
   hipLaunchKernelGGL(matmul_f64_kernel, g2, dim3(128), 0, s, V, sq, V, 1, R, d);          // R = V diag(sq) V^T = sqrt(S1)
   hipLaunchKernelGGL(matmul_f64_kernel, g2, dim3(128), 0, s, R, (const double*)nullptr, S2, 0, T2, d);
   hipLaunchKernelGGL(matmul_f64_kernel, g2, dim3(128), 0, s, T2, (const double*)nullptr, R, 0, Wk, d);   // sqrt(S1) S2 sqrt(S1)
-  hipLaunchKernelGGL(jacobi_eig_kernel, dim3(1), dim3(1024), 0, s, Wk, V, d, sweeps, cs);
+  sym_eig(Wk, V, d, cs, s);
   hipLaunchKernelGGL(diag_sqrt_kernel, g1, dim3(128), 0, s, Wk, sq, d, 1e-10);           // trace of the square root = sum of sqrt(eigenvalues)
   hipLaunchKernelGGL(fd_finish_kernel, dim3(1), dim3(1), 0, s, S1, S2, sq, m1, m2, out, d);
   check_launch("frechet_distance");
