@@ -701,6 +701,64 @@ int svg_op_rowsum_f16(svg_ctx* ctx, const uint16_t* w, float* out, int N, int K,
 /* f32 skinny GEMM of the latent Transformer: Y[M,N] = X[M,K] * W[N,K]^T + bias (relu_in: X:=max(X,0)). */
 int svg_op_xf_gemm(svg_ctx* ctx, const float* X, const float* W, const float* bias, float* Y,
                    int M, int N, int K, int relu_in, void* stream);
+/* The forward kernels of the latent Transformer, the CLIP text tower and the MiniLM sentence encoder one by one (test hooks: each is
+ * its launcher, nothing is added; f32 device buffers).  Each hook checks what its launcher assumes of its arguments and returns
+ * SVG_ERR_INVALID without launching when a check fails.
+ * svg_xf_gemm_describe: host only (no context, no device): path[3] = {form, mt, ksplit} of the launch svg_op_xf_gemm(_ex) makes for
+ *   (M, N, K): form 1 = 16-column form, 2 = column-block form; mt = accumulator height in 16-row tiles; ksplit = split-K factor.
+ * svg_op_xf_gemm_ex: Y[M,N] = act_in(X[M,K]) W[N,K]^T + bias[N] + residual[M,N]; bias / residual may be NULL; act_in 0 none, 1 ReLU,
+ *   2 quick-GELU, 3 exact GELU; 1 <= M <= 336, K % 8 == 0, N % 4 == 0; path (or NULL) receives the three ints of the launch made.
+ * svg_op_xf_add_ln: y = LayerNorm(x + r) gamma + beta over M rows of d <= 3072 (r may be NULL).
+ * svg_op_xf_embed_post: emb (B*T, d - d_txt) -> y (T,B,d) = v * scale + pe[pe_row[b]]; the last d_txt channels of every token come
+ *   from text (B,d_txt); pe is a table of 64 rows of d: pe_row (B int32, or NULL: row b, B <= 64) holds values in 0..63.
+ * svg_op_xf_attention: o (Tq,B,heads*hd) = softmax(q k^T / sqrt(hd) + mask + kpad) v per (batch row, head); q rows (t*B + b) of
+ *   stride ldq, k / v rows of stride ldk; mask (Tq,Tk) and kpad (B,Tk) additive, may be NULL; Tq, Tk <= 32.
+ * svg_op_xf_attention_qkv: packed rows (b*T + t) of [q | k | v] (3*heads*hd floats) -> o (B*T, heads*hd); lens NULL: causal (CLIP);
+ *   lens (B int32): bidirectional over the first clamp(lens[b], 1, T) keys (BERT); T <= 128, hd <= 64.
+ * svg_op_xf_embed_tokens: y[row] = tok[clamp(ids[row], 0, vocab-1)] + pos[row % T]; svg_op_xf_embed_bert: + type0; d % 4 == 0.
+ * svg_op_xf_mean_pool_norm: out[b] = normalize(mean of the first clamp(lens[b], 0, T) rows of x[b]) (zeros for no rows).
+ * svg_op_xf_walk: one layer-walking launch over a caller's stage table (small != 0: the small-row form, rows is ignored and 8 is
+ *   taken); the table passes the launch's own validation; the hook waits for the launch and raises a barrier give-up; info[4] receives
+ *   {workgroups of the launch, dynamic LDS bytes, accumulator height (0: small-row form), sizeof(svg_walk_stage)}.  SVG_ERR_RUNTIME
+ *   when the walk is unavailable. */
+typedef struct svg_walk_stage {
+  int32_t kind, bar;            /* 0 GEMM, 1 RED, 2 LN, 3 ATTN, 4 EMBED, 5 GEMMF; bar: device-wide barrier before the stage */
+  int32_t M, N, K, ld;          /* GEMM(F): X is M x K with row stride ld, W is N x K; RED / LN / EMBED: an M x N result */
+  int32_t ksplit, relu;         /* slabs to add up (GEMM: K / 128; LN: 0 = none); ReLU on the result (RED, GEMMF) */
+  const float *X, *W;
+  float* slab;
+  const float *bias, *res;
+  float* Y;
+  const float *g1, *b1, *g2, *b2;
+  float* Y2;
+  float eps;
+  int32_t Tq, Tk, B, heads, hd; /* ATTN (B, T also EMBED / GEMMF with perm or pe) */
+  int32_t q_ld, kv_ld, q_span, kv_span;
+  const float *qs, *ks, *vs, *mask, *kpad;
+  const float* pe;              /* EMBED / GEMMF: 64 rows (of N + d_txt floats / of ld_res floats) */
+  const int32_t* pe_row;
+  const float* text;
+  int32_t d_txt, T;
+  float scale;
+  int32_t ldy, ld_res, reuse_x, perm;   /* GEMMF */
+  float* Yln;
+} svg_walk_stage;
+int svg_xf_gemm_describe(int M, int N, int K, int* path);
+int svg_op_xf_gemm_ex(svg_ctx* ctx, const float* X, const float* W, const float* bias, const float* residual, float* Y, int M, int N, int K,
+                      int act_in, int* path, void* stream);
+int svg_op_xf_add_ln(svg_ctx* ctx, const float* x, const float* r, const float* gamma, const float* beta, float* y, int M, int d, float eps,
+                     void* stream);
+int svg_op_xf_embed_post(svg_ctx* ctx, const float* emb, const float* pe, const int32_t* pe_row, const float* text, int d_txt, float* y, int B,
+                         int T, int d, float scale, void* stream);
+int svg_op_xf_attention(svg_ctx* ctx, const float* q, int ldq, const float* k, const float* v, int ldk, const float* mask, const float* kpad,
+                        float* o, int Tq, int Tk, int B, int heads, int hd, void* stream);
+int svg_op_xf_attention_qkv(svg_ctx* ctx, const float* qkv, const int32_t* lens, float* o, int B, int T, int heads, int hd, void* stream);
+int svg_op_xf_embed_tokens(svg_ctx* ctx, const int32_t* ids, const float* tok, const float* pos, float* y, int rows, int T, int d, int vocab,
+                           void* stream);
+int svg_op_xf_embed_bert(svg_ctx* ctx, const int32_t* ids, const float* word, const float* pos, const float* type0, float* y, int rows, int T,
+                         int d, int vocab, void* stream);
+int svg_op_xf_mean_pool_norm(svg_ctx* ctx, const float* x, const int32_t* lens, float* out, int B, int T, int d, void* stream);
+int svg_op_xf_walk(svg_ctx* ctx, const svg_walk_stage* stages, int n_stages, int rows, int small, int* info, void* stream);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* When enabled (on = 1), every launch of each kernel family is bracketed by hipEvents on its stream;

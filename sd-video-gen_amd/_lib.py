@@ -83,6 +83,20 @@ class ConvMxDesc(C.Structure):
                 ("gn_part", _vp), ("q_out", _vp), ("s_out", _vp), ("w8_out", _vp), ("w8s_out", _vp)]
 
 
+class WalkStage(C.Structure):
+    """struct svg_walk_stage (include/svg_hip.h): one stage of the table of svg_op_xf_walk."""
+    _fields_ = [("kind", _i), ("bar", _i), ("M", _i), ("N", _i), ("K", _i), ("ld", _i), ("ksplit", _i), ("relu", _i),
+                ("X", _vp), ("W", _vp), ("slab", _vp), ("bias", _vp), ("res", _vp), ("Y", _vp),
+                ("g1", _vp), ("b1", _vp), ("g2", _vp), ("b2", _vp), ("Y2", _vp), ("eps", _f),
+                ("Tq", _i), ("Tk", _i), ("B", _i), ("heads", _i), ("hd", _i),
+                ("q_ld", _i), ("kv_ld", _i), ("q_span", _i), ("kv_span", _i),
+                ("qs", _vp), ("ks", _vp), ("vs", _vp), ("mask", _vp), ("kpad", _vp),
+                ("pe", _vp), ("pe_row", _vp), ("text", _vp), ("d_txt", _i), ("T", _i), ("scale", _f),
+                ("ldy", _i), ("ld_res", _i), ("reuse_x", _i), ("perm", _i), ("Yln", _vp)]
+
+
+WK_GEMM, WK_RED, WK_LN, WK_ATTN, WK_EMBED, WK_GEMMF = range(6)      # svg_walk_stage.kind
+
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/svg_hip.h
 SIGNATURES = {
     "svg_create": [_i, C.POINTER(_vp)],
@@ -175,6 +189,16 @@ SIGNATURES = {
     "svg_op_attention_ex": [_vp, C.POINTER(AttnDesc), C.POINTER(_i), _vp],
     "svg_op_vae_attention": [_vp, _vp, _vp, _i, _i64, _vp, _i, _i64, _vp, _i, _i64, _i, _i, _i, _vp],
     "svg_op_xf_gemm": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "svg_xf_gemm_describe": [_i, _i, _i, C.POINTER(_i)],
+    "svg_op_xf_gemm_ex": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_i), _vp],
+    "svg_op_xf_add_ln": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp],
+    "svg_op_xf_embed_post": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _f, _vp],
+    "svg_op_xf_attention": [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "svg_op_xf_attention_qkv": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "svg_op_xf_embed_tokens": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "svg_op_xf_embed_bert": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "svg_op_xf_mean_pool_norm": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "svg_op_xf_walk": [_vp, C.POINTER(WalkStage), _i, _i, _i, C.POINTER(_i), _vp],
     "svg_prof_enable": [_vp, _i],
     "svg_prof_reset": [_vp],
     "svg_prof_report": [_vp, C.c_char_p, _i],
@@ -259,6 +283,15 @@ def load():
 def env_refresh():
     """the library caches its $SVG_* knobs per name: call after changing one in-process (svg_env_refresh)"""
     load().svg_env_refresh()
+
+
+def xf_gemm_describe(M, N, K):
+    """(form, mt, ksplit) of the launch xf_gemm makes for an (M, N, K) product (svg_xf_gemm_describe; host only, no context, no GPU)"""
+    lib = load()
+    p = (_i * 3)()
+    if lib.svg_xf_gemm_describe(int(M), int(N), int(K), p) != 0:
+        raise ValueError("svg_xf_gemm_describe: " + lib.svg_last_error(None).decode())
+    return tuple(p)
 
 
 def lms_coefs(num_steps, i):

@@ -287,8 +287,14 @@ void xformer_init_device();
 // latent Transformer (f32, f32-input MFMA)
 // ------------------------------------------------------------------------------------------------
 // act_in on X: 0 none, 1 ReLU, 2 quick-GELU, 3 exact GELU (erf); Y = act_in(X) W^T + bias (+ residual[M][N]); M <= 336
+// what one xf_gemm() launches (xf_plan.cpp: plain host code): form 1 = the 16-column form (xf_gemm_kernel<mt>), 2 = the column-block
+// form (xf_gemm2_kernel<mt>); mt: the instantiated accumulator height (1, 2, 3, 4, 6, 8, 11, 16, 21 tiles of 16 rows); ksplit: the
+// split-K factor (> 1: ksplit slabs of M x N floats from the arena and a finishing launch).  The grid is (ceil(N / 16), ksplit) in
+// form 1 and (ceil(N / 64), ksplit) in form 2.
+struct XfGemmPath { int form, mt, ksplit; };
+XfGemmPath xf_gemm_describe(int M, int N, int K);
 void xf_gemm(svg_ctx* ctx, const float* X, const float* W, const float* bias, float* Y, int M, int N,
-             int K, int act_in, hipStream_t s, const float* residual = nullptr);
+             int K, int act_in, hipStream_t s, const float* residual = nullptr, XfGemmPath* ran = nullptr);
 // CLIP text tower pieces (f32): token + position embedding lookup; causal self-attention on packed [q|k|v] rows
 void xf_embed_tokens(const int32_t* ids, const float* tok, const float* pos, float* y, int rows, int T, int d, int vocab, hipStream_t s);
 void xf_attention_causal(const float* qkv, float* o, int B, int T, int heads, int hd, hipStream_t s);

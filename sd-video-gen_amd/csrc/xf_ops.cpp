@@ -1,0 +1,149 @@
+// C ABI, operator level: the forward kernels of the latent Transformer / CLIP text tower / MiniLM encoder one by one, and one
+// layer-walking launch over a caller's stage table (test hooks: each is its launcher and nothing else).  Every hook checks what its
+// launcher silently assumes of its arguments and refuses (svg_fail) instead of launching.
+#include "models.h"
+#include "xf_walk.h"
+#include "../../include/svg_hip.h"
+#include <vector>
+
+extern "C" {
+
+int svg_xf_gemm_describe(int M, int N, int K, int* path) {
+  try {
+    SVG_CHECK(path && M >= 1 && N >= 1 && K >= 1, "svg_xf_gemm_describe: bad argument");
+    const XfGemmPath p = xf_gemm_describe(M, N, K);
+    path[0] = p.form; path[1] = p.mt; path[2] = p.ksplit;
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(nullptr, e); }
+}
+
+int svg_op_xf_gemm_ex(svg_ctx* ctx, const float* X, const float* W, const float* bias, const float* residual, float* Y, int M, int N, int K,
+                      int act_in, int* path, void* stream) {
+  try {
+    SVG_CHECK(ctx && X && W && Y, "svg_op_xf_gemm_ex: null argument");
+    SVG_CHECK(M >= 1 && N >= 1 && K >= 1, "svg_op_xf_gemm_ex: empty problem %d x %d x %d", M, N, K);
+    SVG_CHECK(act_in >= 0 && act_in <= 3, "svg_op_xf_gemm_ex: act_in %d (0 none, 1 ReLU, 2 quick-GELU, 3 GELU)", act_in);
+    XfGemmPath ran{0, 0, 0};
+    run_planned(ctx, [&]() { xf_gemm(ctx, X, W, bias, Y, M, N, K, act_in, (hipStream_t)stream, residual, &ran); });
+    if (path) { path[0] = ran.form; path[1] = ran.mt; path[2] = ran.ksplit; }
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_add_ln(svg_ctx* ctx, const float* x, const float* r, const float* gamma, const float* beta, float* y, int M, int d, float eps,
+                     void* stream) {
+  try {
+    SVG_CHECK(ctx && x && gamma && beta && y, "svg_op_xf_add_ln: null argument");
+    SVG_CHECK(M >= 1 && d >= 1, "svg_op_xf_add_ln: empty problem %d x %d", M, d);
+    xf_add_ln(x, r, gamma, beta, y, M, d, eps, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_embed_post(svg_ctx* ctx, const float* emb, const float* pe, const int32_t* pe_row, const float* text, int d_txt, float* y, int B,
+                         int T, int d, float scale, void* stream) {
+  try {
+    SVG_CHECK(ctx && emb && pe && y, "svg_op_xf_embed_post: null argument");
+    SVG_CHECK(B >= 1 && T >= 1 && d >= 1 && d_txt >= 0 && d_txt < d, "svg_op_xf_embed_post: B %d T %d d %d d_txt %d", B, T, d, d_txt);
+    SVG_CHECK(d_txt == 0 || text, "svg_op_xf_embed_post: %d text channels without a text buffer", d_txt);
+    SVG_CHECK(pe_row || B <= 64, "svg_op_xf_embed_post: batch row %d has no row in the 64-row positional table (pass pe_row)", B - 1);
+    xf_embed_post(emb, pe, pe_row, text, d_txt, y, B, T, d, scale, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_attention(svg_ctx* ctx, const float* q, int ldq, const float* k, const float* v, int ldk, const float* mask, const float* kpad,
+                        float* o, int Tq, int Tk, int B, int heads, int hd, void* stream) {
+  try {
+    SVG_CHECK(ctx && q && k && v && o, "svg_op_xf_attention: null argument");
+    SVG_CHECK(Tq >= 1 && Tk >= 1 && B >= 1 && heads >= 1 && hd >= 1, "svg_op_xf_attention: Tq %d Tk %d B %d heads %d hd %d", Tq, Tk, B, heads, hd);
+    SVG_CHECK(ldq >= heads * hd && ldk >= heads * hd, "svg_op_xf_attention: row strides %d / %d below heads * hd = %d", ldq, ldk, heads * hd);
+    xf_attention(q, ldq, k, v, ldk, mask, o, Tq, Tk, B, heads, hd, (hipStream_t)stream, kpad);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_attention_qkv(svg_ctx* ctx, const float* qkv, const int32_t* lens, float* o, int B, int T, int heads, int hd, void* stream) {
+  try {
+    SVG_CHECK(ctx && qkv && o, "svg_op_xf_attention_qkv: null argument");
+    SVG_CHECK(B >= 1 && heads >= 1, "svg_op_xf_attention_qkv: B %d heads %d", B, heads);
+    if (lens) xf_attention_padded(qkv, lens, o, B, T, heads, hd, (hipStream_t)stream);
+    else xf_attention_causal(qkv, o, B, T, heads, hd, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_embed_tokens(svg_ctx* ctx, const int32_t* ids, const float* tok, const float* pos, float* y, int rows, int T, int d, int vocab,
+                           void* stream) {
+  try {
+    SVG_CHECK(ctx && ids && tok && pos && y, "svg_op_xf_embed_tokens: null argument");
+    SVG_CHECK(rows >= 1 && T >= 1 && vocab >= 1 && d >= 4 && d % 4 == 0, "svg_op_xf_embed_tokens: rows %d T %d vocab %d d %d (a multiple of 4: 16-byte loads)",
+              rows, T, vocab, d);
+    xf_embed_tokens(ids, tok, pos, y, rows, T, d, vocab, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_embed_bert(svg_ctx* ctx, const int32_t* ids, const float* word, const float* pos, const float* type0, float* y, int rows, int T,
+                         int d, int vocab, void* stream) {
+  try {
+    SVG_CHECK(ctx && ids && word && pos && type0 && y, "svg_op_xf_embed_bert: null argument");
+    SVG_CHECK(rows >= 1 && T >= 1 && vocab >= 1 && d >= 4 && d % 4 == 0, "svg_op_xf_embed_bert: rows %d T %d vocab %d d %d (a multiple of 4: 16-byte loads)",
+              rows, T, vocab, d);
+    xf_embed_bert(ids, word, pos, type0, y, rows, T, d, vocab, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_mean_pool_norm(svg_ctx* ctx, const float* x, const int32_t* lens, float* out, int B, int T, int d, void* stream) {
+  try {
+    SVG_CHECK(ctx && x && lens && out, "svg_op_xf_mean_pool_norm: null argument");
+    SVG_CHECK(B >= 1 && T >= 1 && d >= 1, "svg_op_xf_mean_pool_norm: B %d T %d d %d", B, T, d);
+    xf_mean_pool_norm(x, lens, out, B, T, d, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_walk(svg_ctx* ctx, const svg_walk_stage* stages, int n_stages, int rows, int small, int* info, void* stream) {
+  try {
+    hipStream_t s = (hipStream_t)stream;
+    SVG_CHECK(ctx && stages, "svg_op_xf_walk: null argument");
+    SVG_CHECK(n_stages >= 1 && n_stages <= kWalkMaxOps, "svg_op_xf_walk: %d stages (at most %d)", n_stages, kWalkMaxOps);
+    if (small) rows = kWalkSmallRows;
+    SVG_CHECK(rows >= 1 && rows <= kWalkMaxRows, "svg_op_xf_walk: %d rows (at most %d)", rows, kWalkMaxRows);
+    const int grid = xf_walk_grid();
+    if (!xf_walk_enabled(s) || grid < 8) throw SvgHipError("svg_op_xf_walk: the layer-walking launch is unavailable on this device / stream");
+    std::vector<WalkOp> ops(n_stages);
+    int Tq = 1, Tk = 1, hd = 4;                            // the largest attention job of the table sizes the LDS
+    for (int i = 0; i < n_stages; ++i) {
+      const svg_walk_stage& g = stages[i];
+      WalkOp op{};
+      op.kind = g.kind; op.bar = g.bar; op.M = g.M; op.N = g.N; op.K = g.K; op.ld = g.ld; op.ksplit = g.ksplit; op.relu = g.relu;
+      op.X = g.X; op.W = g.W; op.slab = g.slab; op.bias = g.bias; op.res = g.res; op.Y = g.Y;
+      op.g1 = g.g1; op.b1 = g.b1; op.g2 = g.g2; op.b2 = g.b2; op.Y2 = g.Y2; op.eps = g.eps;
+      op.Tq = g.Tq; op.Tk = g.Tk; op.B = g.B; op.heads = g.heads; op.hd = g.hd;
+      op.q_ld = g.q_ld; op.kv_ld = g.kv_ld; op.q_span = g.q_span; op.kv_span = g.kv_span;
+      op.qs = g.qs; op.ks = g.ks; op.vs = g.vs; op.mask = g.mask; op.kpad = g.kpad;
+      op.pe = g.pe; op.pe_row = g.pe_row; op.text = g.text; op.d_txt = g.d_txt; op.T = g.T; op.scale = g.scale;
+      op.ldy = g.ldy; op.ld_res = g.ld_res; op.reuse_x = g.reuse_x; op.perm = g.perm; op.Yln = g.Yln;
+      ops[i] = op;
+      if (g.kind == WK_ATTN) {
+        SVG_CHECK(g.hd >= 4 && g.hd % 4 == 0 && g.Tq >= 1 && g.Tq <= 32 && g.Tk >= 1 && g.Tk <= 32 && g.heads >= 1 && g.B >= 1,
+                  "svg_op_xf_walk: stage %d: attention Tq %d Tk %d (at most 32) head dim %d (a multiple of 4)", i, g.Tq, g.Tk, g.hd);
+        SVG_CHECK(g.q_ld >= g.heads * g.hd && g.kv_ld >= g.heads * g.hd, "svg_op_xf_walk: stage %d: row strides below heads * hd", i);
+        Tq = std::max(Tq, g.Tq); Tk = std::max(Tk, g.Tk); hd = std::max(hd, g.hd);
+      }
+      if (g.kind == WK_EMBED || (g.kind == WK_GEMMF && g.pe))
+        SVG_CHECK(g.pe_row || g.B <= 64, "svg_op_xf_walk: stage %d: batch row %d has no row in the 64-row positional table (pass pe_row)", i, g.B - 1);
+    }
+    const int64_t lds = small ? xf_walk_small_lds_bytes(std::max(Tq, Tk), hd) : xf_walk_lds_bytes(rows, Tq, Tk, hd);
+    if (small) xf_walk_small_launch(ctx, ops.data(), n_stages, lds, s);
+    else xf_walk_launch(ctx, ops.data(), n_stages, rows, lds, s);
+    if (info) { info[0] = grid; info[1] = (int)lds; info[2] = small ? 0 : xf_walk_mt(rows); info[3] = (int)sizeof(svg_walk_stage); }
+    HIP_OK(hipStreamSynchronize(s));                       // a give-up of THIS launch is raised by this call
+    xf_walk_check(ctx);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+}  // extern "C"

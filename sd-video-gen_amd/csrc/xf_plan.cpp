@@ -279,3 +279,27 @@ XfPlan xf_plan(const XfModel& m, const XfShape& sh, const XfDevice& dev, const X
   p.form = XF_WALK_SMALL; p.rows = kWalkSmallRows; p.lds_bytes = lds_small; p.n_stages = ns;
   return p;
 }
+
+// ---- what xf_gemm launches (xformer.hip takes its decision from here) ------------------------------------------------------------------
+// Two forms (same-box kbench, profiles/README.md): up to 47 rows the 16-column form (every wave streams its own K slice, X straight from
+// L2: 1.6-3.1 TB/s at 6 rows) is ahead; from 48 rows on X re-reads bound it and the column-block form (X shared through LDS) wins: 71 vs
+// 53 TFLOP/s at 168 x 6144 x 2048.  The column-block form needs one whole 32-wide K step (its masked W loads read row offset 0).
+XfGemmPath xf_gemm_describe(int M, int N, int K) {
+  XfGemmPath p;
+  const int mt = cdiv(M, 16);
+  p.mt = mt <= 4 ? mt : (mt <= 6 ? 6 : (mt <= 8 ? 8 : (mt <= 11 ? 11 : (mt <= 16 ? 16 : 21))));
+  const int steps = cdiv(K, 32);
+  p.ksplit = 1;
+  if (M >= 48 && K >= 32) {
+    p.form = 2;
+    const int nb = cdiv(N, 64);
+    // enough workgroups for two per CU while each keeps >= 8 steps (two rounds of its 4-deep pipeline)
+    while (nb * p.ksplit < 512 && steps / (p.ksplit * 2) >= 8 && p.ksplit < 16) p.ksplit *= 2;
+  } else {
+    p.form = 1;
+    const int nb = cdiv(N, 16);
+    // K split: enough workgroups to put >= 2 on every CU while every wave (of 8) keeps >= 2 steps of 32 (its load pipeline)
+    while (nb * p.ksplit < 512 && steps / (8 * p.ksplit * 2) >= 2 && p.ksplit < 8) p.ksplit *= 2;
+  }
+  return p;
+}

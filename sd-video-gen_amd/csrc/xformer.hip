@@ -443,72 +443,37 @@ void xformer_init_device() {
   xf2_attr<1>(); xf2_attr<2>(); xf2_attr<3>(); xf2_attr<4>(); xf2_attr<6>(); xf2_attr<8>(); xf2_attr<11>(); xf2_attr<16>(); xf2_attr<21>();
 }
 
-// column-block form (X shared through LDS): grid (N / 64, ksplit)
-static void xf_gemm_v2(svg_ctx* ctx, const float* X, const float* W, const float* bias, float* Y, int M, int N, int K, int act_in,
-                       hipStream_t s, const float* residual) {
-  SVG_CHECK(K >= 32 && K % 4 == 0, "xf_gemm (column-block form): K = %d must be a multiple of 4 and at least one 32-wide step (masked W loads read row offset 0)", K);
-  const int nb = cdiv(N, 64);
-  const int steps = cdiv(K, 32);
-  // enough workgroups for two per CU while each keeps >= 8 steps (two rounds of its 4-deep pipeline)
-  int ksplit = 1;
-  while (nb * ksplit < 512 && steps / (ksplit * 2) >= 8 && ksplit < 16) ksplit *= 2;
-  float* slabs = nullptr;
-  if (ksplit > 1) { ctx->arena.push(); slabs = ctx->arena.get<float>((int64_t)ksplit * M * N); ctx->arena.pop(); }
-  if (!SVG_LAUNCHING(ctx)) return;
-  char tag[64];
-  snprintf(tag, sizeof(tag), "v2_M%d_N%d_K%d_ks%d", M, N, K, ksplit);
-  ProfScope ps(ctx, PK_XF_GEMM, s, 2.0 * M * (double)N * K, 4.0 * ((double)N * K + (double)M * K + (double)M * N), tag);
-  dim3 grid(nb, ksplit);
-  float* dst = ksplit > 1 ? slabs : Y;
-  const int mt = cdiv(M, 16);
-  if (mt <= 1) xf2_launch<1>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else if (mt <= 2) xf2_launch<2>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else if (mt <= 3) xf2_launch<3>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else if (mt <= 4) xf2_launch<4>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else if (mt <= 6) xf2_launch<6>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else if (mt <= 8) xf2_launch<8>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else if (mt <= 11) xf2_launch<11>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else if (mt <= 16) xf2_launch<16>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else xf2_launch<21>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  check_launch("xf_gemm2");
-  if (ksplit > 1) {
-    const int64_t MN = (int64_t)M * N;
-    hipLaunchKernelGGL(xf_splitk_finish_kernel, dim3((unsigned)std::min<int64_t>((MN / 4 + 255) / 256, 1024)), dim3(256), 0, s, slabs, bias, residual,
-                       Y, MN, N, ksplit);
-    check_launch("xf_splitk_finish");
-  }
-}
-
+// The form, the accumulator height and the K split come from xf_gemm_describe (xf_plan.cpp), the one place where they are decided.
+// form 1: grid (N / 16, ksplit); form 2 (X shared through LDS): grid (N / 64, ksplit).  ksplit > 1: partial sums to slabs, then the finish.
 void xf_gemm(svg_ctx* ctx, const float* X, const float* W, const float* bias, float* Y, int M, int N, int K, int act_in,
-             hipStream_t s, const float* residual) {
+             hipStream_t s, const float* residual, XfGemmPath* ran) {
   SVG_CHECK(K % 8 == 0 && N % 4 == 0, "xf_gemm: K=%d must be a multiple of 8 and N=%d of 4", K, N);
   SVG_CHECK(M >= 1 && M <= 16 * XF_MAXMT, "xf_gemm: M=%d must be in 1..%d", M, 16 * XF_MAXMT);
-  // Two forms (same-box kbench, profiles/README.md): up to 47 rows the 16-column form below (every wave streams its own K slice,
-  // X straight from L2: 1.6-3.1 TB/s at 6 rows) is ahead; from 48 rows on X re-reads bound it and the column-block form (X
-  // shared through LDS) wins: 71 vs 53 TFLOP/s at 168 x 6144 x 2048.
-  if (M >= 48 && K >= 32) { xf_gemm_v2(ctx, X, W, bias, Y, M, N, K, act_in, s, residual); return; }
-  const int nb = cdiv(N, 16);
-  // K split: enough workgroups to put >= 2 on every CU while every wave keeps >= 2 steps of 32 (its load pipeline)
-  const int steps = cdiv(K, 32);
-  int ksplit = 1;
-  while (nb * ksplit < 512 && steps / (XF_WAVES * ksplit * 2) >= 2 && ksplit < 8) ksplit *= 2;
+  const XfGemmPath p = xf_gemm_describe(M, N, K);
+  if (ran) *ran = p;
+  const bool v2 = p.form == 2;
+  if (v2) SVG_CHECK(K >= 32 && K % 4 == 0, "xf_gemm (column-block form): K = %d must be a multiple of 4 and at least one 32-wide step (masked W loads read row offset 0)", K);
+  const int nb = cdiv(N, v2 ? 64 : 16);
+  const int ksplit = p.ksplit;
   float* slabs = nullptr;
   if (ksplit > 1) { ctx->arena.push(); slabs = ctx->arena.get<float>((int64_t)ksplit * M * N); ctx->arena.pop(); }   // stream order protects it
   if (!SVG_LAUNCHING(ctx)) return;
-  ProfScope ps(ctx, PK_XF_GEMM, s, 2.0 * M * (double)N * K, 4.0 * ((double)N * K + (double)M * K + (double)M * N));
+  char tag[64];
+  snprintf(tag, sizeof(tag), "v2_M%d_N%d_K%d_ks%d", M, N, K, ksplit);
+  ProfScope ps(ctx, PK_XF_GEMM, s, 2.0 * M * (double)N * K, 4.0 * ((double)N * K + (double)M * K + (double)M * N), v2 ? tag : nullptr);
   dim3 grid(nb, ksplit);
   float* dst = ksplit > 1 ? slabs : Y;
-  const int mt = cdiv(M, 16);
-  if (mt <= 1) xf_launch<1>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else if (mt <= 2) xf_launch<2>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else if (mt <= 3) xf_launch<3>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else if (mt <= 4) xf_launch<4>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else if (mt <= 6) xf_launch<6>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else if (mt <= 8) xf_launch<8>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else if (mt <= 11) xf_launch<11>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else if (mt <= 16) xf_launch<16>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  else xf_launch<21>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);
-  check_launch("xf_gemm");
+  switch (p.mt) {
+#define XF_MT(MT)                                                                              \
+  case MT:                                                                                     \
+    if (v2) xf2_launch<MT>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);       \
+    else xf_launch<MT>(grid, s, X, W, bias, residual, dst, M, N, K, act_in, ksplit);           \
+    break;
+    XF_MT(1) XF_MT(2) XF_MT(3) XF_MT(4) XF_MT(6) XF_MT(8) XF_MT(11) XF_MT(16) XF_MT(21)
+#undef XF_MT
+    default: SVG_CHECK(false, "xf_gemm: no instantiation of height %d", p.mt);
+  }
+  check_launch(v2 ? "xf_gemm2" : "xf_gemm");
   if (ksplit > 1) {
     const int64_t MN = (int64_t)M * N;
     hipLaunchKernelGGL(xf_splitk_finish_kernel, dim3((unsigned)std::min<int64_t>((MN / 4 + 255) / 256, 1024)), dim3(256), 0, s, slabs, bias, residual,
