@@ -607,6 +607,40 @@ int svg_op_softmax_rows(svg_ctx* ctx, const float* s_in, uint16_t* p_out, int64_
 int svg_op_fold_ln(svg_ctx* ctx, float* w, const float* bias_in, const float* gamma, const float* beta, float* bias_out, int N, int K,
                    void* stream);
 int svg_op_rowsum(svg_ctx* ctx, const uint16_t* w, float* out, int N, int K, void* stream);
+/* The element-wise and layout kernels at the VAE / UNet boundary (csrc/eltwise.hip) and add_noise of the sampling loop, one by one
+ * (test hooks: each checks its arguments and calls the launcher the models call, nothing is added).  Device buffers.
+ * svg_op_img_to_act: img (N,sh,sw,3) u8 -> out (N,H,W,8) 16-bit = 2 (p / 255 - 0.5), channels 3..7 zero; (sh,sw) != (H,W): nearest source
+ *   pixel floor(dst * in / out) in f32, as svg_resize_nearest_u8; out 16-byte aligned.
+ * svg_op_act_to_img: x (N,h,w,ldc) f32, channels 0..2 -> img (N,oh,ow,3) u8 = round-half-even(clamp(x / 2 + 0.5, 0, 1) 255), nearest
+ *   resized, and / or float_out (N,3,h,w) f32 = the same channels untouched; either may be NULL, not both.
+ * svg_op_nchw_to_act: x (N,C,h,w) f32 -> out (N,h,w,Cpad) 16-bit = x * scale, channels C..Cpad-1 zero.  svg_op_nchw_to_actf32: the same
+ *   to (N,h,w,C) f32.  svg_op_actf32_pad_h16: x (P,C) f32 -> out (P,Cpad) 16-bit, zero padded.
+ * svg_op_actf32_to_nchw: x (N,h,w,ld) f32, ld >= C -> out (N,C,h,w) f32.
+ * svg_op_pixel_linear_f32: y[p][o] = b[o] (0 when NULL) + sum_i w[o][i] x[p][i] over P pixels; row strides ldx, ldy; Cin <= 8.
+ * svg_op_vae_sample: mom (N,h,w,ldm) f32 = [mean(4) | logvar(4) | ...] -> z (N,4,h,w) = 0.18215 (mean + exp(0.5 clamp(logvar, -30, 20)) eps),
+ *   eps (N,4,h,w) or NULL (the mode: 0.18215 mean); mom_nchw (N,8,h,w, or NULL) receives the moments as they came (logvar not clamped).
+ * svg_op_concat_channels: out (P,Ca+Cb) = [a (P,Ca) | b (P,Cb)] 16-bit; Ca, Cb multiples of 8, pointers 16-byte aligned.
+ * svg_op_f32_to_h16 / svg_op_h16_to_f32: n elements, round to nearest even / exact.  svg_op_f32_to_h16_x8: the same conversion eight
+ *   elements per thread; n % 8 == 0, x 32-byte and y 16-byte aligned, anything else is an error.
+ * svg_op_timestep_embed: t f32[N] -> out (N,dim) 16-bit = [cos | sin](t exp(-ln(10000) i / (dim / 2))), i < dim / 2; dim even.
+ * svg_op_add_noise: out = sa x0 + s1a noise over n floats; out may be x0. */
+int svg_op_img_to_act(svg_ctx* ctx, const uint8_t* img, uint16_t* out, int N, int sh, int sw, int H, int W, void* stream);
+int svg_op_act_to_img(svg_ctx* ctx, const float* x, int ldc, uint8_t* img, float* float_out, int N, int h, int w, int oh, int ow,
+                      void* stream);
+int svg_op_nchw_to_act(svg_ctx* ctx, const float* x, uint16_t* out, int N, int C, int h, int w, int Cpad, float scale, void* stream);
+int svg_op_nchw_to_actf32(svg_ctx* ctx, const float* x, float* out, int N, int C, int h, int w, float scale, void* stream);
+int svg_op_actf32_pad_h16(svg_ctx* ctx, const float* x, int C, uint16_t* out, int Cpad, int64_t P, void* stream);
+int svg_op_actf32_to_nchw(svg_ctx* ctx, const float* x, int ld, float* out, int N, int C, int h, int w, void* stream);
+int svg_op_pixel_linear_f32(svg_ctx* ctx, const float* x, int ldx, const float* w, const float* b, float* y, int ldy, int64_t P, int Cin,
+                            int Cout, void* stream);
+int svg_op_vae_sample(svg_ctx* ctx, const float* mom, int ldm, const float* eps, float* z, float* mom_nchw, int N, int h, int w,
+                      void* stream);
+int svg_op_concat_channels(svg_ctx* ctx, const uint16_t* a, int Ca, const uint16_t* b, int Cb, uint16_t* out, int64_t P, void* stream);
+int svg_op_f32_to_h16(svg_ctx* ctx, const float* x, uint16_t* y, int64_t n, void* stream);
+int svg_op_f32_to_h16_x8(svg_ctx* ctx, const float* x, uint16_t* y, int64_t n, void* stream);
+int svg_op_h16_to_f32(svg_ctx* ctx, const uint16_t* x, float* y, int64_t n, void* stream);
+int svg_op_timestep_embed(svg_ctx* ctx, const float* t, uint16_t* out, int N, int dim, void* stream);
+int svg_op_add_noise(svg_ctx* ctx, const float* x0, const float* noise, float* out, int64_t n, float sa, float s1a, void* stream);
 /* LayerNorm over the last dim of (M,C) bf16. */
 int svg_op_layernorm(svg_ctx* ctx, const uint16_t* x, const float* gamma, const float* beta,
                      uint16_t* out, int M, int C, float eps, void* stream);
@@ -698,6 +732,14 @@ int svg_op_ln_stats_f16(svg_ctx* ctx, const uint16_t* x, float* rs, float* rm, i
 int svg_op_softmax_rows_f16(svg_ctx* ctx, const float* s_in, uint16_t* p_out, int64_t rows, int cols, int ld_in, int ld_out, float scale,
                             void* stream);
 int svg_op_rowsum_f16(svg_ctx* ctx, const uint16_t* w, float* out, int N, int K, void* stream);
+int svg_op_img_to_act_f16(svg_ctx* ctx, const uint8_t* img, uint16_t* out, int N, int sh, int sw, int H, int W, void* stream);
+int svg_op_nchw_to_act_f16(svg_ctx* ctx, const float* x, uint16_t* out, int N, int C, int h, int w, int Cpad, float scale, void* stream);
+int svg_op_actf32_pad_h16_f16(svg_ctx* ctx, const float* x, int C, uint16_t* out, int Cpad, int64_t P, void* stream);
+int svg_op_concat_channels_f16(svg_ctx* ctx, const uint16_t* a, int Ca, const uint16_t* b, int Cb, uint16_t* out, int64_t P, void* stream);
+int svg_op_f32_to_h16_f16(svg_ctx* ctx, const float* x, uint16_t* y, int64_t n, void* stream);
+int svg_op_f32_to_h16_x8_f16(svg_ctx* ctx, const float* x, uint16_t* y, int64_t n, void* stream);
+int svg_op_h16_to_f32_f16(svg_ctx* ctx, const uint16_t* x, float* y, int64_t n, void* stream);
+int svg_op_timestep_embed_f16(svg_ctx* ctx, const float* t, uint16_t* out, int N, int dim, void* stream);
 /* f32 skinny GEMM of the latent Transformer: Y[M,N] = X[M,K] * W[N,K]^T + bias (relu_in: X:=max(X,0)). */
 int svg_op_xf_gemm(svg_ctx* ctx, const float* X, const float* W, const float* bias, float* Y,
                    int M, int N, int K, int relu_in, void* stream);

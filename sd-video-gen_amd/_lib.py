@@ -184,6 +184,20 @@ SIGNATURES = {
     "svg_op_softmax_rows": [_vp, _vp, _vp, _i64, _i, _i, _i, _f, _vp],
     "svg_op_fold_ln": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "svg_op_rowsum": [_vp, _vp, _vp, _i, _i, _vp],
+    "svg_op_img_to_act": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "svg_op_act_to_img": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "svg_op_nchw_to_act": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
+    "svg_op_nchw_to_actf32": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
+    "svg_op_actf32_pad_h16": [_vp, _vp, _i, _vp, _i, _i64, _vp],
+    "svg_op_actf32_to_nchw": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp],
+    "svg_op_pixel_linear_f32": [_vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _vp],
+    "svg_op_vae_sample": [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "svg_op_concat_channels": [_vp, _vp, _i, _vp, _i, _vp, _i64, _vp],
+    "svg_op_f32_to_h16": [_vp, _vp, _vp, _i64, _vp],
+    "svg_op_f32_to_h16_x8": [_vp, _vp, _vp, _i64, _vp],
+    "svg_op_h16_to_f32": [_vp, _vp, _vp, _i64, _vp],
+    "svg_op_timestep_embed": [_vp, _vp, _vp, _i, _i, _vp],
+    "svg_op_add_noise": [_vp, _vp, _vp, _vp, _i64, _f, _f, _vp],
     "svg_op_layernorm": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp],
     "svg_op_attention": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _f, _vp],
     "svg_op_attention_ex": [_vp, C.POINTER(AttnDesc), C.POINTER(_i), _vp],
@@ -213,7 +227,8 @@ SIGNATURES = {
 # fp16-storage twins of the 16-bit operator hooks (svg_op_<name>_f16: same arguments)
 for _n in ("gemm", "gemm_ex", "gemm_plan", "conv3x3", "conv3x3_gn", "conv3x3_mx", "conv3x3_mx_ex", "gemm_fp8_ex", "quant_act_mx", "gemm_lnstats", "gemm_cat", "ff_fused", "xattn_fused", "quant_mx", "gemm_fp8", "groupnorm", "layernorm",
            "attention", "attention_ex", "vae_attention", "conv3x3_f32s", "groupnorm_f32", "groupnorm_ex", "groupnorm_mx", "gn_fold_weights", "ln_stats",
-           "softmax_rows", "rowsum"):
+           "softmax_rows", "rowsum", "img_to_act", "nchw_to_act", "actf32_pad_h16", "concat_channels", "f32_to_h16", "f32_to_h16_x8", "h16_to_f32",
+           "timestep_embed"):
     SIGNATURES["svg_op_%s_f16" % _n] = SIGNATURES["svg_op_" + _n]
 SIGNATURES["svg_model_dtype"] = [_vp, _i]
 _RESTYPES = {"svg_destroy": None, "svg_env_refresh": None, "svg_model_dtype": C.c_char_p, "svg_last_error": C.c_char_p, "svg_version": C.c_char_p,

@@ -181,9 +181,6 @@ __global__ void f32_to_h16_x8_kernel(const float* __restrict__ x, h16* __restric
 __global__ void h16_to_f32_kernel(const h16* __restrict__ x, float* __restrict__ y, int64_t n) {
   GRID_STRIDE(i, n) y[i] = (float)x[i];
 }
-__global__ void silu_kernel(const h16* __restrict__ x, h16* __restrict__ y, int64_t n) {
-  GRID_STRIDE(i, n) { float f = (float)x[i]; y[i] = (h16)(f / (1.f + __expf(-f))); }
-}
 
 // diffusers get_timestep_embedding(flip_sin_to_cos=True, downscale_freq_shift=0): [cos | sin]
 __global__ void timestep_embed_kernel(const float* __restrict__ t, h16* __restrict__ out, int N, int dim) {
@@ -280,10 +277,6 @@ void f32_to_h16_x8(const float* x, h16* y, int64_t n, hipStream_t s) {
 void h16_to_f32(const h16* x, float* y, int64_t n, hipStream_t s) {
   hipLaunchKernelGGL(h16_to_f32_kernel, grid_for(n), dim3(256), 0, s, x, y, n);
   check_launch("h16_to_f32");
-}
-void silu_h16(const h16* x, h16* y, int64_t n, hipStream_t s) {
-  hipLaunchKernelGGL(silu_kernel, grid_for(n), dim3(256), 0, s, x, y, n);
-  check_launch("silu");
 }
 void timestep_embed(const float* t, h16* out, int N, int dim, hipStream_t s) {
   hipLaunchKernelGGL(timestep_embed_kernel, grid_for((int64_t)N * dim / 2), dim3(256), 0, s, t, out, N, dim);

@@ -275,7 +275,6 @@ void h16_to_f32(const h16* x, float* y, int64_t n, hipStream_t s);
 void f32_to_h16_x8(const float* x, h16* y, int64_t n, hipStream_t s);
 // timestep sinusoid (flip_sin_to_cos, shift 0): t f32[N] -> bf16 (N,dim) = [cos | sin]
 void timestep_embed(const float* t, h16* out, int N, int dim, hipStream_t s);
-void silu_h16(const h16* x, h16* y, int64_t n, hipStream_t s);
 void fill_f32(float* p, int64_t n, float v, hipStream_t s);
 
 }  // namespace SDNS

@@ -542,7 +542,99 @@ int svg_op_fold_ln(svg_ctx* ctx, float* w, const float* bias_in, const float* ga
   fold_ln_weights(w, bias_in, gamma, beta, bias_out, N, K, (hipStream_t)stream);
   API_END(ctx)
 }
+// the f32 / u8 kernels of eltwise.hip and add_noise of sampler.hip on caller buffers (one export each).  Test hooks.
+int svg_op_act_to_img(svg_ctx* ctx, const float* x, int ldc, uint8_t* img, float* float_out, int N, int h, int w, int oh, int ow, void* stream) {
+  API_BEGIN
+  SVG_CHECK(x && (img || float_out) && ldc >= 3 && N > 0 && h > 0 && w > 0 && oh > 0 && ow > 0, "act_to_img op: bad arguments (ldc %d N %d %dx%d -> %dx%d)",
+            ldc, N, h, w, oh, ow);
+  act_to_img(x, ldc, img, float_out, N, h, w, oh, ow, (hipStream_t)stream);
+  API_END(ctx)
+}
+int svg_op_nchw_to_actf32(svg_ctx* ctx, const float* x, float* out, int N, int C, int h, int w, float scale, void* stream) {
+  API_BEGIN
+  SVG_CHECK(x && out && N > 0 && C > 0 && h > 0 && w > 0, "nchw_to_actf32 op: bad arguments (N %d C %d %dx%d)", N, C, h, w);
+  nchw_to_actf32(x, out, N, C, h, w, scale, (hipStream_t)stream);
+  API_END(ctx)
+}
+int svg_op_actf32_to_nchw(svg_ctx* ctx, const float* x, int ld, float* out, int N, int C, int h, int w, void* stream) {
+  API_BEGIN
+  SVG_CHECK(x && out && N > 0 && C > 0 && ld >= C && h > 0 && w > 0, "actf32_to_nchw op: bad arguments (N %d C %d ld %d %dx%d)", N, C, ld, h, w);
+  actf32_to_nchw(x, ld, out, N, C, h, w, (hipStream_t)stream);
+  API_END(ctx)
+}
+int svg_op_pixel_linear_f32(svg_ctx* ctx, const float* x, int ldx, const float* w, const float* b, float* y, int ldy, int64_t P, int Cin, int Cout,
+                            void* stream) {
+  API_BEGIN
+  SVG_CHECK(x && w && y && P > 0 && Cin > 0 && Cout > 0 && ldx >= Cin && ldy >= Cout, "pixel_linear_f32 op: bad arguments (P %lld Cin %d Cout %d ldx %d ldy %d)",
+            (long long)P, Cin, Cout, ldx, ldy);
+  pixel_linear_f32(x, ldx, w, b, y, ldy, P, Cin, Cout, (hipStream_t)stream);
+  API_END(ctx)
+}
+int svg_op_vae_sample(svg_ctx* ctx, const float* mom, int ldm, const float* eps, float* z, float* mom_nchw, int N, int h, int w, void* stream) {
+  API_BEGIN
+  SVG_CHECK(mom && z && ldm >= 8 && N > 0 && h > 0 && w > 0, "vae_sample op: bad arguments (ldm %d N %d %dx%d)", ldm, N, h, w);
+  vae_sample(mom, ldm, eps, z, mom_nchw, N, h, w, (hipStream_t)stream);
+  API_END(ctx)
+}
+int svg_op_add_noise(svg_ctx* ctx, const float* x0, const float* noise, float* out, int64_t n, float sa, float s1a, void* stream) {
+  API_BEGIN
+  SVG_CHECK(x0 && noise && out && n > 0, "add_noise op: bad arguments (n %lld)", (long long)n);
+  add_noise(x0, noise, out, n, sa, s1a, (hipStream_t)stream);
+  API_END(ctx)
+}
 #endif
+
+// the kernels of eltwise.hip with a 16-bit side on caller buffers.  Test hooks.
+int SVG_OP(svg_op_img_to_act)(svg_ctx* ctx, const uint8_t* img, uint16_t* out, int N, int sh, int sw, int H, int W, void* stream) {
+  API_BEGIN
+  SVG_CHECK(img && out && N > 0 && sh > 0 && sw > 0 && H > 0 && W > 0 && ((uintptr_t)out & 15) == 0, "img_to_act op: bad arguments (N %d %dx%d -> %dx%d)",
+            N, sh, sw, H, W);
+  img_to_act(img, (h16*)out, N, sh, sw, H, W, (hipStream_t)stream);
+  API_END(ctx)
+}
+int SVG_OP(svg_op_nchw_to_act)(svg_ctx* ctx, const float* x, uint16_t* out, int N, int C, int h, int w, int Cpad, float scale, void* stream) {
+  API_BEGIN
+  SVG_CHECK(x && out && N > 0 && C > 0 && Cpad >= C && h > 0 && w > 0, "nchw_to_act op: bad arguments (N %d C %d -> %d %dx%d)", N, C, Cpad, h, w);
+  nchw_to_act(x, (h16*)out, N, C, h, w, Cpad, scale, (hipStream_t)stream);
+  API_END(ctx)
+}
+int SVG_OP(svg_op_actf32_pad_h16)(svg_ctx* ctx, const float* x, int C, uint16_t* out, int Cpad, int64_t P, void* stream) {
+  API_BEGIN
+  SVG_CHECK(x && out && P > 0 && C > 0 && Cpad >= C, "actf32_pad_h16 op: bad arguments (P %lld C %d -> %d)", (long long)P, C, Cpad);
+  actf32_pad_h16(x, C, (h16*)out, Cpad, P, (hipStream_t)stream);
+  API_END(ctx)
+}
+int SVG_OP(svg_op_concat_channels)(svg_ctx* ctx, const uint16_t* a, int Ca, const uint16_t* b, int Cb, uint16_t* out, int64_t P, void* stream) {
+  API_BEGIN
+  SVG_CHECK(a && b && out && P > 0 && Ca > 0 && Cb > 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) == 0,
+            "concat_channels op: bad arguments (P %lld Ca %d Cb %d, 16-byte aligned pointers)", (long long)P, Ca, Cb);
+  concat_channels((const h16*)a, Ca, (const h16*)b, Cb, (h16*)out, P, (hipStream_t)stream);
+  API_END(ctx)
+}
+int SVG_OP(svg_op_f32_to_h16)(svg_ctx* ctx, const float* x, uint16_t* y, int64_t n, void* stream) {
+  API_BEGIN
+  SVG_CHECK(x && y && n > 0, "f32_to_h16 op: bad arguments (n %lld)", (long long)n);
+  f32_to_h16(x, (h16*)y, n, (hipStream_t)stream);
+  API_END(ctx)
+}
+int SVG_OP(svg_op_f32_to_h16_x8)(svg_ctx* ctx, const float* x, uint16_t* y, int64_t n, void* stream) {
+  API_BEGIN
+  SVG_CHECK(x && y && n > 0, "f32_to_h16_x8 op: bad arguments (n %lld)", (long long)n);
+  f32_to_h16_x8(x, (h16*)y, n, (hipStream_t)stream);
+  API_END(ctx)
+}
+int SVG_OP(svg_op_h16_to_f32)(svg_ctx* ctx, const uint16_t* x, float* y, int64_t n, void* stream) {
+  API_BEGIN
+  SVG_CHECK(x && y && n > 0, "h16_to_f32 op: bad arguments (n %lld)", (long long)n);
+  h16_to_f32((const h16*)x, y, n, (hipStream_t)stream);
+  API_END(ctx)
+}
+int SVG_OP(svg_op_timestep_embed)(svg_ctx* ctx, const float* t, uint16_t* out, int N, int dim, void* stream) {
+  API_BEGIN
+  SVG_CHECK(t && out && N > 0 && dim >= 2 && dim % 2 == 0, "timestep_embed op: bad arguments (N %d dim %d)", N, dim);
+  timestep_embed(t, (h16*)out, N, dim, (hipStream_t)stream);
+  API_END(ctx)
+}
 
 int SVG_OP(svg_op_layernorm)(svg_ctx* ctx, const uint16_t* x, const float* gamma, const float* beta, uint16_t* out, int M, int C,
                      float eps, void* stream) {
