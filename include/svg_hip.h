@@ -235,6 +235,25 @@ int svg_fvd_preprocess(svg_ctx* ctx, const uint8_t* videos, int B, int T, int H,
  * Means / unbiased covariances in f64, the two symmetric square roots (fvd_2.py:22-33, SVD there) by a Jacobi eigen-decomposition. */
 int svg_frechet_distance(svg_ctx* ctx, const float* x1, int n1, const float* x2, int n2, int d, double* out, void* stream);
 
+/* ---- per-frame quality: squared error and SSIM (an addition: the reference measures FVD only and has no counterpart) -------------- */
+/* a, b: uint8 NHWC stacks (N,H,W,3), contiguous, any byte alignment.  Per image n:
+ *   sse[n]   int64: the exact integer sum of (a - b)^2 over all H*W*3 bytes (MSE = sse / (H*W*3), PSNR = 10 log10(255^2 / MSE) are host
+ *            arithmetic on it);
+ *   ssim[n]  double: the mean over the (H-10)*(W-10)*3 valid positions of the SSIM map of Wang et al. 2004 — 11x11 Gaussian window G,
+ *            sigma 1.5, taps exp(-x^2 / (2 sigma^2)) for x = -5..5 normalised to sum 1, separable; K1 = 0.01, K2 = 0.03, data range 255, so
+ *            C1 = 6.5025, C2 = 58.5225; per channel mu = G*a, var_a = G*a^2 - mu_a^2, cov = G*ab - mu_a mu_b and
+ *            s = (2 mu_a mu_b + C1)(2 cov + C2) / ((mu_a^2 + mu_b^2 + C1)(var_a + var_b + C2))
+ *            (skimage structural_similarity(gaussian_weights=True, use_sample_covariance=False, data_range=255, channel_axis=-1); the
+ *            valid-convolution form of tf.image.ssim).  The map is computed in f32, its sum in double.
+ *   ssim_map (optional, may be NULL): f32 (N,H-10,W-10,3), every map value; sse and ssim get the same bits with or without it.
+ * sse, ssim and ssim_map are device memory; the call only enqueues and does not synchronise.  The sums are taken in a fixed order and
+ * without atomics: an image gives the same bits alone, repeated, or inside a larger batch.  The per-tile partial sums live in the
+ * context's workspace (the call takes part in svg_plan_begin .. svg_plan_end; a second call of a shape grows nothing).
+ * SVG_ERR_INVALID, with nothing launched: a null ctx, a, b, sse or ssim; N < 1; H < 11 or W < 11; H or W > 16384 (image offsets are
+ * 32-bit: H*W*3 < 2^31); N * ceil((H-10)/32) * ceil((W-10)/32) >= 2^31 (one workgroup per image and 32x32 map tile). */
+int svg_frame_metrics(svg_ctx* ctx, const uint8_t* a, const uint8_t* b, int N, int H, int W, int64_t* sse, double* ssim, float* ssim_map,
+                      void* stream);
+
 /* ---- VAE ------------------------------------------------------------------------------------ */
 /* img: u8 NHWC (N,srcH,srcW,3); nearest-resized to (H,W) on the fly when they differ.
  * eps: f32 (N,4,H/8,W/8) standard-normal draws for .sample(), or NULL for the distribution mean.

@@ -126,6 +126,7 @@ SIGNATURES = {
     "svg_fvd_logits": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "svg_fvd_preprocess": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "svg_frechet_distance": [_vp, _vp, _i, _vp, _i, _i, C.POINTER(C.c_double), _vp],
+    "svg_frame_metrics": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
     "svg_vae_encode": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "svg_vae_decode": [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp],
     "svg_unet_forward": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp],
@@ -599,6 +600,23 @@ class Context:
         self.check(self.lib.svg_frechet_distance(self.h, _ptr(x1), x1.shape[0], _ptr(x2), x2.shape[0], x1.shape[1], C.byref(out), _stream()),
                    "svg_frechet_distance")
         return float(out.value)
+
+    # ---- per-frame quality ------------------------------------------------------------------------
+    def frame_metrics(self, a, b, return_map=False):
+        """a, b (N,H,W,3) uint8 -> (sse int64[N], ssim float64[N] [, ssim_map f32 (N,H-10,W-10,3)]) on the device (svg_frame_metrics:
+        the exact sum of squared differences and the mean 11x11-Gaussian SSIM per image; enqueues only)"""
+        a = torch.as_tensor(a).to(self.device).contiguous()
+        b = torch.as_tensor(b).to(self.device).contiguous()
+        if a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.dim() != 4 or a.shape[-1] != 3 or a.shape != b.shape:
+            raise ValueError("frame_metrics: two uint8 (N,H,W,3) stacks of one shape, got %s %s and %s %s"
+                             % (a.dtype, tuple(a.shape), b.dtype, tuple(b.shape)))
+        N, H, W, _ = a.shape
+        sse = torch.empty((N,), device=self.device, dtype=torch.int64)
+        ssim = torch.empty((N,), device=self.device, dtype=torch.float64)
+        smap = torch.empty((N, max(H - 10, 0), max(W - 10, 0), 3), device=self.device, dtype=torch.float32) if return_map else None
+        self.check(self.lib.svg_frame_metrics(self.h, _ptr(a), _ptr(b), N, H, W, _ptr(sse), _ptr(ssim), _ptr(smap), _stream()),
+                   "svg_frame_metrics")
+        return (sse, ssim, smap) if return_map else (sse, ssim)
 
     def vae_encode(self, img_u8, H=None, W=None, eps=None, return_moments=False):
         """img_u8: (N,h,w,3) uint8 on device; nearest-resized to (H,W) when given."""

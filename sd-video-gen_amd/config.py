@@ -57,6 +57,8 @@ def build_parser():
     # the denoising loop's sampler and schedule length (num_inference_steps, hard-coded to 50 in the reference's predict loop)
     p.add_argument("--sampler", type=str, default="ddim", choices=("ddim", "dpmpp_2m"))
     p.add_argument("--denoise_steps", type=int, default=50)
+    # prediction.predict: hold each clip's last --pred_frames frames out as targets and report PSNR / SSIM per predicted step
+    p.add_argument("--eval_holdout", type=bool, default=False)
     # the trainer's optimizer step (all off by default: the reference's optim.Adam(lr) on every batch)
     p.add_argument("--grad_accum", type=int, default=1)              # batches whose gradients are summed per optimizer step
     p.add_argument("--clip_grad_norm", type=float, default=0.0)      # global gradient 2-norm bound, 0: no clipping

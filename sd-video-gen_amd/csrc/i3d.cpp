@@ -213,6 +213,21 @@ int svg_frechet_distance(svg_ctx* ctx, const float* x1, int n1, const float* x2,
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }
+int svg_frame_metrics(svg_ctx* ctx, const uint8_t* a, const uint8_t* b, int N, int H, int W, int64_t* sse, double* ssim, float* ssim_map, void* stream) {
+  try {
+    SVG_CHECK(ctx && a && b && sse && ssim, "frame_metrics: null argument");
+    SVG_CHECK(N >= 1 && H >= 11 && W >= 11, "frame_metrics: N=%d H=%d W=%d (at least one image, at least the 11 x 11 window)", N, H, W);
+    SVG_CHECK(H <= 16384 && W <= 16384 && (int64_t)N * frame_metrics_tiles(H, W) < ((int64_t)1 << 31),
+              "frame_metrics: N=%d H=%d W=%d (H, W <= 16384; N * ceil((H-10)/32) * ceil((W-10)/32) < 2^31)", N, H, W);
+    run_planned(ctx, [&]() {
+      const int64_t parts = (int64_t)N * frame_metrics_tiles(H, W);
+      double* part_ssim = ctx->arena.get<double>(parts);
+      uint32_t* part_sse = ctx->arena.get<uint32_t>(parts);
+      if (SVG_LAUNCHING(ctx)) frame_metrics(a, b, N, H, W, part_ssim, part_sse, sse, ssim, ssim_map, (hipStream_t)stream);
+    });
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
 
 // ---- the kernels one by one (test hooks: each is the launcher the model calls; sizes and pads come from same_pad above) ----------------
 int svg_op_conv3d(svg_ctx* ctx, const float* x, int B, int T, int H, int W, int Cin_pad, const float* w, const float* bias, float* y, int64_t y_elems,

@@ -353,3 +353,10 @@ void xf_adamw(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chunks,
 // kpad (B,Tk) or null: additive key-padding bias per batch row
 void xf_attention(const float* q, int ldq, const float* k, const float* v, int ldk, const float* mask,
                   float* o, int Tq, int Tk, int B, int heads, int hd, hipStream_t s, const float* kpad = nullptr);
+
+// ---- frame comparison (metrics.hip): per image of two uint8 NHWC stacks (N,H,W,3) the exact sum of squared differences and the mean SSIM
+// (definition: include/svg_hip.h, svg_frame_metrics); H, W >= 11.  part_ssim / part_sse: N * frame_metrics_tiles(H, W) elements of
+// scratch; ssim_map (N,H-10,W-10,3) f32 or null
+int64_t frame_metrics_tiles(int H, int W);
+void frame_metrics(const uint8_t* a, const uint8_t* b, int N, int H, int W, double* part_ssim, uint32_t* part_sse, int64_t* sse, double* ssim,
+                   float* ssim_map, hipStream_t s);

@@ -329,17 +329,22 @@ def main(argv=None):
         print("[sd-video-gen] weights: transformer=%s vae=%s unet=%s" % (weights_source, sd_utils.vae_source, sd_utils.unet_source))
     model.eval()
     F = config.FRAME_SIZE
+    # --eval_holdout: every clip is loaded with pred_frames more frames, which are the targets of the predicted steps, not conditioning
+    hold = bool(args.eval_holdout)
+    if hold and args.pred_frames < 1:
+        raise ValueError("--eval_holdout needs --pred_frames >= 1")
+    n_frames = 5 + args.pred_frames if hold else 5
     if args.dataset in ("synthetic-ball", "synthetic"):
-        clips = bouncing_ball_clips(8, F, 5, seed=0)
+        clips = bouncing_ball_clips(8, F, n_frames, seed=0)
     elif args.dataset in ("ball", "kitti"):                                                               # predict.py:56-58,111-114
         from .loaders import BouncingBall, Kitti
         if not args.folder:
             raise ValueError("dataset '%s' needs --folder (directory with a test/ stage of PNG frame folders)" % args.dataset)
         # unshuffled: clip c keeps its index (and its seed) whatever the world size — the reference shuffles (batch_size 1)
-        ds = (BouncingBall if args.dataset == "ball" else Kitti)(num_frames=5, stride=1, dir=args.folder, stage="test", shuffle=False)
-        items = [ds[i][1] for i in range(len(ds)) if len(ds.dataset[i]) == 5]
+        ds = (BouncingBall if args.dataset == "ball" else Kitti)(num_frames=n_frames, stride=1, dir=args.folder, stage="test", shuffle=False)
+        items = [ds[i][1] for i in range(len(ds)) if len(ds.dataset[i]) == n_frames]
         if not items:
-            raise ValueError("no 5-frame clips under %s" % os.path.join(args.folder, "test"))
+            raise ValueError("no %d-frame clips under %s" % (n_frames, os.path.join(args.folder, "test")))
         clips = torch.from_numpy(np.stack(items))
         if clips.shape[2] != F or clips.shape[3] != F:
             raise ValueError("frames are %dx%d but config %s has FRAME_SIZE %d" % (clips.shape[2], clips.shape[3], args.config, F))
@@ -351,18 +356,18 @@ def main(argv=None):
         if rank == 0:
             print("Loading UCF dataset from", ucf_data_dir)
         train = args.mode == "train"
-        ucf = UCF101Frames(ucf_data_dir, ucf_label_dir, frames_per_clip=5, train=train, transform=ucf_transform(F),
+        ucf = UCF101Frames(ucf_data_dir, ucf_label_dir, frames_per_clip=n_frames, train=train, transform=ucf_transform(F),
                            frame_rate=3 if train else None)               # :99-106
         if len(ucf) == 0:
-            raise ValueError("no 5-frame clips under %s for the %s fold" % (ucf_data_dir, args.mode))
+            raise ValueError("no %d-frame clips under %s for the %s fold" % (n_frames, ucf_data_dir, args.mode))
         n_clips = min(len(ucf), int(os.environ.get("SVG_MAX_CLIPS", "256")))
         clips = torch.from_numpy(np.stack([ucf[i][0] for i in range(n_clips)]))          # unshuffled: clip c keeps its seed
     elif args.folder:
-        clips = _png_clips(args.folder, F)
+        clips = _png_clips(args.folder, F, n_frames=n_frames)
     else:
         raise ValueError("Invalid dataset name")                                                          # predict.py:70
     n = clips.shape[0]
-    lat, frames = run_sharded(clips, lambda c, seeds: sample_clips(
+    lat, frames = run_sharded(clips[:, :5].contiguous() if hold else clips, lambda c, seeds: sample_clips(
         model, sd_utils, c.to(device), args.pred_frames, denoise=bool(args.denoise), start_step=args.denoise_start_step,
         num_inference_steps=args.denoise_steps, sampler=args.sampler, seeds=seeds, return_frames=True))                          # ends in the ONE collective of the path
     if rank == 0:
@@ -374,4 +379,15 @@ def main(argv=None):
                 folder_index = len(os.listdir("outputs"))
                 save_frames(frames[c].cpu().numpy(), [False] * n_in + [True] * (frames.shape[1] - n_in),
                             os.path.join("outputs", str(folder_index)))
+        if hold:
+            # on the gathered frames against the clips every rank holds: no further collective, the same figures at any world size
+            from . import metrics
+            res = metrics.holdout_metrics(frames, clips, 5)
+            for row in metrics.format_table(res):
+                print(row)
+            if args.save_output:
+                import json
+                os.makedirs("outputs", exist_ok=True)
+                with open(os.path.join("outputs", "metrics_%s_%s_%s.json" % (args.config, args.index, args.mode)), "w") as f:
+                    json.dump(metrics.to_json(res), f, indent=1)
     return lat

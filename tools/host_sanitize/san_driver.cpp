@@ -223,6 +223,15 @@ static void i3d_and_fvd() {
   double fd = 0;
   OK(svg_frechet_distance(ctx, a.data(), 20, b.data(), 30, 16, &fd, nullptr));
   EXPECT_ERR(svg_frechet_distance(ctx, a.data(), 1, b.data(), 30, 16, &fd, nullptr));
+  // frame metrics: the partials come from the arena; bad sizes and null pointers are refused before anything is planned
+  std::vector<uint8_t> fa((size_t)3 * 43 * 75 * 3, 7), fb(fa.size(), 9);
+  std::vector<int64_t> sse(3);
+  std::vector<double> ssim(3);
+  OK(svg_frame_metrics(ctx, fa.data(), fb.data(), 3, 43, 75, sse.data(), ssim.data(), nullptr, nullptr));
+  EXPECT_ERR(svg_frame_metrics(ctx, fa.data(), fb.data(), 3, 10, 75, sse.data(), ssim.data(), nullptr, nullptr));
+  EXPECT_ERR(svg_frame_metrics(ctx, fa.data(), fb.data(), 0, 43, 75, sse.data(), ssim.data(), nullptr, nullptr));
+  EXPECT_ERR(svg_frame_metrics(ctx, fa.data(), nullptr, 3, 43, 75, sse.data(), ssim.data(), nullptr, nullptr));
+  EXPECT_ERR(svg_frame_metrics(ctx, fa.data(), fb.data(), 3, 43, 16385, sse.data(), ssim.data(), nullptr, nullptr));
 }
 
 static void ops() {
