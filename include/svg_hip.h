@@ -660,6 +660,32 @@ int svg_op_f32_to_h16_x8(svg_ctx* ctx, const float* x, uint16_t* y, int64_t n, v
 int svg_op_h16_to_f32(svg_ctx* ctx, const uint16_t* x, float* y, int64_t n, void* stream);
 int svg_op_timestep_embed(svg_ctx* ctx, const float* t, uint16_t* out, int N, int dim, void* stream);
 int svg_op_add_noise(svg_ctx* ctx, const float* x0, const float* noise, float* out, int64_t n, float sa, float s1a, void* stream);
+/* The update kernels of the sampling loop (csrc/sampler.hip), one by one on caller data (test hooks: each checks its arguments on the
+ * host and calls the launcher the loop calls).  f32 device buffers of n elements; eps = eps_u + guidance (eps_c - eps_u), or eps_u when
+ * eps_c is NULL.  The row (8 floats, laid out per rule as in csrc/sampler_plan.h) is given in exactly one of two ways: `row`, 8 HOST
+ * floats, or row idx[0] of the DEVICE table `tab` under the DEVICE counter `idx`; the other way's pointers are NULL.  Nothing on the host
+ * can check idx[0] against the size of the table.  A null tensor, n < 0 or a row given both ways or neither is SVG_ERR_INVALID, and
+ * nothing is launched.
+ * svg_op_ddim_step: x_out = DDIM step with clip_sample; x_out may be x.
+ * svg_op_dpmpp_step: x_out = DPM-Solver++(2M) step, m_out (may be NULL) = the x0 prediction; m_prev is read only by a second-order row
+ *   (row[5] != 0).  x_out may be x and m_out may be m_prev.  Refused: a second-order argument row with m_prev NULL, and ANY table row
+ *   with m_prev NULL (its order is on the device).
+ * svg_op_lms_step: x_out = x + sum_k c_k d_{i-k}, the combined eps stored to slot i & 3 of the ring dhist (4 x n floats); x_out may be x.
+ *   `order` and `step` are read for a table row only, where the caller must state what the row holds: both, like those of an argument
+ *   row, are refused unless step >= 0 and 1 <= order <= min(4, step + 1).
+ * svg_op_lms_input: o0 (and o1 unless NULL) = x * c, c the argument or, with tab and idx, element 1 of the table row; o0 may be x.
+ * svg_op_sampler_tvec: tvec[0 .. nb-1] = element 0 (the timestep) of the table row idx[0]; nb > 0.
+ * svg_op_sampler_bump: idx[0] += 1. */
+int svg_op_ddim_step(svg_ctx* ctx, const float* x, const float* eps_u, const float* eps_c, float guidance, float* x_out, int64_t n,
+                     const float* row, const float* tab, const int* idx, void* stream);
+int svg_op_dpmpp_step(svg_ctx* ctx, const float* x, const float* eps_u, const float* eps_c, float guidance, const float* m_prev,
+                      float* x_out, float* m_out, int64_t n, const float* row, const float* tab, const int* idx, void* stream);
+int svg_op_lms_step(svg_ctx* ctx, const float* x, const float* eps_u, const float* eps_c, float guidance, float* dhist, float* x_out,
+                    int64_t n, const float* row, const float* tab, const int* idx, int order, int step, void* stream);
+int svg_op_lms_input(svg_ctx* ctx, const float* x, float* o0, float* o1, int64_t n, float c, const float* tab, const int* idx,
+                     void* stream);
+int svg_op_sampler_tvec(svg_ctx* ctx, float* tvec, int nb, const float* tab, const int* idx, void* stream);
+int svg_op_sampler_bump(svg_ctx* ctx, int* idx, void* stream);
 /* LayerNorm over the last dim of (M,C) bf16. */
 int svg_op_layernorm(svg_ctx* ctx, const uint16_t* x, const float* gamma, const float* beta,
                      uint16_t* out, int M, int C, float eps, void* stream);

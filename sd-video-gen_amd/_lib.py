@@ -199,6 +199,12 @@ SIGNATURES = {
     "svg_op_h16_to_f32": [_vp, _vp, _vp, _i64, _vp],
     "svg_op_timestep_embed": [_vp, _vp, _vp, _i, _i, _vp],
     "svg_op_add_noise": [_vp, _vp, _vp, _vp, _i64, _f, _f, _vp],
+    "svg_op_ddim_step": [_vp, _vp, _vp, _vp, _f, _vp, _i64, _vp, _vp, _vp, _vp],
+    "svg_op_dpmpp_step": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "svg_op_lms_step": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _vp],
+    "svg_op_lms_input": [_vp, _vp, _vp, _vp, _i64, _f, _vp, _vp, _vp],
+    "svg_op_sampler_tvec": [_vp, _vp, _i, _vp, _vp, _vp],
+    "svg_op_sampler_bump": [_vp, _vp, _vp],
     "svg_op_layernorm": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp],
     "svg_op_attention": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _f, _vp],
     "svg_op_attention_ex": [_vp, C.POINTER(AttnDesc), C.POINTER(_i), _vp],

@@ -582,6 +582,59 @@ int svg_op_add_noise(svg_ctx* ctx, const float* x0, const float* noise, float* o
   add_noise(x0, noise, out, n, sa, s1a, (hipStream_t)stream);
   API_END(ctx)
 }
+// the update kernels of sampler.hip on caller buffers, each through the launcher the loop calls.  Test hooks.  The row of a launch
+// is either `row` (kSamplerRow host floats) or row idx[0] of the device table `tab`: exactly one of the two.
+static SamplerRowArg op_row(const char* what, const float* row, const float* tab, const int* idx) {
+  SVG_CHECK((row != nullptr) != (tab != nullptr), "%s op: exactly one of an argument row and a table row", what);
+  SVG_CHECK(!tab || idx, "%s op: a table row needs its device counter", what);
+  SVG_CHECK(!row || !idx, "%s op: an argument row takes no device counter", what);
+  return row ? sampler_row(row) : sampler_row_at(tab, idx);
+}
+int svg_op_ddim_step(svg_ctx* ctx, const float* x, const float* eps_u, const float* eps_c, float guidance, float* x_out, int64_t n,
+                     const float* row, const float* tab, const int* idx, void* stream) {
+  API_BEGIN
+  SVG_CHECK(x && eps_u && x_out && n >= 0, "ddim_step op: null tensor or negative size (n %lld)", (long long)n);
+  ddim_step(x, eps_u, eps_c, guidance, x_out, n, op_row("ddim_step", row, tab, idx), (hipStream_t)stream);
+  API_END(ctx)
+}
+int svg_op_dpmpp_step(svg_ctx* ctx, const float* x, const float* eps_u, const float* eps_c, float guidance, const float* m_prev, float* x_out,
+                      float* m_out, int64_t n, const float* row, const float* tab, const int* idx, void* stream) {
+  API_BEGIN
+  SVG_CHECK(x && eps_u && x_out && n >= 0, "dpmpp_step op: null tensor or negative size (n %lld)", (long long)n);
+  // k of a table row is on the device: the launcher cannot tell a second-order row there, and the kernel would read through null
+  SVG_CHECK(m_prev || !tab, "dpmpp_step op: a table row needs m_prev");
+  dpmpp_step(x, eps_u, eps_c, guidance, m_prev, x_out, m_out, n, op_row("dpmpp_step", row, tab, idx), (hipStream_t)stream);
+  API_END(ctx)
+}
+int svg_op_lms_step(svg_ctx* ctx, const float* x, const float* eps_u, const float* eps_c, float guidance, float* dhist, float* x_out, int64_t n,
+                    const float* row, const float* tab, const int* idx, int order, int step, void* stream) {
+  API_BEGIN
+  SVG_CHECK(x && eps_u && dhist && x_out && n >= 0, "lms_step op: null tensor or negative size (n %lld)", (long long)n);
+  const SamplerRowArg r = op_row("lms_step", row, tab, idx);
+  // the launcher checks the order and step of an argument row; those of a table row are on the device, so the caller states them
+  if (tab) SVG_CHECK(step >= 0 && order >= 1 && order <= 4 && order <= step + 1, "lms_step op: order %d at step %d", order, step);
+  lms_step(x, eps_u, eps_c, guidance, dhist, x_out, n, r, (hipStream_t)stream);
+  API_END(ctx)
+}
+int svg_op_lms_input(svg_ctx* ctx, const float* x, float* o0, float* o1, int64_t n, float c, const float* tab, const int* idx, void* stream) {
+  API_BEGIN
+  SVG_CHECK(x && o0 && n >= 0, "lms_input op: null tensor or negative size (n %lld)", (long long)n);
+  SVG_CHECK((tab != nullptr) == (idx != nullptr), "lms_input op: a table row needs the table and its device counter");
+  lms_input(x, o0, o1, n, tab ? sampler_row_at(tab, idx) : sampler_scale(c), (hipStream_t)stream);
+  API_END(ctx)
+}
+int svg_op_sampler_tvec(svg_ctx* ctx, float* tvec, int nb, const float* tab, const int* idx, void* stream) {
+  API_BEGIN
+  SVG_CHECK(tvec && tab && idx && nb > 0, "sampler_tvec op: bad arguments (nb %d)", nb);
+  sampler_tvec(tvec, nb, tab, idx, (hipStream_t)stream);
+  API_END(ctx)
+}
+int svg_op_sampler_bump(svg_ctx* ctx, int* idx, void* stream) {
+  API_BEGIN
+  SVG_CHECK(idx, "sampler_bump op: null counter");
+  sampler_bump(idx, (hipStream_t)stream);
+  API_END(ctx)
+}
 #endif
 
 // the kernels of eltwise.hip with a 16-bit side on caller buffers.  Test hooks.
