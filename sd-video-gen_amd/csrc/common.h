@@ -12,6 +12,7 @@
 #include <atomic>
 #include <mutex>
 #include <shared_mutex>
+#include <utility>
 
 // Storage type of the Stable-Diffusion side (activations and packed weights; accumulation is always f32).  Every SD source is
 // compiled twice into libsvg_hip.so: once with h16 = bf16 (namespace sd_bf16, the default) and once with -DSVG_F16, h16 = IEEE
@@ -171,6 +172,35 @@ struct DeviceWideScope {
   DeviceWideScope() : lk(svg_capture_mutex()) {}
   DeviceWideScope(const DeviceWideScope&) = delete;
 };
+
+// An instantiated hipGraph, released with its owner (move-only; assigning {} releases it now).  The template it was instantiated from
+// goes with it, after the executable graph, unless drop_template() released it earlier.
+struct GraphExec {
+  hipGraphExec_t h = nullptr;
+  hipGraph_t tmpl = nullptr;
+  GraphExec() = default;
+  GraphExec(GraphExec&& o) noexcept : h(o.h), tmpl(o.tmpl) { o.h = nullptr; o.tmpl = nullptr; }
+  GraphExec& operator=(GraphExec&& o) noexcept { std::swap(h, o.h); std::swap(tmpl, o.tmpl); return *this; }
+  ~GraphExec() { if (h) hipGraphExecDestroy(h); drop_template(); }
+  void drop_template() { if (tmpl) hipGraphDestroy(tmpl); tmpl = nullptr; }
+  explicit operator bool() const { return h != nullptr; }
+};
+// THE capture window of the library: what record() enqueues on `s` becomes an executable graph instead of running.  CaptureScope is
+// held from begin to end of capture only; a throwing record() ends the capture and drops the partial graph before the exception goes
+// on.  The owner returned holds the template too (released with it if instantiation fails): each call site releases it where it
+// always did, the training step at once (drop_template), the sampling loop with the executable graph once the stream has run it.
+template <class Record>
+GraphExec capture_graph(hipStream_t s, Record&& record) {
+  GraphExec exec;
+  {
+    CaptureScope cap;
+    HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    try { record(); } catch (...) { hipStreamEndCapture(s, &exec.tmpl); throw; }
+    HIP_OK(hipStreamEndCapture(s, &exec.tmpl));
+  }
+  HIP_OK(hipGraphInstantiate(&exec.h, exec.tmpl, nullptr, nullptr, 0));
+  return exec;
+}
 
 // Kernel families for the profiler (index into prof_entries)
 enum ProfKind {

@@ -678,35 +678,22 @@ void UnetModel::sample_loop(svg_ctx* ctx, int sampler, float* z, int N, int h, i
       return;
     }
     one_step(start_step, true);                        // direct launches: fills the K / V^T cache, bumps the counter
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    {
-      // Shared with other captures, exclusive against every device-wide synchronisation of the library (common.h): HIP rejects
-      // hipDeviceSynchronize from ANY thread while this window is open (BENCH_r05: the other stream group's workspace growth).
-      CaptureScope cap;
-      HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      try {
-        one_step(start_step + 1, true);
-        // test hook: keep the window open so that a test can drive another context's calls into it (tests/test_streams_gpu.py)
-        if (const int64_t hold = svg_env_i64("SVG_TEST_CAPTURE_HOLD_MS", 0)) std::this_thread::sleep_for(std::chrono::milliseconds(hold));
-      } catch (...) {
-        hipStreamEndCapture(s, &graph);
-        if (graph) hipGraphDestroy(graph);
-        throw;
-      }
-      HIP_OK(hipStreamEndCapture(s, &graph));
-    }
-    hipError_t ge = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    if (ge != hipSuccess) { hipGraphDestroy(graph); HIP_OK(ge); }
+    // The window is shared with other captures and exclusive against every device-wide synchronisation of the library (capture_graph,
+    // common.h): HIP rejects hipDeviceSynchronize from ANY thread while it is open (BENCH_r05: the other stream group's workspace growth).
+    GraphExec exec = capture_graph(s, [&]() {
+      one_step(start_step + 1, true);
+      // test hook: keep the window open so that a test can drive another context's calls into it (tests/test_streams_gpu.py)
+      if (const int64_t hold = svg_env_i64("SVG_TEST_CAPTURE_HOLD_MS", 0)) std::this_thread::sleep_for(std::chrono::milliseconds(hold));
+    });
+    hipError_t ge = hipSuccess;
     for (int i = start_step + 1; i < num_steps; ++i) {
-      ge = hipGraphLaunch(exec, s);
+      ge = hipGraphLaunch(exec.h, s);
       if (ge != hipSuccess) break;
     }
     // the executable graph is released once the stream has run it (the call stays asynchronous otherwise: the destroy is deferred
     // through a host callback would need a thread-safe queue; a DDIM loop is 1.5 s of GPU work, the sync costs nothing measurable)
     hipError_t se = hipStreamSynchronize(s);
-    hipGraphExecDestroy(exec);
-    hipGraphDestroy(graph);
+    exec = {};
     HIP_OK(ge);
     HIP_OK(se);
   };

@@ -1,10 +1,22 @@
-// C ABI, operator level: the forward kernels of the latent Transformer / CLIP text tower / MiniLM encoder one by one, and one
-// layer-walking launch over a caller's stage table (test hooks: each is its launcher and nothing else).  Every hook checks what its
-// launcher silently assumes of its arguments and refuses (svg_fail) instead of launching.
+// C ABI, operator level: the forward kernels of the latent Transformer / CLIP text tower / MiniLM encoder one by one, one
+// layer-walking launch over a caller's stage table, and the training-step kernels (xf_train.hip) one by one (test hooks: each is its
+// launcher and nothing else).  Every hook checks what its launcher silently assumes of its arguments and refuses (svg_fail) instead of
+// launching.
 #include "models.h"
 #include "xf_walk.h"
 #include "../../include/svg_hip.h"
 #include <vector>
+
+namespace {
+// the dropout site (seed, site, p) of an operator-level call: the seed goes through the context's device word, as the kernels read it
+XfDrop op_drop(svg_ctx* ctx, const char* what, uint64_t seed, int site, float p, hipStream_t s) {
+  SVG_CHECK(p >= 0.f && p < 1.f && site >= 0, "%s: bad dropout site (site %d, p %g)", what, site, p);
+  if (!ctx->seed_scratch) ctx->seed_scratch = (uint64_t*)ctx->dalloc(sizeof(uint64_t));
+  HIP_OK(hipMemcpyAsync(ctx->seed_scratch, &seed, sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  HIP_OK(hipStreamSynchronize(s));            // `seed` is a stack word
+  return XfDrop{ctx->seed_scratch, (uint32_t)site, p};
+}
+}  // namespace
 
 extern "C" {
 
@@ -142,6 +154,128 @@ int svg_op_xf_walk(svg_ctx* ctx, const svg_walk_stage* stages, int n_stages, int
     if (info) { info[0] = grid; info[1] = (int)lds; info[2] = small ? 0 : xf_walk_mt(rows); info[3] = (int)sizeof(svg_walk_stage); }
     HIP_OK(hipStreamSynchronize(s));                       // a give-up of THIS launch is raised by this call
     xf_walk_check(ctx);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+// ---- the training kernels one by one ---------------------------------------------------------------------------------------------
+int svg_op_dropout_mask(svg_ctx* ctx, uint64_t seed, int site, float p, float* out, int64_t n, void* stream) {
+  try {
+    SVG_CHECK(ctx && out && n >= 0, "svg_op_dropout_mask: bad argument");
+    xf_drop_mask(op_drop(ctx, "svg_op_dropout_mask", seed, site, p, (hipStream_t)stream), out, n, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_gemm_tn(svg_ctx* ctx, const float* dY, int ldy, const float* X, int ldx, float* dW, float* db, int M, int N, int K, int accumulate,
+                      void* stream) {
+  try {
+    SVG_CHECK(ctx && dY && X && dW, "svg_op_xf_gemm_tn: null argument");
+    xf_gemm_tn(dY, ldy, X, ldx, dW, db, M, N, K, accumulate, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_gemm_nn(svg_ctx* ctx, const float* dY, int ldy, const float* W, float* out, int M, int N, int K, const float* gate, float gate_scale,
+                      const float* add, int* splits, void* stream) {
+  try {
+    SVG_CHECK(ctx && dY && W && out, "svg_op_xf_gemm_nn: null argument");
+    SVG_CHECK(M > 0 && N > 0 && K > 0, "svg_op_xf_gemm_nn: empty problem %d x %d x %d", M, N, K);
+    run_planned(ctx, [&]() {
+      float* slabs = ctx->arena.get<float>(xf_gemm_nn_slab_floats(M, N, K));
+      if (SVG_LAUNCHING(ctx)) xf_gemm_nn(dY, ldy, W, slabs, out, M, N, K, gate, gate_scale, add, (hipStream_t)stream);
+    });
+    if (splits) *splits = xf_gemm_nn_splits(N, K);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_relu_drop(svg_ctx* ctx, const float* h, float* r, int64_t n, uint64_t seed, int site, float p, void* stream) {
+  try {
+    SVG_CHECK(ctx && h && r && n >= 0, "svg_op_xf_relu_drop: bad argument");
+    xf_relu_drop(h, r, n, op_drop(ctx, "svg_op_xf_relu_drop", seed, site, p, (hipStream_t)stream), (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_add_ln_train(svg_ctx* ctx, const float* x, const float* r, uint64_t seed, int site, float p, const float* gamma, const float* beta,
+                           float* y, float* xhat, float* rstd, int M, int d, float eps, void* stream) {
+  try {
+    SVG_CHECK(ctx && x && gamma && beta && y && xhat && rstd, "svg_op_xf_add_ln_train: null argument");
+    xf_add_ln_train(x, r, op_drop(ctx, "svg_op_xf_add_ln_train", seed, site, p, (hipStream_t)stream), gamma, beta, y, xhat, rstd, M, d, eps,
+                    (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_ln_bwd(svg_ctx* ctx, const float* dy, const float* xhat, const float* rstd, const float* gamma, float* dz, float* dz_drop,
+                     uint64_t seed, int site, float p, float* dgamma, float* dbeta, int M, int d, int accumulate, void* stream) {
+  try {
+    SVG_CHECK(ctx && dy && xhat && rstd && gamma && dz && dgamma && dbeta, "svg_op_xf_ln_bwd: null argument");
+    xf_ln_bwd(dy, xhat, rstd, gamma, dz, dz_drop, op_drop(ctx, "svg_op_xf_ln_bwd", seed, site, p, (hipStream_t)stream), dgamma, dbeta, M, d,
+              accumulate, (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_attention_train(svg_ctx* ctx, const float* q, int ldq, const float* k, const float* v, int ldk, const float* mask, float* o,
+                              float* P, int Tq, int Tk, int B, int heads, int hd, uint64_t seed, int site, float p, void* stream) {
+  try {
+    SVG_CHECK(ctx && q && k && v && o && P, "svg_op_xf_attention_train: null argument");
+    xf_attention_train(q, ldq, k, v, ldk, mask, o, P, Tq, Tk, B, heads, hd,
+                       op_drop(ctx, "svg_op_xf_attention_train", seed, site, p, (hipStream_t)stream), (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_attention_bwd(svg_ctx* ctx, const float* dout, const float* q, int ldq, const float* k, const float* v, int ldk, const float* P,
+                            float* dq, int lddq, float* dk, float* dv, int lddk, int Tq, int Tk, int B, int heads, int hd, uint64_t seed,
+                            int site, float p, void* stream) {
+  try {
+    SVG_CHECK(ctx && dout && q && k && v && P && dq && dk && dv, "svg_op_xf_attention_bwd: null argument");
+    xf_attention_bwd(dout, q, ldq, k, v, ldk, P, dq, lddq, dk, dv, lddk, Tq, Tk, B, heads, hd,
+                     op_drop(ctx, "svg_op_xf_attention_bwd", seed, site, p, (hipStream_t)stream), (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_embed_post_train(svg_ctx* ctx, const float* emb, const float* pe, const int32_t* pe_row, const float* text, int d_txt, float* y,
+                               int B, int T, int d, float scale, uint64_t seed, int site, float p, void* stream) {
+  try {
+    SVG_CHECK(ctx && emb && pe && y, "svg_op_xf_embed_post_train: null argument");
+    xf_embed_post_train(emb, pe, pe_row, text, d_txt, y, B, T, d, scale,
+                        op_drop(ctx, "svg_op_xf_embed_post_train", seed, site, p, (hipStream_t)stream), (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_embed_post_bwd(svg_ctx* ctx, const float* dy, float* de, int B, int T, int d, int d_img, float scale, uint64_t seed, int site,
+                             float p, void* stream) {
+  try {
+    SVG_CHECK(ctx && dy && de, "svg_op_xf_embed_post_bwd: null argument");
+    xf_embed_post_bwd(dy, de, B, T, d, d_img, scale, op_drop(ctx, "svg_op_xf_embed_post_bwd", seed, site, p, (hipStream_t)stream),
+                      (hipStream_t)stream);
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
+
+int svg_op_xf_criterion(svg_ctx* ctx, const float* pred, const float* expected, float* dpred, float* losses, int Tt, int B, int D, int t0,
+                        int fh, int fw, float w_mse, float w_l1, float w_gdl, float alpha, float w_nce, float temperature, void* stream) {
+  try {
+    SVG_CHECK(ctx && pred && expected && dpred && losses, "svg_op_xf_criterion: null argument");
+    SVG_CHECK(Tt > 0 && B > 0, "svg_op_xf_criterion: empty problem (%d x %d rows)", Tt, B);
+    float h_losses[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    run_planned(ctx, [&]() {
+      float* part = ctx->arena.get<float>((int64_t)Tt * B * 3);          // the per-row partial sums and the device copy of the losses
+      float* part2 = ctx->arena.get<float>((int64_t)Tt * B);
+      float* d_losses = ctx->arena.get<float>(5);
+      if (!SVG_LAUNCHING(ctx)) return;
+      xf_criterion(pred, expected, dpred, part, part2, d_losses, Tt, B, D, t0, fh, fw, w_mse, w_l1, w_gdl, alpha, w_nce, temperature,
+                   (hipStream_t)stream);
+      HIP_OK(hipMemcpyAsync(h_losses, d_losses, sizeof(h_losses), hipMemcpyDeviceToHost, (hipStream_t)stream));
+      HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+    });
+    for (int i = 0; i < 5; ++i) losses[i] = h_losses[i];                 // losses: host memory
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }

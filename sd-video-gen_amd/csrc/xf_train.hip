@@ -838,10 +838,15 @@ void xf_criterion(const float* pred, const float* expected, float* dpred, float*
   check_launch("xf_criterion");
 }
 
+// the bias corrections of step `step`, as both update kernels take them (torch computes them in double)
+struct AdamBias { float bc1, bc2_sqrt; };
+static AdamBias adam_bias(float beta1, float beta2, int step) {
+  return AdamBias{(float)(1.0 - pow((double)beta1, (double)step)), (float)sqrt(1.0 - pow((double)beta2, (double)step))};
+}
+
 void xf_adam(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chunks, float lr, float beta1, float beta2, float eps, int step,
              float* const* ema, float ema_decay, hipStream_t s) {
-  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));          // torch computes the corrections in double
-  const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+  const auto [bc1, bc2_sqrt] = adam_bias(beta1, beta2, step);
   if (ema) hipLaunchKernelGGL(adam_kernel<true>, dim3(n_chunks), dim3(256), 0, s, tens, chunks, lr, beta1, beta2, eps, bc1, bc2_sqrt, ema, ema_decay);
   else hipLaunchKernelGGL(adam_kernel<false>, dim3(n_chunks), dim3(256), 0, s, tens, chunks, lr, beta1, beta2, eps, bc1, bc2_sqrt, ema, 0.f);
   check_launch("xf_adam");
@@ -856,8 +861,7 @@ void xf_grad_norm(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chu
 void xf_adamw(const XfAdamTensor* tens, const XfAdamChunk* chunks, int n_chunks, float lr, float beta1, float beta2, float eps, int step,
               float weight_decay, int decoupled, float grad_scale, float max_norm, const double* norm, float* const* ema, float ema_decay,
               hipStream_t s) {
-  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));          // as xf_adam
-  const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+  const auto [bc1, bc2_sqrt] = adam_bias(beta1, beta2, step);
   // torch.optim.AdamW: param.mul_(1 - lr * weight_decay) with the factor evaluated in double
   const float decay_mul = decoupled ? (float)(1.0 - (double)lr * (double)weight_decay) : 1.f;
   const float wd_l2 = decoupled ? 0.f : weight_decay;

@@ -4,11 +4,14 @@
 // (validation_loop: the same loss in eval mode) over torch.nn.Transformer (post-norm, ReLU, dropout after the positional
 // encoding, on the attention probabilities, after each sublayer and inside the feed-forward) and torch.optim.Adam(lr).
 // The Stable Diffusion side stays frozen (encode_batch is the VAE encoder the sampling path already has).
+// This file: the training state (XfTrain), the step as operations of xf_graph() and their backward (Run), loss_pass, and the public
+// training entry points.  The per-kernel test hooks are in xf_ops.cpp.
 #include "xf_plan.h"
 #include "../../include/svg_hip.h"
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
+#include <tuple>
 
 struct XfTrain {
   struct Slot { float* g = nullptr; float* m = nullptr; float* v = nullptr; float* e = nullptr; int64_t n = 0; };
@@ -27,21 +30,45 @@ struct XfTrain {
   double* h_norm = nullptr;      // pinned mirror
   float* d_losses = nullptr;     // [5]
   float* h_losses = nullptr;     // pinned mirror: a device-to-pageable copy goes through the runtime's staging path and its host thread
-  // One plan per call signature (shapes + every criterion / dropout parameter except the seed): the workspace high-water mark and,
-  // for the loss (+ backward) calls, the captured hipGraph of the whole step.  ~540 launches per step cost more host time than
-  // the GPU needs to run them (15.3 ms wall against 9.3 ms of kernels); the graph replays them from fixed staging buffers.
+  // The signature of a call: the shapes, the mode and every criterion / dropout parameter except the seed.
+  struct Sig {
+    int B, Ts, Tt, backward;       // backward: 0, 1 or SVG_BACKWARD_ACCUMULATE
+    bool loss, has_mask, has_text; // loss == false: forward only
+    int frames_to_predict, feat_h, feat_w;
+    float w_mse, w_l1, w_gdl, gdl_alpha, w_contrastive, temperature, dropout_p;
+    auto key() const {
+      return std::make_tuple(B, Ts, Tt, backward, loss, has_mask, has_text, frames_to_predict, feat_h, feat_w, w_mse, w_l1, w_gdl, gdl_alpha,
+                             w_contrastive, temperature, dropout_p);
+    }
+    bool operator==(const Sig& o) const { return key() == o.key(); }
+  };
+  // One plan per signature: the workspace high-water mark and, for the loss (+ backward) calls, the captured hipGraph of the whole
+  // step.  ~540 launches per step cost more host time than the GPU needs to run them (15.3 ms wall against 9.3 ms of kernels); the
+  // graph replays them from fixed staging buffers.
   struct Plan {
-    svg_train_cfg cfg{}; int B = 0, Ts = 0, Tt = 0, backward = 0, mode = 0; bool has_mask = false, has_text = false;
+    Sig sig{};
     int64_t high = 0;
-    hipGraphExec_t exec = nullptr;
+    GraphExec exec;
     char* arena_base = nullptr;
     float *src = nullptr, *tgt = nullptr, *exp = nullptr, *text = nullptr, *mask = nullptr;
   };
   std::vector<Plan> plans;
-  uint64_t* d_seed = nullptr;     // device seed word read by every dropout site
-  uint64_t* h_seed = nullptr;     // pinned ring of 16 seeds (a call that does not synchronise must not race the next one's seed)
-  hipEvent_t seed_ev[16] = {};    // recorded behind each slot's upload: the 17th unsynchronised call waits for the 1st one's copy
-  int seed_slot = 0;
+  // The seed word every dropout site reads, fed through a pinned ring of 16 (a call that does not synchronise must not race the
+  // next one's seed); an event behind each slot's upload makes the 17th unsynchronised call wait for the 1st one's copy.
+  struct SeedRing {
+    uint64_t *d_seed = nullptr, *h_seed = nullptr;
+    hipEvent_t ev[16] = {};
+    int slot = 0;
+    void upload(uint64_t seed, hipStream_t s) {
+      slot = (slot + 1) & 15;
+      if (!ev[slot]) HIP_OK(hipEventCreateWithFlags(&ev[slot], hipEventDisableTiming));
+      else HIP_OK(hipEventSynchronize(ev[slot]));       // the slot's previous upload (16 calls ago) has been read
+      h_seed[slot] = seed;
+      HIP_OK(hipMemcpyAsync(d_seed, h_seed + slot, sizeof(uint64_t), hipMemcpyHostToDevice, s));
+      HIP_OK(hipEventRecord(ev[slot], s));
+    }
+    ~SeedRing() { if (h_seed) hipHostFree(h_seed); for (auto e : ev) if (e) hipEventDestroy(e); }
+  } seed;
   // The training step's own workspace.  The captured graph bakes workspace addresses: if it lived in the context-wide arena, a
   // VAE / UNet / CLIP call of the same context on ANOTHER stream (or a forward that regrows the arena) could reuse or move the
   // memory while the graph is still running.  loss_pass swaps these in for the duration of its planning and launches.
@@ -55,12 +82,9 @@ struct XfTrain {
     return p;
   }
   ~XfTrain() {
-    for (auto& pl : plans) if (pl.exec) hipGraphExecDestroy(pl.exec);
     for (void* p : bufs) hipFree(p);
     if (h_losses) hipHostFree(h_losses);
-    if (h_seed) hipHostFree(h_seed);
     if (h_norm) hipHostFree(h_norm);
-    for (auto e : seed_ev) if (e) hipEventDestroy(e);
     if (ws_buf.p) hipFree(ws_buf.p);
   }
 };
@@ -68,6 +92,8 @@ struct XfTrain {
 namespace {
 
 constexpr int kAdamChunk = 1 << 16;
+using Sig = XfTrain::Sig;
+struct Inputs { const float *src, *tgt, *expected, *text, *mask; };   // expected == nullptr: forward only
 
 // what a forward operation leaves for its backward: activations, and the parameters (w) with where their gradients go (gw, gb)
 struct LinTape { const float* x = nullptr; int M = 0, N = 0, K = 0; const float* w = nullptr; float* gw = nullptr; float* gb = nullptr; };
@@ -83,17 +109,21 @@ struct MhaTape {
 struct FfnTape { LinTape l1, l2; float* r = nullptr; float gate_scale = 1.f; };
 struct LayerTape { MhaTape sa, ca; FfnTape ff; LnTape n[3]; };     // an encoder layer leaves ca and n[2] unused
 
-// the training kernels (xf_train.hip) as the operations of xf_graph(), and their backward counterparts
+// One pass over the step: the training kernels (xf_train.hip) as the operations of xf_graph(), their backward counterparts, and
+// step() = forward, criterion, backward.  The order of launches and of arena.get calls IS the captured graph and the workspace layout.
 struct Run {
   static constexpr bool kSharesEmbedding = false;   // each embedding draws its own dropout mask
-  svg_ctx* ctx; XfModel* m; XfTrain* tr; hipStream_t s; int B; const uint64_t* seed; float p; bool grads;
-  bool acc;      // SVG_BACKWARD_ACCUMULATE: every gradient store adds to its slot
+  svg_ctx* ctx; XfModel* m; XfTrain* tr; const Sig& sig; hipStream_t s; const int B; const uint64_t* seed; const float p;
+  const bool acc;    // SVG_BACKWARD_ACCUMULATE: every gradient store adds to its slot
   const float* text = nullptr;
   uint32_t site = 0;
   std::vector<LayerTape> enc, dec;
   LinTape e_lin[2], l_out;
   XfDrop e_drop[2];
   LnTape n_enc, n_dec;
+  Run(svg_ctx* ctx_, XfModel* m_, XfTrain* tr_, const Sig& g, hipStream_t s_)
+      : ctx(ctx_), m(m_), tr(tr_), sig(g), s(s_), B(g.B), seed(tr_->seed.d_seed), p(g.backward ? g.dropout_p : 0.f),
+        acc(g.backward == SVG_BACKWARD_ACCUMULATE), enc(m_->enc_layers), dec(m_->dec_layers) {}
   struct Layer { const XfModel::LayerW& w; const XfTable<float*>::Layer& g; LayerTape& t; };
   Layer layer(bool d, int i) { return d ? Layer{m->w.dec[i], tr->g.dec[i], dec[i]} : Layer{m->w.enc[i], tr->g.enc[i], enc[i]}; }
   bool go() const { return SVG_LAUNCHING(ctx); }
@@ -218,6 +248,69 @@ struct Run {
     lin_bwd(e_lin[which], de, nullptr, nullptr, nullptr, 1.f, accumulate);
   }
   float* out(const float* x, int M) { return lin(l_out, x, m->w.out_w, m->w.out_b, tr->g.out_w, tr->g.out_b, M, m->d_lat, m->d_model); }
+
+  // ---- the step ---------------------------------------------------------------------------------------------------------------
+  // forward only: the prediction (Tt,B,D_lat) goes to pred_out
+  void step(const Inputs& in, float* pred_out) {
+    text = in.text;
+    float* pred = xf_graph(*this, *m, XfChunk{B, sig.Ts, sig.Tt, in.src, in.tgt, in.mask, in.text, nullptr, nullptr, m->iota, nullptr});
+    if (!sig.loss) {
+      if (go()) HIP_OK(hipMemcpyAsync(pred_out, pred, (size_t)sig.Tt * B * m->d_lat * sizeof(float), hipMemcpyDeviceToDevice, s));
+      return;
+    }
+    float* dpred = criterion(pred, in.expected);
+    if (sig.backward) backward(dpred);
+  }
+  // on the last frames_to_predict positions (trainer.py:145); returns the gradient of the prediction
+  float* criterion(const float* pred, const float* expected) {
+    const int Mt = sig.Tt * B;
+    float* dpred = get<float>((int64_t)Mt * m->d_lat);
+    float* part = get<float>((int64_t)Mt * 3);
+    float* part2 = get<float>(Mt);
+    if (go())
+      xf_criterion(pred, expected, dpred, part, part2, tr->d_losses, sig.Tt, B, m->d_lat, sig.Tt - sig.frames_to_predict, sig.feat_h, sig.feat_w,
+                   sig.w_mse, sig.w_l1, sig.w_gdl, sig.gdl_alpha, sig.w_contrastive, sig.temperature, s);
+    return dpred;
+  }
+  // backward of one post-norm sublayer y = LN(x + dropout(f(x))), f the feed-forward or an attention: returns dx
+  float* ffn_sub_bwd(const LnTape& n, const FfnTape& f, const float* dy) {
+    float* dzd = nullptr;
+    float* dz = add_ln_bwd(n, dy, &dzd);
+    float* dx = get<float>((int64_t)n.M * m->d_model);
+    ffn_bwd(f, dzd, dx, dz);
+    return dx;
+  }
+  float* mha_sub_bwd(const LnTape& n, const MhaTape& a, const float* dy, float* dmem = nullptr, bool dmem_accumulate = false) {
+    float* dzd = nullptr;
+    float* dz = add_ln_bwd(n, dy, &dzd);
+    float* dx = get<float>((int64_t)n.M * m->d_model);
+    mha_bwd(a, dzd, dx, dz, dmem, dmem_accumulate);
+    return dx;
+  }
+  void backward(const float* dpred) {
+    const int d = m->d_model, Ms = sig.Ts * B, Mt = sig.Tt * B;
+    float* dx = get<float>((int64_t)Mt * d);
+    lin_bwd(l_out, dpred, dx);
+    float* dxt = add_ln_bwd(n_dec, dx, nullptr);
+    float* dmem = get<float>((int64_t)Ms * d);
+    bool dmem_set = false;
+    for (int i = m->dec_layers - 1; i >= 0; --i) {
+      const LayerTape& t = dec[i];
+      dxt = ffn_sub_bwd(t.n[2], t.ff, dxt);                     // x2 + dropout(ff(x2))
+      dxt = mha_sub_bwd(t.n[1], t.ca, dxt, dmem, dmem_set);     // x1 + dropout(cross(x1, mem))
+      dmem_set = true;
+      dxt = mha_sub_bwd(t.n[0], t.sa, dxt);                     // x + dropout(self(x))
+    }
+    if (!dmem_set && go()) SDNS::fill_f32(dmem, (int64_t)Ms * d, 0.f, s);
+    float* dxs = add_ln_bwd(n_enc, dmem, nullptr);
+    for (int i = m->enc_layers - 1; i >= 0; --i) {
+      const LayerTape& t = enc[i];
+      dxs = ffn_sub_bwd(t.n[1], t.ff, dxs);
+      dxs = mha_sub_bwd(t.n[0], t.sa, dxs);
+    }
+    embed_bwd(0, dxs, sig.Ts, false);
+    embed_bwd(1, dxt, sig.Tt, true);                // the embedding layer is shared: second contribution accumulates
+  }
 };
 
 void ensure_train(svg_ctx* ctx, XfModel* m) {
@@ -250,8 +343,8 @@ void ensure_train(svg_ctx* ctx, XfModel* m) {
   tr->d_norm = (double*)tr->dalloc(sizeof(double));
   HIP_OK(hipHostMalloc((void**)&tr->h_norm, sizeof(double), hipHostMallocDefault));
   HIP_OK(hipHostMalloc((void**)&tr->h_losses, 5 * sizeof(float), hipHostMallocDefault));
-  tr->d_seed = (uint64_t*)tr->dalloc(sizeof(uint64_t));
-  HIP_OK(hipHostMalloc((void**)&tr->h_seed, 16 * sizeof(uint64_t), hipHostMallocDefault));
+  tr->seed.d_seed = (uint64_t*)tr->dalloc(sizeof(uint64_t));
+  HIP_OK(hipHostMalloc((void**)&tr->seed.h_seed, 16 * sizeof(uint64_t), hipHostMallocDefault));
   HIP_OK(hipMemcpy(tr->d_tens, tens.data(), tens.size() * sizeof(XfAdamTensor), hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(tr->d_chunks, chunks.data(), chunks.size() * sizeof(XfAdamChunk), hipMemcpyHostToDevice));
   tr->n_chunks = (int)chunks.size();
@@ -260,150 +353,81 @@ void ensure_train(svg_ctx* ctx, XfModel* m) {
   m->train = tr.release();
 }
 
-// expected == nullptr: forward only (train-mode dropout when backward != 0), the prediction (Tt,B,D_lat) goes to pred_out
-void loss_pass(svg_ctx* ctx, XfModel* m, const svg_train_cfg& cfg, const float* src, const float* tgt, const float* expected, const float* text,
-               int B, int Ts, int Tt, const float* mask, int backward, float* losses_host, hipStream_t s, float* pred_out = nullptr) {
+void check_call(const XfModel* m, const Sig& g) {
   SVG_CHECK(m->ready, "transformer: svg_finalize has not been called");
-  SVG_CHECK((m->text_dim > 0) == (text != nullptr), "transformer: the text-conditioned variant needs (and only it takes) a text embedding");
-  SVG_CHECK(B >= 1 && B <= 64 && Ts >= 1 && Tt >= 1 && Ts <= 32 && Tt <= 32, "transformer training: B=%d Ts=%d Tt=%d unsupported (B <= 64, T <= 32)", B, Ts, Tt);
-  SVG_CHECK(cfg.dropout_p >= 0.f && cfg.dropout_p < 1.f, "dropout_p %g out of range", cfg.dropout_p);
-  if (expected) {
-    SVG_CHECK(cfg.frames_to_predict >= 1 && cfg.frames_to_predict <= Tt, "frames_to_predict %d out of range 1..%d", cfg.frames_to_predict, Tt);
-    SVG_CHECK(cfg.feat_h > 0 && cfg.feat_w > 0 && 4 * cfg.feat_h * cfg.feat_w == m->d_lat, "criterion: D_lat %d is not 4 x %d x %d", m->d_lat,
-              cfg.feat_h, cfg.feat_w);
-    SVG_CHECK(cfg.w_contrastive == 0.f || (cfg.temperature > 0.f && cfg.feat_h * cfg.feat_w <= 4096), "contrastive loss: bad temperature / patch count");
+  SVG_CHECK((m->text_dim > 0) == g.has_text, "transformer: the text-conditioned variant needs (and only it takes) a text embedding");
+  SVG_CHECK(g.B >= 1 && g.B <= 64 && g.Ts >= 1 && g.Tt >= 1 && g.Ts <= 32 && g.Tt <= 32,
+            "transformer training: B=%d Ts=%d Tt=%d unsupported (B <= 64, T <= 32)", g.B, g.Ts, g.Tt);
+  SVG_CHECK(g.dropout_p >= 0.f && g.dropout_p < 1.f, "dropout_p %g out of range", g.dropout_p);
+  if (!g.loss) return;
+  SVG_CHECK(g.frames_to_predict >= 1 && g.frames_to_predict <= g.Tt, "frames_to_predict %d out of range 1..%d", g.frames_to_predict, g.Tt);
+  SVG_CHECK(g.feat_h > 0 && g.feat_w > 0 && 4 * g.feat_h * g.feat_w == m->d_lat, "criterion: D_lat %d is not 4 x %d x %d", m->d_lat, g.feat_h,
+            g.feat_w);
+  SVG_CHECK(g.w_contrastive == 0.f || (g.temperature > 0.f && g.feat_h * g.feat_w <= 4096), "contrastive loss: bad temperature / patch count");
+}
+
+// the training workspace stands in for the context arena until the call returns (or throws)
+struct ArenaSwap {
+  svg_ctx* c; XfTrain* t;
+  ArenaSwap(svg_ctx* c_, XfTrain* t_) : c(c_), t(t_) { std::swap(c->arena, t->ws); std::swap(c->arena_buf, t->ws_buf); }
+  ~ArenaSwap() { std::swap(c->arena, t->ws); std::swap(c->arena_buf, t->ws_buf); }
+};
+
+// the plan of a signature; a new one takes its workspace need from a dry pass of the step, and is dropped again if that throws
+template <class Body>
+XfTrain::Plan& find_or_plan(svg_ctx* ctx, XfTrain* tr, const Sig& sig, Body&& dry_pass) {
+  for (auto& pl : tr->plans)
+    if (pl.sig == sig) return pl;
+  tr->plans.emplace_back();
+  tr->plans.back().sig = sig;
+  ctx->arena.dry = true; ctx->arena.high = 0;
+  try { dry_pass(); } catch (...) { ctx->arena.dry = false; tr->plans.pop_back(); throw; }
+  ctx->arena.dry = false;
+  tr->plans.back().high = ctx->arena.high;
+  return tr->plans.back();
+}
+
+// a replayed step reads its inputs from the plan's fixed staging buffers (allocated at the signature's first replay)
+Inputs stage(XfModel* m, XfTrain::Plan& pl, const Inputs& in, hipStream_t s) {
+  const Sig& g = pl.sig;
+  const int64_t rows_s = (int64_t)g.B * g.Ts * m->d_lat, rows_t = (int64_t)g.B * g.Tt * m->d_lat;
+  const struct { float** slot; const float* from; int64_t floats; } table[] = {
+      {&pl.src, in.src, rows_s}, {&pl.tgt, in.tgt, rows_t}, {&pl.exp, in.expected, rows_t},
+      {&pl.text, in.text, (int64_t)g.B * m->text_dim}, {&pl.mask, in.mask, (int64_t)g.Tt * g.Tt}};
+  for (auto& e : table) {
+    if (!e.from) continue;                         // no text / no mask: the slot stays null
+    if (!*e.slot) *e.slot = (float*)m->train->dalloc(e.floats * sizeof(float));
+    HIP_OK(hipMemcpyAsync(*e.slot, e.from, (size_t)e.floats * sizeof(float), hipMemcpyDefault, s));
   }
+  return Inputs{pl.src, pl.tgt, pl.exp, pl.text, pl.mask};
+}
+
+// in.expected == nullptr: forward only (train-mode dropout when backward != 0), the prediction (Tt,B,D_lat) goes to pred_out
+void loss_pass(svg_ctx* ctx, XfModel* m, const svg_train_cfg& cfg, const Inputs& in, int B, int Ts, int Tt, int backward, float* losses_host,
+               hipStream_t s, float* pred_out = nullptr) {
+  const Sig sig{B, Ts, Tt, backward, in.expected != nullptr, in.mask != nullptr, in.text != nullptr, cfg.frames_to_predict, cfg.feat_h,
+                cfg.feat_w, cfg.w_mse, cfg.w_l1, cfg.w_gdl, cfg.gdl_alpha, cfg.w_contrastive, cfg.temperature, cfg.dropout_p};
+  check_call(m, sig);
   ensure_train(ctx, m);
   XfTrain* tr = m->train;
-  if (expected && backward) tr->has_grads = true;
-  const int d = m->d_model, Ms = Ts * B, Mt = Tt * B;
-  auto body = [&](const float* src, const float* tgt, const float* expected, const float* text, const float* mask) {
-    Run r{ctx, m, tr, s, B, tr->d_seed, backward ? cfg.dropout_p : 0.f, backward != 0, backward == SVG_BACKWARD_ACCUMULATE};
-    r.text = text;
-    r.enc.resize(m->enc_layers); r.dec.resize(m->dec_layers);
-    float* pred = xf_graph(r, *m, XfChunk{B, Ts, Tt, src, tgt, mask, text, nullptr, nullptr, m->iota, nullptr});
-    if (!expected) {                                           // forward only
-      if (r.go()) HIP_OK(hipMemcpyAsync(pred_out, pred, (size_t)Mt * m->d_lat * sizeof(float), hipMemcpyDeviceToDevice, s));
-      return;
-    }
-
-    // criterion on the last frames_to_predict positions (trainer.py:145)
-    float* dpred = r.get<float>((int64_t)Mt * m->d_lat);
-    float* part = r.get<float>((int64_t)Mt * 3);
-    float* part2 = r.get<float>(Mt);
-    if (r.go())
-      xf_criterion(pred, expected, dpred, part, part2, tr->d_losses, Tt, B, m->d_lat, Tt - cfg.frames_to_predict, cfg.feat_h, cfg.feat_w, cfg.w_mse,
-                   cfg.w_l1, cfg.w_gdl, cfg.gdl_alpha, cfg.w_contrastive, cfg.temperature, s);
-    if (!backward) return;
-
-    // ---- backward ----------------------------------------------------------------------------------------------------------
-    float* dx = r.get<float>((int64_t)Mt * d);
-    r.lin_bwd(r.l_out, dpred, dx);
-    float* dxt = r.add_ln_bwd(r.n_dec, dx, nullptr);
-    float* dmem = r.get<float>((int64_t)Ms * d);
-    bool dmem_set = false;
-    for (int i = m->dec_layers - 1; i >= 0; --i) {
-      LayerTape& t = r.dec[i];
-      float *dzd = nullptr, *dz;
-      dz = r.add_ln_bwd(t.n[2], dxt, &dzd);                     // x2 + dropout(ff(x2))
-      float* dx2 = r.get<float>((int64_t)Mt * d);
-      r.ffn_bwd(t.ff, dzd, dx2, dz);
-      dz = r.add_ln_bwd(t.n[1], dx2, &dzd);                     // x1 + dropout(cross(x1, mem))
-      float* dx1 = r.get<float>((int64_t)Mt * d);
-      r.mha_bwd(t.ca, dzd, dx1, dz, dmem, dmem_set);
-      dmem_set = true;
-      dz = r.add_ln_bwd(t.n[0], dx1, &dzd);                     // x + dropout(self(x))
-      float* dx0 = r.get<float>((int64_t)Mt * d);
-      r.mha_bwd(t.sa, dzd, dx0, dz, nullptr, false);
-      dxt = dx0;
-    }
-    if (!dmem_set && r.go()) SDNS::fill_f32(dmem, (int64_t)Ms * d, 0.f, s);
-    float* dxs = r.add_ln_bwd(r.n_enc, dmem, nullptr);
-    for (int i = m->enc_layers - 1; i >= 0; --i) {
-      LayerTape& t = r.enc[i];
-      float *dzd = nullptr, *dz;
-      dz = r.add_ln_bwd(t.n[1], dxs, &dzd);
-      float* dx1 = r.get<float>((int64_t)Ms * d);
-      r.ffn_bwd(t.ff, dzd, dx1, dz);
-      dz = r.add_ln_bwd(t.n[0], dx1, &dzd);
-      float* dx0 = r.get<float>((int64_t)Ms * d);
-      r.mha_bwd(t.sa, dzd, dx0, dz, nullptr, false);
-      dxs = dx0;
-    }
-    r.embed_bwd(0, dxs, Ts, false);
-    r.embed_bwd(1, dxt, Tt, true);                // the embedding layer is shared: second contribution accumulates
-  };
-  // ---- the plan of this call signature ----------------------------------------------------------------------------------------
-  struct ArenaSwap {       // the training workspace stands in for the context arena until this call returns (or throws)
-    svg_ctx* c; XfTrain* t;
-    ArenaSwap(svg_ctx* c_, XfTrain* t_) : c(c_), t(t_) { std::swap(c->arena, t->ws); std::swap(c->arena_buf, t->ws_buf); }
-    ~ArenaSwap() { std::swap(c->arena, t->ws); std::swap(c->arena_buf, t->ws_buf); }
-  } arena_swap(ctx, tr);
-  const int mode = expected ? 0 : 2;
-  XfTrain::Plan* pl = nullptr;
-  for (auto& c : tr->plans)
-    if (c.B == B && c.Ts == Ts && c.Tt == Tt && c.backward == backward && c.mode == mode && c.has_mask == (mask != nullptr) &&
-        c.has_text == (text != nullptr) && c.cfg.frames_to_predict == cfg.frames_to_predict && c.cfg.feat_h == cfg.feat_h &&
-        c.cfg.feat_w == cfg.feat_w && c.cfg.w_mse == cfg.w_mse && c.cfg.w_l1 == cfg.w_l1 && c.cfg.w_gdl == cfg.w_gdl &&
-        c.cfg.gdl_alpha == cfg.gdl_alpha && c.cfg.w_contrastive == cfg.w_contrastive && c.cfg.temperature == cfg.temperature &&
-        c.cfg.dropout_p == cfg.dropout_p) { pl = &c; break; }
-  if (!pl) {
-    tr->plans.emplace_back();
-    pl = &tr->plans.back();
-    pl->cfg = cfg; pl->B = B; pl->Ts = Ts; pl->Tt = Tt; pl->backward = backward; pl->mode = mode;
-    pl->has_mask = mask != nullptr; pl->has_text = text != nullptr;
-    ctx->arena.reset(); ctx->arena.dry = true; ctx->arena.high = 0;          // dry pass: the workspace this signature needs
-    try { body(src, tgt, expected, text, mask); } catch (...) { ctx->arena.dry = false; tr->plans.pop_back(); throw; }
-    ctx->arena.dry = false;
-    pl->high = ctx->arena.high;
-  }
-  ctx->ensure_arena(pl->high);
-  tr->seed_slot = (tr->seed_slot + 1) & 15;
-  if (!tr->seed_ev[tr->seed_slot]) HIP_OK(hipEventCreateWithFlags(&tr->seed_ev[tr->seed_slot], hipEventDisableTiming));
-  else HIP_OK(hipEventSynchronize(tr->seed_ev[tr->seed_slot]));       // the slot's previous upload (16 calls ago) has been read
-  tr->h_seed[tr->seed_slot] = cfg.seed;
-  HIP_OK(hipMemcpyAsync(tr->d_seed, tr->h_seed + tr->seed_slot, sizeof(uint64_t), hipMemcpyHostToDevice, s));
-  HIP_OK(hipEventRecord(tr->seed_ev[tr->seed_slot], s));
-  const bool graph_env = svg_env_i64("SVG_TRAIN_GRAPH", 1) != 0;
+  if (sig.loss && backward) tr->has_grads = true;
+  ArenaSwap arena_swap(ctx, tr);
+  auto body = [&](const Inputs& x) { ctx->arena.reset(); Run(ctx, m, tr, sig, s).step(x, pred_out); };
+  XfTrain::Plan& pl = find_or_plan(ctx, tr, sig, [&]() { body(in); });
+  ctx->ensure_arena(pl.high);
+  tr->seed.upload(cfg.seed, s);
   // hipGraph replay of the whole step: needs a capturable (non-null) stream; the inputs go through fixed staging buffers
-  if (graph_env && expected && s != nullptr && !ctx->prof) {
-    if (!pl->src) {
-      pl->src = (float*)tr->dalloc((int64_t)B * Ts * m->d_lat * sizeof(float));
-      pl->tgt = (float*)tr->dalloc((int64_t)B * Tt * m->d_lat * sizeof(float));
-      pl->exp = (float*)tr->dalloc((int64_t)B * Tt * m->d_lat * sizeof(float));
-      if (text) pl->text = (float*)tr->dalloc((int64_t)B * m->text_dim * sizeof(float));
-      if (mask) pl->mask = (float*)tr->dalloc((int64_t)Tt * Tt * sizeof(float));
+  if (svg_env_i64("SVG_TRAIN_GRAPH", 1) != 0 && sig.loss && s != nullptr && !ctx->prof) {
+    const Inputs staged = stage(m, pl, in, s);
+    if (!pl.exec || pl.arena_base != ctx->arena.base) {       // first use, or the workspace moved since the capture
+      pl.exec = {};
+      pl.exec = capture_graph(s, [&]() { body(staged); });
+      pl.exec.drop_template();                                  // a plan lives long: the executable graph is all its replays need
+      pl.arena_base = ctx->arena.base;
     }
-    HIP_OK(hipMemcpyAsync(pl->src, src, (size_t)B * Ts * m->d_lat * sizeof(float), hipMemcpyDefault, s));
-    HIP_OK(hipMemcpyAsync(pl->tgt, tgt, (size_t)B * Tt * m->d_lat * sizeof(float), hipMemcpyDefault, s));
-    HIP_OK(hipMemcpyAsync(pl->exp, expected, (size_t)B * Tt * m->d_lat * sizeof(float), hipMemcpyDefault, s));
-    if (text) HIP_OK(hipMemcpyAsync(pl->text, text, (size_t)B * m->text_dim * sizeof(float), hipMemcpyDefault, s));
-    if (mask) HIP_OK(hipMemcpyAsync(pl->mask, mask, (size_t)Tt * Tt * sizeof(float), hipMemcpyDefault, s));
-    if (!pl->exec || pl->arena_base != ctx->arena.base) {       // first use, or the workspace moved since the capture
-      if (pl->exec) { HIP_OK(hipGraphExecDestroy(pl->exec)); pl->exec = nullptr; }
-      hipGraph_t g = nullptr;
-      {
-        CaptureScope cap;             // shared with other captures, exclusive against device-wide syncs (common.h)
-        HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        try {
-          ctx->arena.reset();
-          body(pl->src, pl->tgt, pl->exp, pl->text, pl->mask);
-        } catch (...) {
-          hipStreamEndCapture(s, &g);
-          if (g) hipGraphDestroy(g);
-          throw;
-        }
-        HIP_OK(hipStreamEndCapture(s, &g));
-      }
-      const hipError_t e = hipGraphInstantiate(&pl->exec, g, nullptr, nullptr, 0);
-      hipGraphDestroy(g);
-      HIP_OK(e);
-      pl->arena_base = ctx->arena.base;
-    }
-    HIP_OK(hipGraphLaunch(pl->exec, s));
+    HIP_OK(hipGraphLaunch(pl.exec.h, s));
   } else {
-    ctx->arena.reset();
-    body(src, tgt, expected, text, mask);
+    body(in);
   }
   if (losses_host) {
     HIP_OK(hipMemcpyAsync(tr->h_losses, tr->d_losses, 5 * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -437,6 +461,24 @@ XfTrain* state_for_restore(svg_ctx* ctx, XfModel* m, bool ema) {
   return tr;
 }
 
+// where a slot keeps a tensor of the training state (nullptr: `kind` names none)
+float* slot_ptr(const XfTrain::Slot& sl, int kind) {
+  return kind == SVG_TENSOR_GRAD ? sl.g : kind == SVG_TENSOR_EXP_AVG ? sl.m : kind == SVG_TENSOR_EXP_AVG_SQ ? sl.v : kind == SVG_TENSOR_EMA ? sl.e : nullptr;
+}
+
+void check_adam_hyper(const char* who, float lr, float beta1, float beta2, float eps) {
+  SVG_CHECK(lr >= 0.f && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "%s: bad hyper-parameters", who);
+}
+
+// enqueues the norm pass; host != nullptr: reads the norm back (synchronises)
+void grad_norm_pass(XfTrain* tr, double* host, hipStream_t s) {
+  xf_grad_norm(tr->d_tens, tr->d_chunks, tr->n_chunks, tr->d_norm_part, tr->d_norm, s);
+  if (!host) return;
+  HIP_OK(hipMemcpyAsync(tr->h_norm, tr->d_norm, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  *host = *tr->h_norm;
+}
+
 }  // namespace
 
 // caller holds DeviceWideScope when m->train exists (svg_destroy, svg_model_configure, svg_load_weight)
@@ -454,7 +496,7 @@ extern "C" int svg_transformer_loss(svg_ctx* ctx, const svg_train_cfg* cfg, cons
     SVG_CHECK(cfg && src && tgt && expected, "svg_transformer_loss: null argument");
     // 0, 1 or SVG_BACKWARD_ACCUMULATE: the plan (and its captured graph) is keyed on the normalised mode
     const int mode = backward == 0 ? 0 : (backward == SVG_BACKWARD_ACCUMULATE ? SVG_BACKWARD_ACCUMULATE : 1);
-    loss_pass(ctx, ctx->xf, *cfg, src, tgt, expected, text, B, Ts, Tt, mask, mode, losses, (hipStream_t)stream);
+    loss_pass(ctx, ctx->xf, *cfg, Inputs{src, tgt, expected, text, mask}, B, Ts, Tt, mode, losses, (hipStream_t)stream);
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }
@@ -467,7 +509,7 @@ extern "C" int svg_transformer_forward_train(svg_ctx* ctx, const float* src, con
     svg_train_cfg cfg{};
     cfg.dropout_p = dropout_p;
     cfg.seed = seed;
-    loss_pass(ctx, ctx->xf, cfg, src, tgt, nullptr, text, B, Ts, Tt, mask, /*train mode*/ 1, nullptr, (hipStream_t)stream, out);
+    loss_pass(ctx, ctx->xf, cfg, Inputs{src, tgt, nullptr, text, mask}, B, Ts, Tt, /*train mode*/ 1, nullptr, (hipStream_t)stream, out);
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }
@@ -475,7 +517,7 @@ extern "C" int svg_transformer_forward_train(svg_ctx* ctx, const float* src, con
 extern "C" int svg_transformer_adam_step(svg_ctx* ctx, float lr, float beta1, float beta2, float eps, void* stream) {
   try {
     SVG_CHECK(ctx && ctx->xf && ctx->xf->train, "adam step: no gradients yet (call svg_transformer_loss with backward=1 first)");
-    SVG_CHECK(lr >= 0.f && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "adam step: bad hyper-parameters");
+    check_adam_hyper("adam step", lr, beta1, beta2, eps);
     XfTrain* tr = ctx->xf->train;
     tr->step += 1;
     xf_adam(tr->d_tens, tr->d_chunks, tr->n_chunks, lr, beta1, beta2, eps, tr->step, tr->ema_decay > 0.f ? tr->d_ema : nullptr, tr->ema_decay,
@@ -483,17 +525,6 @@ extern "C" int svg_transformer_adam_step(svg_ctx* ctx, float lr, float beta1, fl
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }
-
-namespace {
-// enqueues the norm pass; host != nullptr: reads the norm back (synchronises)
-void grad_norm_pass(XfTrain* tr, double* host, hipStream_t s) {
-  xf_grad_norm(tr->d_tens, tr->d_chunks, tr->n_chunks, tr->d_norm_part, tr->d_norm, s);
-  if (!host) return;
-  HIP_OK(hipMemcpyAsync(tr->h_norm, tr->d_norm, sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  *host = *tr->h_norm;
-}
-}  // namespace
 
 extern "C" int svg_transformer_grad_norm(svg_ctx* ctx, double* out, void* stream) {
   try {
@@ -508,8 +539,7 @@ extern "C" int svg_transformer_optim_step(svg_ctx* ctx, const svg_optim_cfg* cfg
   try {
     SVG_CHECK(ctx && ctx->xf && cfg, "svg_transformer_optim_step: null argument");
     SVG_CHECK(ctx->xf->train && ctx->xf->train->has_grads, "optimizer step: no gradients yet (call svg_transformer_loss with backward=1 first)");
-    SVG_CHECK(cfg->lr >= 0.f && cfg->beta1 >= 0.f && cfg->beta1 < 1.f && cfg->beta2 >= 0.f && cfg->beta2 < 1.f && cfg->eps >= 0.f,
-              "optimizer step: bad hyper-parameters");
+    check_adam_hyper("optimizer step", cfg->lr, cfg->beta1, cfg->beta2, cfg->eps);
     SVG_CHECK(cfg->weight_decay >= 0.f, "optimizer step: weight_decay %g is negative", cfg->weight_decay);
     SVG_CHECK(cfg->max_grad_norm >= 0.f, "optimizer step: max_grad_norm %g is negative", cfg->max_grad_norm);
     SVG_CHECK(cfg->grad_scale > 0.f, "optimizer step: grad_scale %g is not positive", cfg->grad_scale);
@@ -538,10 +568,9 @@ extern "C" int svg_transformer_tensor(svg_ctx* ctx, int kind, const char* name, 
       SVG_CHECK(kind == SVG_TENSOR_GRAD || kind == SVG_TENSOR_EXP_AVG || kind == SVG_TENSOR_EXP_AVG_SQ || kind == SVG_TENSOR_EMA,
                 "svg_transformer_tensor: kind %d", kind);
       SVG_CHECK(m->train && m->train->slots.count(name), "svg_transformer_tensor: %s has no training state", name);
-      const XfTrain::Slot& sl = m->train->slots.at(name);
       SVG_CHECK(kind != SVG_TENSOR_EMA || m->train->d_ema,
                 "svg_transformer_tensor: no averaged weights yet (svg_transformer_ema_configure or svg_transformer_set_tensor(SVG_TENSOR_EMA) first)");
-      srcp = kind == SVG_TENSOR_GRAD ? sl.g : (kind == SVG_TENSOR_EXP_AVG ? sl.m : (kind == SVG_TENSOR_EXP_AVG_SQ ? sl.v : sl.e));
+      srcp = slot_ptr(m->train->slots.at(name), kind);
     }
     HIP_OK(hipMemcpyAsync(out, srcp, numel * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
@@ -559,9 +588,7 @@ extern "C" int svg_transformer_set_tensor(svg_ctx* ctx, int kind, const char* na
     const Weight& w = m->ws.get(name);
     SVG_CHECK(numel == w.numel, "svg_transformer_set_tensor: %s has %lld elements, caller gave %lld", name, (long long)w.numel, (long long)numel);
     XfTrain* tr = state_for_restore(ctx, m, kind == SVG_TENSOR_EMA);
-    const XfTrain::Slot& sl = tr->slots.at(name);
-    float* dst = kind == SVG_TENSOR_EXP_AVG ? sl.m : (kind == SVG_TENSOR_EXP_AVG_SQ ? sl.v : sl.e);
-    HIP_OK(hipMemcpyAsync(dst, data, numel * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
+    HIP_OK(hipMemcpyAsync(slot_ptr(tr->slots.at(name), kind), data, numel * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
@@ -593,141 +620,6 @@ extern "C" int svg_transformer_ema_configure(svg_ctx* ctx, float decay) {
       return 0;
     }
     state_for_restore(ctx, ctx->xf, true)->ema_decay = decay;
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
-}
-
-namespace {
-// the dropout site (seed, site, p) of an operator-level call: the seed goes through the context's device word, as the kernels read it
-XfDrop op_drop(svg_ctx* ctx, const char* what, uint64_t seed, int site, float p, hipStream_t s) {
-  SVG_CHECK(p >= 0.f && p < 1.f && site >= 0, "%s: bad dropout site (site %d, p %g)", what, site, p);
-  if (!ctx->seed_scratch) ctx->seed_scratch = (uint64_t*)ctx->dalloc(sizeof(uint64_t));
-  HIP_OK(hipMemcpyAsync(ctx->seed_scratch, &seed, sizeof(uint64_t), hipMemcpyHostToDevice, s));
-  HIP_OK(hipStreamSynchronize(s));            // `seed` is a stack word
-  return XfDrop{ctx->seed_scratch, (uint32_t)site, p};
-}
-}  // namespace
-
-extern "C" int svg_op_dropout_mask(svg_ctx* ctx, uint64_t seed, int site, float p, float* out, int64_t n, void* stream) {
-  try {
-    SVG_CHECK(ctx && out && n >= 0, "svg_op_dropout_mask: bad argument");
-    xf_drop_mask(op_drop(ctx, "svg_op_dropout_mask", seed, site, p, (hipStream_t)stream), out, n, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
-}
-
-// ---- the training kernels one by one (test hooks: each is its launcher and nothing else) ------------------------------------------
-extern "C" int svg_op_xf_gemm_tn(svg_ctx* ctx, const float* dY, int ldy, const float* X, int ldx, float* dW, float* db, int M, int N, int K,
-                                 int accumulate, void* stream) {
-  try {
-    SVG_CHECK(ctx && dY && X && dW, "svg_op_xf_gemm_tn: null argument");
-    xf_gemm_tn(dY, ldy, X, ldx, dW, db, M, N, K, accumulate, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
-}
-
-extern "C" int svg_op_xf_gemm_nn(svg_ctx* ctx, const float* dY, int ldy, const float* W, float* out, int M, int N, int K, const float* gate,
-                                 float gate_scale, const float* add, int* splits, void* stream) {
-  try {
-    SVG_CHECK(ctx && dY && W && out, "svg_op_xf_gemm_nn: null argument");
-    SVG_CHECK(M > 0 && N > 0 && K > 0, "svg_op_xf_gemm_nn: empty problem %d x %d x %d", M, N, K);
-    run_planned(ctx, [&]() {
-      float* slabs = ctx->arena.get<float>(xf_gemm_nn_slab_floats(M, N, K));
-      if (SVG_LAUNCHING(ctx)) xf_gemm_nn(dY, ldy, W, slabs, out, M, N, K, gate, gate_scale, add, (hipStream_t)stream);
-    });
-    if (splits) *splits = xf_gemm_nn_splits(N, K);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
-}
-
-extern "C" int svg_op_xf_relu_drop(svg_ctx* ctx, const float* h, float* r, int64_t n, uint64_t seed, int site, float p, void* stream) {
-  try {
-    SVG_CHECK(ctx && h && r && n >= 0, "svg_op_xf_relu_drop: bad argument");
-    xf_relu_drop(h, r, n, op_drop(ctx, "svg_op_xf_relu_drop", seed, site, p, (hipStream_t)stream), (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
-}
-
-extern "C" int svg_op_xf_add_ln_train(svg_ctx* ctx, const float* x, const float* r, uint64_t seed, int site, float p, const float* gamma,
-                                      const float* beta, float* y, float* xhat, float* rstd, int M, int d, float eps, void* stream) {
-  try {
-    SVG_CHECK(ctx && x && gamma && beta && y && xhat && rstd, "svg_op_xf_add_ln_train: null argument");
-    xf_add_ln_train(x, r, op_drop(ctx, "svg_op_xf_add_ln_train", seed, site, p, (hipStream_t)stream), gamma, beta, y, xhat, rstd, M, d, eps,
-                    (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
-}
-
-extern "C" int svg_op_xf_ln_bwd(svg_ctx* ctx, const float* dy, const float* xhat, const float* rstd, const float* gamma, float* dz, float* dz_drop,
-                                uint64_t seed, int site, float p, float* dgamma, float* dbeta, int M, int d, int accumulate, void* stream) {
-  try {
-    SVG_CHECK(ctx && dy && xhat && rstd && gamma && dz && dgamma && dbeta, "svg_op_xf_ln_bwd: null argument");
-    xf_ln_bwd(dy, xhat, rstd, gamma, dz, dz_drop, op_drop(ctx, "svg_op_xf_ln_bwd", seed, site, p, (hipStream_t)stream), dgamma, dbeta, M, d,
-              accumulate, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
-}
-
-extern "C" int svg_op_xf_attention_train(svg_ctx* ctx, const float* q, int ldq, const float* k, const float* v, int ldk, const float* mask,
-                                         float* o, float* P, int Tq, int Tk, int B, int heads, int hd, uint64_t seed, int site, float p,
-                                         void* stream) {
-  try {
-    SVG_CHECK(ctx && q && k && v && o && P, "svg_op_xf_attention_train: null argument");
-    xf_attention_train(q, ldq, k, v, ldk, mask, o, P, Tq, Tk, B, heads, hd,
-                       op_drop(ctx, "svg_op_xf_attention_train", seed, site, p, (hipStream_t)stream), (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
-}
-
-extern "C" int svg_op_xf_attention_bwd(svg_ctx* ctx, const float* dout, const float* q, int ldq, const float* k, const float* v, int ldk,
-                                       const float* P, float* dq, int lddq, float* dk, float* dv, int lddk, int Tq, int Tk, int B, int heads,
-                                       int hd, uint64_t seed, int site, float p, void* stream) {
-  try {
-    SVG_CHECK(ctx && dout && q && k && v && P && dq && dk && dv, "svg_op_xf_attention_bwd: null argument");
-    xf_attention_bwd(dout, q, ldq, k, v, ldk, P, dq, lddq, dk, dv, lddk, Tq, Tk, B, heads, hd,
-                     op_drop(ctx, "svg_op_xf_attention_bwd", seed, site, p, (hipStream_t)stream), (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
-}
-
-extern "C" int svg_op_xf_embed_post_train(svg_ctx* ctx, const float* emb, const float* pe, const int32_t* pe_row, const float* text, int d_txt,
-                                          float* y, int B, int T, int d, float scale, uint64_t seed, int site, float p, void* stream) {
-  try {
-    SVG_CHECK(ctx && emb && pe && y, "svg_op_xf_embed_post_train: null argument");
-    xf_embed_post_train(emb, pe, pe_row, text, d_txt, y, B, T, d, scale,
-                        op_drop(ctx, "svg_op_xf_embed_post_train", seed, site, p, (hipStream_t)stream), (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
-}
-
-extern "C" int svg_op_xf_embed_post_bwd(svg_ctx* ctx, const float* dy, float* de, int B, int T, int d, int d_img, float scale, uint64_t seed,
-                                        int site, float p, void* stream) {
-  try {
-    SVG_CHECK(ctx && dy && de, "svg_op_xf_embed_post_bwd: null argument");
-    xf_embed_post_bwd(dy, de, B, T, d, d_img, scale, op_drop(ctx, "svg_op_xf_embed_post_bwd", seed, site, p, (hipStream_t)stream),
-                      (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
-}
-
-extern "C" int svg_op_xf_criterion(svg_ctx* ctx, const float* pred, const float* expected, float* dpred, float* losses, int Tt, int B, int D,
-                                   int t0, int fh, int fw, float w_mse, float w_l1, float w_gdl, float alpha, float w_nce, float temperature,
-                                   void* stream) {
-  try {
-    SVG_CHECK(ctx && pred && expected && dpred && losses, "svg_op_xf_criterion: null argument");
-    SVG_CHECK(Tt > 0 && B > 0, "svg_op_xf_criterion: empty problem (%d x %d rows)", Tt, B);
-    float h_losses[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    run_planned(ctx, [&]() {
-      float* part = ctx->arena.get<float>((int64_t)Tt * B * 3);          // the per-row partial sums and the device copy of the losses
-      float* part2 = ctx->arena.get<float>((int64_t)Tt * B);
-      float* d_losses = ctx->arena.get<float>(5);
-      if (!SVG_LAUNCHING(ctx)) return;
-      xf_criterion(pred, expected, dpred, part, part2, d_losses, Tt, B, D, t0, fh, fw, w_mse, w_l1, w_gdl, alpha, w_nce, temperature,
-                   (hipStream_t)stream);
-      HIP_OK(hipMemcpyAsync(h_losses, d_losses, sizeof(h_losses), hipMemcpyDeviceToHost, (hipStream_t)stream));
-      HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-    });
-    for (int i = 0; i < 5; ++i) losses[i] = h_losses[i];                 // losses: host memory
     return 0;
   } catch (const std::exception& e) { return svg_fail(ctx, e); }
 }

@@ -83,6 +83,34 @@ static void transformer(int text_dim, int dm = 32, int d_lat = 64, int ffn = 204
     }
   }
   OK(svg_transformer_loss(ctx, &tc, src.data(), tgt.data(), tgt.data(), text_dim ? txt.data() : nullptr, B, Ts, Tt, nullptr, 0, losses, nullptr));
+  // the plans of the training state: a second plan and owned graph beside the first (accumulate), the optional staging slot (mask),
+  // a second shape signature and the replay of the first one's plan, the forward-only pass, a refused call and a good one after it
+  const float* text = text_dim ? txt.data() : nullptr;
+  void* const st = (void*)0x10;
+  auto mask = buf((size_t)Tt * Tt, 0.f);
+  OK(svg_transformer_loss(ctx, &tc, src.data(), tgt.data(), tgt.data(), text, B, Ts, Tt, nullptr, SVG_BACKWARD_ACCUMULATE, losses, st));
+  OK(svg_transformer_loss(ctx, &tc, src.data(), tgt.data(), tgt.data(), text, B, Ts, Tt, mask.data(), 1, losses, st));
+  OK(svg_transformer_loss(ctx, &tc, src.data(), tgt.data(), tgt.data(), text, 2, Ts, Tt, nullptr, 1, losses, st));
+  OK(svg_transformer_loss(ctx, &tc, src.data(), tgt.data(), tgt.data(), text, B, Ts, Tt, nullptr, 1, losses, st));
+  auto pred = buf((size_t)Tt * B * d_lat);
+  OK(svg_transformer_forward_train(ctx, src.data(), tgt.data(), text, B, Ts, Tt, nullptr, 0.1f, 5, pred.data(), st));
+  svg_train_cfg bad = tc;
+  bad.frames_to_predict = Tt + 1;
+  bad.w_l1 = 0.5f;                                 // a signature no plan exists for yet: the refused call must leave none behind
+  EXPECT_ERR(svg_transformer_loss(ctx, &bad, src.data(), tgt.data(), tgt.data(), text, B, Ts, Tt, nullptr, 1, losses, st));
+  bad.frames_to_predict = tc.frames_to_predict;
+  OK(svg_transformer_loss(ctx, &bad, src.data(), tgt.data(), tgt.data(), text, B, Ts, Tt, nullptr, 1, losses, st));
+  // averaged weights, the clipped decoupled step with a norm read-back, and putting state back
+  OK(svg_transformer_ema_configure(ctx, 0.9f));
+  svg_optim_cfg oc = {1e-3f, 0.9f, 0.999f, 1e-8f, /*weight_decay*/ 0.01f, /*decoupled*/ 1, /*max_grad_norm*/ 1.f, /*grad_scale*/ 0.5f};
+  double norm = 0.0;
+  OK(svg_transformer_optim_step(ctx, &oc, &norm, st));
+  auto mom = buf((size_t)d_lat * d);
+  OK(svg_transformer_set_tensor(ctx, SVG_TENSOR_EXP_AVG, "out.weight", mom.data(), (int64_t)mom.size(), nullptr));
+  int64_t steps = 0;
+  OK(svg_transformer_set_optim_step_count(ctx, 7));
+  OK(svg_transformer_optim_step_count(ctx, &steps));
+  if (steps != 7) { fprintf(stderr, "optimizer step count %lld after setting 7\n", (long long)steps); exit(5); }
   auto w = buf((size_t)d_lat * d);
   OK(svg_transformer_tensor(ctx, SVG_TENSOR_GRAD, "out.weight", w.data(), (int64_t)w.size(), nullptr));
   EXPECT_ERR(svg_transformer_tensor(ctx, SVG_TENSOR_PARAM, "no.such.weight", w.data(), 1, nullptr));
