@@ -91,9 +91,8 @@ void ClipTextModel::forward(svg_ctx* ctx, const int32_t* ids, int B, int T, floa
 }
 
 extern "C" int svg_clip_text_forward(svg_ctx* ctx, const int32_t* input_ids, int B, int T, float* out, void* stream) {
-  try {
-    SVG_CHECK(ctx && ctx->clip, "clip: model not configured");
-    ctx->clip->forward(ctx, input_ids, B, T, out, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->clip(), "clip: model not configured");
+    ctx->clip()->forward(ctx, input_ids, B, T, out, (hipStream_t)stream);
+  });
 }

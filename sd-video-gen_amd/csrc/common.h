@@ -10,6 +10,7 @@
 #include <cstring>
 #include <cmath>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <shared_mutex>
 #include <utility>
@@ -130,15 +131,17 @@ struct svg_ctx {
   std::unordered_map<std::string, ProfEntry> prof_shapes;
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
-  // models (opaque here; defined in their own translation units)
-  struct XfModel* xf = nullptr;
-  struct VaeIface* vae = nullptr;     // sd_bf16::VaeModel or sd_f16::VaeModel (configure key f16=1)
-  struct UnetIface* unet = nullptr;
-  struct ClipTextModel* clip = nullptr;
-  struct MiniLmModel* minilm = nullptr;
-  struct I3dModel* i3d = nullptr;
-  static constexpr int kCtxSlot = 6;                 // owned[] index of allocations that belong to the context itself
-  std::vector<void*> owned[7];   // device allocations per model id (kCtxSlot = context) freed at reconfigure / destroy
+  // models: one owning slot per SVG_* model id, empty until the model is configured or handed its first weight.  Model and the six
+  // types are defined in models.h, and so are the accessors: each is the typed view of its slot, there is no second pointer to a model
+  static constexpr int kCtxSlot = 6;                 // number of model ids = owned[] index of allocations that belong to the context itself
+  std::unique_ptr<struct Model> models[kCtxSlot];
+  struct XfModel* xf() const;
+  struct VaeIface* vae() const;       // sd_bf16::VaeModel or sd_f16::VaeModel (configure key f16=1)
+  struct UnetIface* unet() const;
+  struct ClipTextModel* clip() const;
+  struct MiniLmModel* minilm() const;
+  struct I3dModel* i3d() const;
+  std::vector<void*> owned[kCtxSlot + 1];   // device allocations per model id (kCtxSlot = context) freed at reconfigure / destroy
   int cur_model = kCtxSlot;
   uint64_t* seed_scratch = nullptr;   // device word for svg_op_dropout_mask
   // Workspace growth never frees and never synchronises: the outgrown block may still be read by this context's queued kernels and
@@ -218,6 +221,15 @@ struct ProfScope {
 
 // C-ABI failure path: records the message on the context (or process-wide when there is none) and returns the code
 int svg_fail(svg_ctx* ctx, const std::exception& e);
+// THE exception boundary of the C ABI.  An exception that leaves an extern "C" function is undefined behaviour, so every entry point
+// that can throw runs its body through this: 0, or the code svg_fail() gives the std::exception that ended the body.
+template <class Body>
+int svg_guard(svg_ctx* ctx, Body&& body) {
+  try {
+    body();
+    return 0;
+  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+}
 
 // Launch guard: in arena-dry mode nothing is launched.
 #define SVG_LAUNCHING(ctx) (!(ctx)->arena.dry)

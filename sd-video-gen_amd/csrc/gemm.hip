@@ -18,11 +18,6 @@
 
 namespace SDNS {
 
-// the other families' launchers (conv_halo.hip, gemm_ws.hip, gemm_pp.hip): bn = the plan's column tile
-void launch_conv_halo(const GemmArgs& g, int bn, dim3 grid, hipStream_t s);
-void launch_gemm_ws(svg_ctx* ctx, const GemmArgs& g, int group_cols, hipStream_t s);
-void launch_gemm_pp(const GemmArgs& g, int bn, hipStream_t s);
-
 namespace {
 
 // GEGLU: h and gate are 4 consecutive packed columns nh.. / nh+16..; output column oc..oc+3

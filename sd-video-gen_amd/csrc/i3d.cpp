@@ -5,26 +5,6 @@
 #include "../../include/svg_hip.h"
 #include <cmath>
 
-struct Conv3dArgs {
-  const float* x; int B, T, H, W, Cin;
-  const float* w; const float* bias;
-  float* y; int To, Ho, Wo, Cout, ldc, coff;
-  int kt, kh, kw, st, sh, sw, pt, ph, pw;
-  int relu;
-};
-void conv3d_launch(const Conv3dArgs& a, hipStream_t s);
-void pack_conv3d(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, const float* cbias, float* wout,
-                 float* bout, int Cout, int Cin, int Cin_pad, int taps, float eps, hipStream_t s);
-void maxpool3d_same(const float* x, float* y, int B, int T, int H, int W, int C, int To, int Ho, int Wo, const int k[3], const int st[3],
-                    const int pf[3], hipStream_t s);
-void avgpool_thw(const float* x, float* y, int B, int T, int HW, int C, int kt, hipStream_t s);
-void time_mean(const float* x, float* y, int B, int To, int C, hipStream_t s);
-void ncthw_to_nthwc(const float* x, float* y, int B, int C, int T, int H, int W, int Cp, hipStream_t s);
-void fvd_preprocess(const uint8_t* v, float* out, int B, int T, int H, int W, int res, hipStream_t s);
-void fd_moments(const float* x, int n, int d, double* mean, double* cov, hipStream_t s);
-void sym_eig(double* A, double* V, int d, double* cs, hipStream_t s);
-void frechet_distance(const float* x1, int n1, const float* x2, int n2, int d, double* ws, double* out, hipStream_t s);
-
 namespace {
 struct MixedCfg { const char* name; int cin; int oc[6]; };
 const MixedCfg kMixed[] = {{"Mixed_3b", 192, {64, 96, 128, 16, 32, 32}},   {"Mixed_3c", 256, {128, 128, 192, 32, 96, 64}},
@@ -175,30 +155,27 @@ void I3dModel::forward(svg_ctx* ctx, const float* x_ncthw, const uint8_t* video_
 
 extern "C" {
 int svg_i3d_forward(svg_ctx* ctx, const float* x, int B, int T, int H, int W, float* logits, void* stream) {
-  try {
-    SVG_CHECK(ctx && ctx->i3d, "i3d: model not configured");
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->i3d(), "i3d: model not configured");
     SVG_CHECK(x && logits, "i3d: null argument");
-    ctx->i3d->forward(ctx, x, nullptr, B, T, H, W, logits, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+    ctx->i3d()->forward(ctx, x, nullptr, B, T, H, W, logits, (hipStream_t)stream);
+  });
 }
 int svg_fvd_logits(svg_ctx* ctx, const uint8_t* videos, int B, int T, int H, int W, float* logits, void* stream) {
-  try {
-    SVG_CHECK(ctx && ctx->i3d, "i3d: model not configured");
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->i3d(), "i3d: model not configured");
     SVG_CHECK(videos && logits, "fvd_logits: null argument");
-    ctx->i3d->forward(ctx, nullptr, videos, B, T, H, W, logits, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+    ctx->i3d()->forward(ctx, nullptr, videos, B, T, H, W, logits, (hipStream_t)stream);
+  });
 }
 int svg_fvd_preprocess(svg_ctx* ctx, const uint8_t* videos, int B, int T, int H, int W, float* out, void* stream) {
-  try {
+  return svg_guard(ctx, [&] {
     SVG_CHECK(ctx && videos && out && B >= 1 && T >= 1 && H >= 1 && W >= 1, "fvd_preprocess: bad arguments");
     fvd_preprocess(videos, out, B, T, H, W, 224, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 int svg_frechet_distance(svg_ctx* ctx, const float* x1, int n1, const float* x2, int n2, int d, double* out_host, void* stream) {
-  try {
+  return svg_guard(ctx, [&] {
     SVG_CHECK(ctx && x1 && x2 && out_host, "frechet_distance: null argument");
     SVG_CHECK(n1 >= 2 && n2 >= 2 && d >= 2 && d % 2 == 0 && d <= 2048, "frechet_distance: n1=%d n2=%d d=%d (>= 2 samples each, even d <= 2048)", n1, n2, d);
     hipStream_t s = (hipStream_t)stream;
@@ -210,11 +187,10 @@ int svg_frechet_distance(svg_ctx* ctx, const float* x1, int n1, const float* x2,
     });
     HIP_OK(hipMemcpyAsync(out_host, out_dev, sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 int svg_frame_metrics(svg_ctx* ctx, const uint8_t* a, const uint8_t* b, int N, int H, int W, int64_t* sse, double* ssim, float* ssim_map, void* stream) {
-  try {
+  return svg_guard(ctx, [&] {
     SVG_CHECK(ctx && a && b && sse && ssim, "frame_metrics: null argument");
     SVG_CHECK(N >= 1 && H >= 11 && W >= 11, "frame_metrics: N=%d H=%d W=%d (at least one image, at least the 11 x 11 window)", N, H, W);
     SVG_CHECK(H <= 16384 && W <= 16384 && (int64_t)N * frame_metrics_tiles(H, W) < ((int64_t)1 << 31),
@@ -225,14 +201,13 @@ int svg_frame_metrics(svg_ctx* ctx, const uint8_t* a, const uint8_t* b, int N, i
       uint32_t* part_sse = ctx->arena.get<uint32_t>(parts);
       if (SVG_LAUNCHING(ctx)) frame_metrics(a, b, N, H, W, part_ssim, part_sse, sse, ssim, ssim_map, (hipStream_t)stream);
     });
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 
 // ---- the kernels one by one (test hooks: each is the launcher the model calls; sizes and pads come from same_pad above) ----------------
 int svg_op_conv3d(svg_ctx* ctx, const float* x, int B, int T, int H, int W, int Cin_pad, const float* w, const float* bias, float* y, int64_t y_elems,
                   int Cout, int ldc, int coff, const int* k, const int* stride, int relu, int* out_thw, void* stream) {
-  try {
+  return svg_guard(ctx, [&] {
     SVG_CHECK(ctx && x && w && y && k && stride && out_thw, "svg_op_conv3d: null argument");
     SVG_CHECK(B >= 1 && T >= 1 && H >= 1 && W >= 1 && Cin_pad >= 4 && Cin_pad % 4 == 0, "svg_op_conv3d: input (%d,%d,%d,%d,%d) (channels: a multiple of 4)", B, T,
               H, W, Cin_pad);
@@ -247,22 +222,20 @@ int svg_op_conv3d(svg_ctx* ctx, const float* x, int B, int T, int H, int W, int 
     Conv3dArgs a{x, B, T, H, W, Cin_pad, w, bias, y, To, Ho, Wo, Cout, ldc, coff, k[0], k[1], k[2], stride[0], stride[1], stride[2], pt, ph, pw, relu ? 1 : 0};
     conv3d_launch(a, (hipStream_t)stream);
     out_thw[0] = To; out_thw[1] = Ho; out_thw[2] = Wo;
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 int svg_op_pack_conv3d(svg_ctx* ctx, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, const float* cbias,
                        float* wout, float* bout, int Cout, int Cin, int Cin_pad, int taps, float eps, void* stream) {
-  try {
+  return svg_guard(ctx, [&] {
     SVG_CHECK(ctx && w && wout && bout, "svg_op_pack_conv3d: null argument");
     SVG_CHECK(!gamma || (beta && mean && var && !cbias), "svg_op_pack_conv3d: BatchNorm takes gamma, beta, mean and var, and no conv bias");
     SVG_CHECK(Cout >= 1 && Cin >= 1 && Cin_pad >= Cin && taps >= 1, "svg_op_pack_conv3d: Cout %d Cin %d (stored %d) taps %d", Cout, Cin, Cin_pad, taps);
     pack_conv3d(w, gamma, beta, mean, var, cbias, wout, bout, Cout, Cin, Cin_pad, taps, eps, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 int svg_op_maxpool3d_same(svg_ctx* ctx, const float* x, float* y, int64_t y_elems, int B, int T, int H, int W, int C, const int* k, const int* stride,
                           int* out_thw, void* stream) {
-  try {
+  return svg_guard(ctx, [&] {
     SVG_CHECK(ctx && x && y && k && stride && out_thw, "svg_op_maxpool3d_same: null argument");
     SVG_CHECK(B >= 1 && T >= 1 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0, "svg_op_maxpool3d_same: input (%d,%d,%d,%d,%d) (channels: a multiple of 4)", B, T, H, W, C);
     for (int i = 0; i < 3; ++i) SVG_CHECK(k[i] >= 1 && stride[i] >= 1, "svg_op_maxpool3d_same: kernel %d / stride %d on axis %d", k[i], stride[i], i);
@@ -274,41 +247,36 @@ int svg_op_maxpool3d_same(svg_ctx* ctx, const float* x, float* y, int64_t y_elem
               B, o[0], o[1], o[2], C, (long long)y_elems);
     maxpool3d_same(x, y, B, T, H, W, C, o[0], o[1], o[2], k, stride, pf, (hipStream_t)stream);
     for (int i = 0; i < 3; ++i) out_thw[i] = o[i];
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 int svg_op_avgpool_thw(svg_ctx* ctx, const float* x, float* y, int B, int T, int HW, int C, int kt, void* stream) {
-  try {
+  return svg_guard(ctx, [&] {
     SVG_CHECK(ctx && x && y && B >= 1 && HW >= 1 && C >= 1 && kt >= 1 && T >= kt, "svg_op_avgpool_thw: bad arguments (B %d T %d HW %d C %d kt %d)", B, T, HW, C, kt);
     avgpool_thw(x, y, B, T, HW, C, kt, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 int svg_op_time_mean(svg_ctx* ctx, const float* x, float* y, int B, int To, int C, void* stream) {
-  try {
+  return svg_guard(ctx, [&] {
     SVG_CHECK(ctx && x && y && B >= 1 && To >= 1 && C >= 1, "svg_op_time_mean: bad arguments (B %d To %d C %d)", B, To, C);
     time_mean(x, y, B, To, C, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 int svg_op_ncthw_to_nthwc(svg_ctx* ctx, const float* x, float* y, int B, int C, int T, int H, int W, int Cp, void* stream) {
-  try {
+  return svg_guard(ctx, [&] {
     SVG_CHECK(ctx && x && y && B >= 1 && C >= 1 && T >= 1 && H >= 1 && W >= 1 && Cp >= C, "svg_op_ncthw_to_nthwc: bad arguments (%d,%d,%d,%d,%d) -> %d channels", B,
               C, T, H, W, Cp);
     ncthw_to_nthwc(x, y, B, C, T, H, W, Cp, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 int svg_op_fd_moments(svg_ctx* ctx, const float* x, int n, int d, double* mean, double* cov, void* stream) {
-  try {
+  return svg_guard(ctx, [&] {
     SVG_CHECK(ctx && x && mean && cov, "svg_op_fd_moments: null argument");
     SVG_CHECK(n >= 2 && d >= 2 && d % 2 == 0 && d <= 2048, "svg_op_fd_moments: n=%d d=%d (>= 2 samples, even d <= 2048)", n, d);
     fd_moments(x, n, d, mean, cov, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 int svg_op_sym_eig(svg_ctx* ctx, const double* A, int d, double* eig, double* V, void* stream) {
-  try {
+  return svg_guard(ctx, [&] {
     SVG_CHECK(ctx && A && eig && V, "svg_op_sym_eig: null argument");
     SVG_CHECK(d >= 2 && d % 2 == 0 && d <= 2048, "svg_op_sym_eig: d=%d (even, 2 .. 2048)", d);
     hipStream_t s = (hipStream_t)stream;
@@ -320,7 +288,6 @@ int svg_op_sym_eig(svg_ctx* ctx, const double* A, int d, double* eig, double* V,
         HIP_OK(hipMemcpy2DAsync(eig, sizeof(double), wk, (size_t)(d + 1) * sizeof(double), sizeof(double), d, hipMemcpyDeviceToDevice, s));
       }
     });
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 }

@@ -15,15 +15,6 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-struct Conv3dArgs {
-  const float* x; int B, T, H, W, Cin;         // input (B,T,H,W,Cin), Cin as stored (multiple of 4)
-  const float* w;                              // [Cout][kt][kh][kw][Cin]
-  const float* bias;                           // [Cout]
-  float* y; int To, Ho, Wo, Cout, ldc, coff;   // output (B,To,Ho,Wo,ldc), channels coff .. coff + Cout
-  int kt, kh, kw, st, sh, sw, pt, ph, pw;      // kernel, stride, front padding
-  int relu;
-};
-
 namespace {
 
 template <int CK>     // channels per K chunk: 8 (Cin % 8 == 0) or 4 (the 3-channel input padded to 4)

@@ -99,6 +99,10 @@ GemmPlan gemm_plan(const GemmArgs& g);
 // gn_part / ln_part set only where the plan emits.  The short form plans and launches a problem that asks for no statistics.
 void gemm_auto(svg_ctx* ctx, GemmArgs g, const GemmPlan& plan, hipStream_t s, int prof_kind);
 void gemm_auto(svg_ctx* ctx, GemmArgs g, hipStream_t s, int prof_kind);
+// the launchers gemm_auto hands a planned problem to (conv_halo.hip, gemm_ws.hip, gemm_pp.hip): bn = the plan's column tile
+void launch_conv_halo(const GemmArgs& g, int bn, dim3 grid, hipStream_t s);
+void launch_gemm_ws(svg_ctx* ctx, const GemmArgs& g, int group_cols, hipStream_t s);
+void launch_gemm_pp(const GemmArgs& g, int bn, hipStream_t s);
 // per-device kernel attributes (dynamic LDS limits) of every instantiation; called by svg_create after hipSetDevice
 void gemm_init_device();
 void gemm_pp_init_device();
@@ -360,3 +364,25 @@ void xf_attention(const float* q, int ldq, const float* k, const float* v, int l
 int64_t frame_metrics_tiles(int H, int W);
 void frame_metrics(const uint8_t* a, const uint8_t* b, int N, int H, int W, double* part_ssim, uint32_t* part_sse, int64_t* sse, double* ssim,
                    float* ssim_map, hipStream_t s);
+
+// ---- I3D / Fréchet distance (i3d_kernels.hip): f32, channels-last (N,T,H,W,C) activations --------------------------------
+struct Conv3dArgs {                            // a kernel argument by value: the graph (i3d.cpp) and the kernel see this one definition
+  const float* x; int B, T, H, W, Cin;         // input (B,T,H,W,Cin), Cin as stored (multiple of 4)
+  const float* w;                              // [Cout][kt][kh][kw][Cin]
+  const float* bias;                           // [Cout]
+  float* y; int To, Ho, Wo, Cout, ldc, coff;   // output (B,To,Ho,Wo,ldc), channels coff .. coff + Cout
+  int kt, kh, kw, st, sh, sw, pt, ph, pw;      // kernel, stride, front padding
+  int relu;
+};
+void conv3d_launch(const Conv3dArgs& a, hipStream_t s);
+void pack_conv3d(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, const float* cbias, float* wout,
+                 float* bout, int Cout, int Cin, int Cin_pad, int taps, float eps, hipStream_t s);
+void maxpool3d_same(const float* x, float* y, int B, int T, int H, int W, int C, int To, int Ho, int Wo, const int k[3], const int st[3],
+                    const int pf[3], hipStream_t s);
+void avgpool_thw(const float* x, float* y, int B, int T, int HW, int C, int kt, hipStream_t s);
+void time_mean(const float* x, float* y, int B, int To, int C, hipStream_t s);
+void ncthw_to_nthwc(const float* x, float* y, int B, int C, int T, int H, int W, int Cp, hipStream_t s);
+void fvd_preprocess(const uint8_t* v, float* out, int B, int T, int H, int W, int res, hipStream_t s);
+void fd_moments(const float* x, int n, int d, double* mean, double* cov, hipStream_t s);
+void sym_eig(double* A, double* V, int d, double* cs, hipStream_t s);
+void frechet_distance(const float* x1, int n1, const float* x2, int n2, int d, double* ws, double* out, hipStream_t s);

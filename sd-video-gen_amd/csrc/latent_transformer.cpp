@@ -176,31 +176,28 @@ void XfModel::forward(svg_ctx* ctx, const float* src, const float* tgt, int B, i
 
 extern "C" int svg_transformer_forward_text(svg_ctx* ctx, const float* src, const float* tgt, const float* text, int B, int Ts, int Tt,
                                             const float* mask, const int32_t* pe_row, float* out, void* stream) {
-  try {
-    SVG_CHECK(ctx && ctx->xf, "transformer: model not configured");
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->xf(), "transformer: model not configured");
     xf_walk_check(ctx);
-    ctx->xf->forward(ctx, src, tgt, B, Ts, Tt, mask, pe_row, out, (hipStream_t)stream, text);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+    ctx->xf()->forward(ctx, src, tgt, B, Ts, Tt, mask, pe_row, out, (hipStream_t)stream, text);
+  });
 }
 
 extern "C" int svg_transformer_forward_padded(svg_ctx* ctx, const float* src, const float* tgt, const float* text, int B, int Ts, int Tt,
                                               const float* mask, const float* src_pad, const float* tgt_pad, const int32_t* pe_row, float* out,
                                               void* stream) {
-  try {
-    SVG_CHECK(ctx && ctx->xf, "transformer: model not configured");
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->xf(), "transformer: model not configured");
     xf_walk_check(ctx);
-    ctx->xf->forward(ctx, src, tgt, B, Ts, Tt, mask, pe_row, out, (hipStream_t)stream, text, src_pad, tgt_pad);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+    ctx->xf()->forward(ctx, src, tgt, B, Ts, Tt, mask, pe_row, out, (hipStream_t)stream, text, src_pad, tgt_pad);
+  });
 }
 
 extern "C" int svg_transformer_forward(svg_ctx* ctx, const float* src, const float* tgt, int B, int Ts, int Tt, const float* mask,
                                        const int32_t* pe_row, float* out, void* stream) {
-  try {
-    SVG_CHECK(ctx && ctx->xf, "transformer: model not configured");
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->xf(), "transformer: model not configured");
     xf_walk_check(ctx);
-    ctx->xf->forward(ctx, src, tgt, B, Ts, Tt, mask, pe_row, out, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+    ctx->xf()->forward(ctx, src, tgt, B, Ts, Tt, mask, pe_row, out, (hipStream_t)stream);
+  });
 }

@@ -101,10 +101,9 @@ void MiniLmModel::encode(svg_ctx* ctx, const int32_t* ids, const int32_t* lens, 
 
 extern "C" int svg_minilm_encode(svg_ctx* ctx, const int32_t* input_ids, const int32_t* lengths, int B, int T, float* out, float* hidden,
                                  void* stream) {
-  try {
-    SVG_CHECK(ctx && ctx->minilm, "minilm: model not configured");
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->minilm(), "minilm: model not configured");
     SVG_CHECK(input_ids && lengths && out, "minilm: null argument");
-    ctx->minilm->encode(ctx, input_ids, lengths, B, T, out, hidden, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+    ctx->minilm()->encode(ctx, input_ids, lengths, B, T, out, hidden, (hipStream_t)stream);
+  });
 }

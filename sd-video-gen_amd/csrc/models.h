@@ -2,6 +2,7 @@
 #pragma once
 #include "kernels.h"
 #include "sampler.h"
+#include "../../include/svg_hip.h"
 #include <algorithm>
 #include <initializer_list>
 #include <memory>
@@ -18,6 +19,20 @@ struct WeightStore {
 };
 
 std::unordered_map<std::string, std::vector<int64_t>> parse_kv(const char* kv);
+
+// What the C ABI's configure / load / finalize dispatch needs of a model: every model type derives from this and sits in its slot of
+// svg_ctx::models.  Device memory is released by explicit calls under DeviceWideScope (ws.clear(), weights_changed(true)), never by
+// the destructor.
+struct Model {
+  WeightStore ws;
+  bool ready = false;                                            // finalize() has packed the weights that are loaded now
+  virtual ~Model() {}
+  virtual const char* dtype() const { return "f32"; }            // storage type as svg_model_dtype reports it
+  virtual void configure(const char* kv) = 0;
+  virtual void finalize(svg_ctx* ctx, int64_t* n_params) = 0;
+  // the weights were replaced or are going away: what was derived from them no longer holds.  locked: the caller holds DeviceWideScope
+  virtual void weights_changed(bool locked) { ready = false; }
+};
 
 // Plans a call twice: a dry pass measures the arena high-water mark, then the real pass launches (in plan mode: the dry pass only).
 template <typename F>
@@ -52,11 +67,9 @@ struct XfTable {
   P emb_w{}, emb_b{}, out_w{}, out_b{}, encn_w{}, encn_b{}, decn_w{}, decn_b{};
 };
 
-struct XfModel {
-  WeightStore ws;
+struct XfModel : Model {
   int d_lat = 0, d_model = 0, heads = 8, enc_layers = 0, dec_layers = 0, ffn = 2048;
   int text_dim = 0;   // > 0: text-conditioned variant (models/transformer_text.py): d_model = DIM_MODEL + text_dim
-  bool ready = false;
   float* pe = nullptr;   // (64, d_model)
   int pe_d = 0;
   int32_t* iota = nullptr;
@@ -95,8 +108,9 @@ struct XfModel {
     f("transformer.encoder.norm.weight", Shape{d}, t.encn_w); f("transformer.encoder.norm.bias", Shape{d}, t.encn_b);
     f("transformer.decoder.norm.weight", Shape{d}, t.decn_w); f("transformer.decoder.norm.bias", Shape{d}, t.decn_b);
   }
-  void configure(const char* kv);
-  void finalize(svg_ctx* ctx, int64_t* n_params);
+  void configure(const char* kv) override;
+  void finalize(svg_ctx* ctx, int64_t* n_params) override;
+  void weights_changed(bool locked) override;   // new weights: a fresh optimizer state
   // src_pad (B,Ts) / tgt_pad (B,Tt): additive key-padding biases (models/transformer.py:64) or null
   void forward(svg_ctx* ctx, const float* src, const float* tgt, int B, int Ts, int Tt, const float* mask,
                const int32_t* pe_row, float* out, hipStream_t s, const float* text = nullptr, const float* src_pad = nullptr,
@@ -105,70 +119,52 @@ struct XfModel {
 
 // ---- CLIP text tower (transformers CLIPTextModel; reference call site utils/sd_utils.py:60,84,91) ---------------------
 // f32 like the reference (the text encoder runs outside autocast), on the latent Transformer's weight-streaming kernels.
-struct ClipTextModel {
-  WeightStore ws;
+struct ClipTextModel : Model {
   int vocab = 49408, d_model = 768, heads = 12, layers = 12, ffn = 3072, max_pos = 77;
-  bool ready = false;
   std::vector<float*> qkv_w, qkv_b;        // per layer: [Wq; Wk; Wv] stacked (3d x d) so the three projections are one stream
-  void configure(const char* kv);
-  void finalize(svg_ctx* ctx, int64_t* n_params);
+  void configure(const char* kv) override;
+  void finalize(svg_ctx* ctx, int64_t* n_params) override;
   // ids (B,T) int32 -> out (B,T,d_model) f32 = last_hidden_state (after final_layer_norm)
   void forward(svg_ctx* ctx, const int32_t* ids, int B, int T, float* out, hipStream_t s);
 };
 
 // ---- MiniLM sentence encoder (SentenceTransformer('all-MiniLM-L6-v2').encode; reference call site models/transformer_text.py:12,82-83)
 // BertModel (6 layers, d 384, 12 heads, ffn 1536) + masked mean pooling + L2 normalisation, f32 on the weight-streaming kernels.
-struct MiniLmModel {
-  WeightStore ws;
+struct MiniLmModel : Model {
   int vocab = 30522, d_model = 384, heads = 12, layers = 6, ffn = 1536, max_pos = 512;
-  bool ready = false;
   std::vector<float*> qkv_w, qkv_b;        // per layer: [Wq; Wk; Wv] stacked
-  void configure(const char* kv);
-  void finalize(svg_ctx* ctx, int64_t* n_params);
+  void configure(const char* kv) override;
+  void finalize(svg_ctx* ctx, int64_t* n_params) override;
   // ids (B,T) int32 ([CLS] ... [SEP] then padding), lens (B) valid tokens per row -> out (B,d_model) unit-norm sentence embeddings;
   // hidden (optional): (B,T,d_model) last_hidden_state
   void encode(svg_ctx* ctx, const int32_t* ids, const int32_t* lens, int B, int T, float* out, float* hidden, hipStream_t s);
 };
 
 // ---- I3D (FVD evaluation: evaluation/pytorch_i3d.py, evaluation/fvd_2.py; f32, channels-last, BatchNorm folded at finalize) ----
-struct I3dModel {
-  WeightStore ws;
+struct I3dModel : Model {
   int num_classes = 400;
-  bool ready = false;
   struct Unit { float* w = nullptr; float* b = nullptr; int cin = 0, cin_pad = 0, cout = 0, k = 1; };
   struct Mixed { Unit b0, b1a, b1b, b2a, b2b, b3b; };
   Unit conv1a, conv2b, conv2c, logits;
   std::vector<Mixed> mixed;
-  void configure(const char* kv);
-  void finalize(svg_ctx* ctx, int64_t* n_params);
+  void configure(const char* kv) override;
+  void finalize(svg_ctx* ctx, int64_t* n_params) override;
   Unit load_unit(svg_ctx* ctx, const std::string& prefix, int cin, int cout, int k, bool bn);
   // x (B,3,T,H,W) f32 in [-1,1] (H = W = 224), or video_u8 (B,T,H,W,3) uint8 (preprocessed inside) -> logits (B,num_classes)
   void forward(svg_ctx* ctx, const float* x_ncthw, const uint8_t* video_u8, int B, int T, int H, int W, float* logits, hipStream_t s);
 };
 
 void xf_train_free(XfModel* m);
-void destroy_models(svg_ctx* ctx);
+void destroy_models(svg_ctx* ctx);   // caller holds DeviceWideScope (svg_destroy)
 
 // ---- Stable-Diffusion networks: one implementation per storage type (namespace sd_bf16 / sd_f16), chosen at configure time ----
-struct VaeIface {
-  WeightStore ws;
-  bool ready = false;
-  virtual ~VaeIface() {}
-  virtual const char* dtype() const = 0;
-  virtual void configure(const char* kv) = 0;
-  virtual void finalize(svg_ctx* ctx, int64_t* n_params) = 0;
+struct VaeIface : Model {
   virtual void encode(svg_ctx* ctx, const uint8_t* img, int N, int srcH, int srcW, int H, int W, const float* eps, float* z_out,
                       float* moments_out, hipStream_t s) = 0;
   virtual void decode(svg_ctx* ctx, const float* z, int N, int h, int w, uint8_t* img_out, int outH, int outW, float* float_out,
                       hipStream_t s) = 0;
 };
-struct UnetIface {
-  WeightStore ws;
-  bool ready = false;
-  virtual ~UnetIface() {}
-  virtual const char* dtype() const = 0;
-  virtual void configure(const char* kv) = 0;
-  virtual void finalize(svg_ctx* ctx, int64_t* n_params) = 0;
+struct UnetIface : Model {
   virtual void forward(svg_ctx* ctx, const float* x, int N, int h, int w, const float* timesteps, const float* ctx_emb, int ctx_len,
                        float* eps_out, hipStream_t s) = 0;
   // the img2img loop under the update rule `sampler` (kSampler* of sampler_plan.h, which also holds every schedule coefficient)
@@ -181,6 +177,14 @@ UnetIface* new_unet_bf16();
 UnetIface* new_unet_f16();
 namespace sd_bf16 { void sd_init_device(); }
 namespace sd_f16 { void sd_init_device(); }
+
+// the typed views of the context's slots: the id -> type pairing that make_model() (capi_models.cpp) creates
+inline XfModel* svg_ctx::xf() const { return static_cast<XfModel*>(models[SVG_TRANSFORMER].get()); }
+inline VaeIface* svg_ctx::vae() const { return static_cast<VaeIface*>(models[SVG_VAE].get()); }
+inline UnetIface* svg_ctx::unet() const { return static_cast<UnetIface*>(models[SVG_UNET].get()); }
+inline ClipTextModel* svg_ctx::clip() const { return static_cast<ClipTextModel*>(models[SVG_CLIP_TEXT].get()); }
+inline MiniLmModel* svg_ctx::minilm() const { return static_cast<MiniLmModel*>(models[SVG_MINILM].get()); }
+inline I3dModel* svg_ctx::i3d() const { return static_cast<I3dModel*>(models[SVG_I3D].get()); }
 
 namespace SDNS {
 

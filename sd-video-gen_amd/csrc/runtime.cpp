@@ -164,12 +164,6 @@ std::unordered_map<std::string, std::vector<int64_t>> parse_kv(const char* kv) {
 }
 
 // ---- C ABI: context ------------------------------------------------------------------------------------
-#define API_BEGIN try {
-#define API_END(ctx)                                   \
-  return 0;                                            \
-  }                                                    \
-  catch (const std::exception& e) { return svg_fail(ctx, e); }
-
 static std::mutex g_env_mu;
 static std::unordered_map<std::string, int64_t> g_env;      // values of the $SVG_* knobs already looked up (absent -> its default)
 
@@ -199,28 +193,27 @@ void svg_env_refresh(void) {
 const char* svg_version(void) { return "svg_hip 0.3 (gfx950, bf16+fp16) src " SVG_SRC_HASH; }
 
 int svg_create(int device_id, svg_ctx** out) {
-  svg_ctx* ctx = nullptr;
-  API_BEGIN
-  SVG_CHECK(out, "svg_create: out is NULL");
-  int n = 0;
-  HIP_OK(hipGetDeviceCount(&n));
-  SVG_CHECK(device_id >= 0 && device_id < n, "svg_create: device %d of %d", device_id, n);
-  HIP_OK(hipSetDevice(device_id));
-  hipDeviceProp_t prop;
-  HIP_OK(hipGetDeviceProperties(&prop, device_id));
-  SVG_CHECK(std::string(prop.gcnArchName).find("gfx950") != std::string::npos,
-            "svg_create: this library is built for gfx950 only, device reports %s", prop.gcnArchName);
-  sd_bf16::sd_init_device();
-  sd_f16::sd_init_device();
-  xf_train_init_device();
-  xformer_init_device();
-  xf_walk_init_device();
-  ctx = new svg_ctx();
-  ctx->device = device_id;
-  ctx->prof_entries.resize(PK_COUNT);
-  for (int i = 0; i < PK_COUNT; ++i) ctx->prof_entries[i].name = kProfNames[i];
-  *out = ctx;
-  API_END((svg_ctx*)nullptr)
+  return svg_guard(nullptr, [&] {
+    SVG_CHECK(out, "svg_create: out is NULL");
+    int n = 0;
+    HIP_OK(hipGetDeviceCount(&n));
+    SVG_CHECK(device_id >= 0 && device_id < n, "svg_create: device %d of %d", device_id, n);
+    HIP_OK(hipSetDevice(device_id));
+    hipDeviceProp_t prop;
+    HIP_OK(hipGetDeviceProperties(&prop, device_id));
+    SVG_CHECK(std::string(prop.gcnArchName).find("gfx950") != std::string::npos,
+              "svg_create: this library is built for gfx950 only, device reports %s", prop.gcnArchName);
+    sd_bf16::sd_init_device();
+    sd_f16::sd_init_device();
+    xf_train_init_device();
+    xformer_init_device();
+    xf_walk_init_device();
+    svg_ctx* ctx = new svg_ctx();
+    ctx->device = device_id;
+    ctx->prof_entries.resize(PK_COUNT);
+    for (int i = 0; i < PK_COUNT; ++i) ctx->prof_entries[i].name = kProfNames[i];
+    *out = ctx;
+  });
 }
 
 void svg_destroy(svg_ctx* ctx) {
@@ -242,32 +235,31 @@ int64_t svg_workspace_growths(svg_ctx* ctx) { return ctx ? ctx->arena_growths : 
 int svg_debug_captures_active(void) { return g_captures_active.load(); }
 
 int svg_reserve_workspace(svg_ctx* ctx, int64_t bytes) {
-  API_BEGIN
-  SVG_CHECK(ctx && bytes >= 0, "svg_reserve_workspace: bad arguments");
-  HIP_OK(hipSetDevice(ctx->device));
-  ctx->ensure_arena(bytes);
-  if (!ctx->arena_retired.empty()) {
-    DeviceWideScope lk;
-    HIP_OK(hipDeviceSynchronize());   // kernels queued on the outgrown blocks
-    ctx->release_retired();
-  }
-  API_END(ctx)
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && bytes >= 0, "svg_reserve_workspace: bad arguments");
+    HIP_OK(hipSetDevice(ctx->device));
+    ctx->ensure_arena(bytes);
+    if (!ctx->arena_retired.empty()) {
+      DeviceWideScope lk;
+      HIP_OK(hipDeviceSynchronize());   // kernels queued on the outgrown blocks
+      ctx->release_retired();
+    }
+  });
 }
 int svg_plan_begin(svg_ctx* ctx) {
-  API_BEGIN
-  SVG_CHECK(ctx, "svg_plan_begin: null context");
-  ctx->plan_only = true;
-  ctx->plan_high = 0;
-  API_END(ctx)
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx, "svg_plan_begin: null context");
+    ctx->plan_only = true;
+    ctx->plan_high = 0;
+  });
 }
 int svg_plan_end(svg_ctx* ctx, int64_t* bytes) {
-  API_BEGIN
-  SVG_CHECK(ctx && ctx->plan_only, "svg_plan_end without svg_plan_begin");
-  ctx->plan_only = false;
-  if (bytes) *bytes = ctx->plan_high;
-  const int rc = svg_reserve_workspace(ctx, ctx->plan_high);
-  if (rc != 0) return rc;
-  API_END(ctx)
+  const int rc = svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->plan_only, "svg_plan_end without svg_plan_begin");
+    ctx->plan_only = false;
+    if (bytes) *bytes = ctx->plan_high;
+  });
+  return rc != 0 ? rc : svg_reserve_workspace(ctx, ctx->plan_high);
 }
 
 int svg_prof_enable(svg_ctx* ctx, int on) {
@@ -281,61 +273,53 @@ static void prof_wait(svg_ctx* ctx) {
   for (size_t i = 0; i < ctx->ev_used; ++i) HIP_OK(hipEventSynchronize(ctx->ev_pool[i]));
 }
 int svg_prof_reset(svg_ctx* ctx) {
-  API_BEGIN
-  prof_wait(ctx);
-  for (auto& e : ctx->prof_entries) { e.calls = 0; e.flops = 0; e.bytes = 0; e.ev.clear(); }
-  ctx->prof_shapes.clear();
-  ctx->ev_used = 0;
-  API_END(ctx)
+  return svg_guard(ctx, [&] {
+    prof_wait(ctx);
+    for (auto& e : ctx->prof_entries) { e.calls = 0; e.flops = 0; e.bytes = 0; e.ev.clear(); }
+    ctx->prof_shapes.clear();
+    ctx->ev_used = 0;
+  });
 }
 int svg_prof_report(svg_ctx* ctx, char* buf, int buflen) {
-  API_BEGIN
-  prof_wait(ctx);
-  std::ostringstream os;
-  for (auto& e : ctx->prof_entries) {
-    if (!e.calls) continue;
-    double ms = 0;
-    for (auto& p : e.ev) {
-      float t = 0;
-      if (hipEventElapsedTime(&t, p.first, p.second) == hipSuccess) ms += t;
+  return svg_guard(ctx, [&] {
+    prof_wait(ctx);
+    std::ostringstream os;
+    for (auto& e : ctx->prof_entries) {
+      if (!e.calls) continue;
+      double ms = 0;
+      for (auto& p : e.ev) {
+        float t = 0;
+        if (hipEventElapsedTime(&t, p.first, p.second) == hipSuccess) ms += t;
+      }
+      os << e.name << " " << e.calls << " " << ms << " " << e.flops << " " << e.bytes << "\n";
     }
-    os << e.name << " " << e.calls << " " << ms << " " << e.flops << " " << e.bytes << "\n";
-  }
-  for (auto& kv : ctx->prof_shapes) {
-    double ms = 0;
-    for (auto& p : kv.second.ev) {
-      float t = 0;
-      if (hipEventElapsedTime(&t, p.first, p.second) == hipSuccess) ms += t;
+    for (auto& kv : ctx->prof_shapes) {
+      double ms = 0;
+      for (auto& p : kv.second.ev) {
+        float t = 0;
+        if (hipEventElapsedTime(&t, p.first, p.second) == hipSuccess) ms += t;
+      }
+      os << kv.first << " " << kv.second.calls << " " << ms << " " << kv.second.flops << " " << kv.second.bytes << "\n";
     }
-    os << kv.first << " " << kv.second.calls << " " << ms << " " << kv.second.flops << " " << kv.second.bytes << "\n";
-  }
-  std::string s = os.str();
-  SVG_CHECK((int)s.size() + 1 <= buflen, "svg_prof_report: buffer too small");
-  memcpy(buf, s.c_str(), s.size() + 1);
-  API_END(ctx)
+    std::string s = os.str();
+    SVG_CHECK((int)s.size() + 1 <= buflen, "svg_prof_report: buffer too small");
+    memcpy(buf, s.c_str(), s.size() + 1);
+  });
 }
 
-// ---- C ABI: operator level (the hooks on 16-bit buffers are in sd_ops.cpp, once per storage type) ----
-int svg_op_xf_gemm(svg_ctx* ctx, const float* X, const float* W, const float* bias, float* Y, int M, int N, int K, int relu_in,
-                   void* stream) {
-  API_BEGIN
-  run_planned(ctx, [&]() { xf_gemm(ctx, X, W, bias, Y, M, N, K, relu_in, (hipStream_t)stream); });
-  API_END(ctx)
-}
-
+// ---- C ABI: operator level (the hooks on 16-bit buffers are in sd_ops.cpp, once per storage type; the Transformer's in xf_ops.cpp) ----
 int svg_resize_bilinear_f32(svg_ctx* ctx, const float* src, int planes, int h, int w, float* dst, int oh, int ow, void* stream) {
-  try {
+  return svg_guard(ctx, [&] {
     SVG_CHECK(ctx && src && dst && planes > 0 && h > 0 && w > 0 && oh > 0 && ow > 0, "svg_resize_bilinear_f32: bad arguments");
     resize_bilinear_f32(src, dst, planes, h, w, oh, ow, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 
 int svg_resize_nearest_u8(svg_ctx* ctx, const uint8_t* src, int N, int sh, int sw, int C, uint8_t* dst, int dh, int dw,
                           void* stream) {
-  API_BEGIN
-  resize_nearest_u8(src, dst, N, sh, sw, C, dh, dw, (hipStream_t)stream);
-  API_END(ctx)
+  return svg_guard(ctx, [&] {
+    resize_nearest_u8(src, dst, N, sh, sw, C, dh, dw, (hipStream_t)stream);
+  });
 }
 
 }  // extern "C"

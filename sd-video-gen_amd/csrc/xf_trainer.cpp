@@ -488,62 +488,63 @@ void xf_train_free(XfModel* m) {
   delete m->train;
   m->train = nullptr;
 }
+void XfModel::weights_changed(bool locked) {
+  if (locked) xf_train_free(this);
+  else if (train) { DeviceWideScope lk; xf_train_free(this); }
+  ready = false;
+}
 
 extern "C" int svg_transformer_loss(svg_ctx* ctx, const svg_train_cfg* cfg, const float* src, const float* tgt, const float* expected,
                                     const float* text, int B, int Ts, int Tt, const float* mask, int backward, float* losses, void* stream) {
-  try {
-    SVG_CHECK(ctx && ctx->xf, "transformer: model not configured");
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->xf(), "transformer: model not configured");
     SVG_CHECK(cfg && src && tgt && expected, "svg_transformer_loss: null argument");
     // 0, 1 or SVG_BACKWARD_ACCUMULATE: the plan (and its captured graph) is keyed on the normalised mode
     const int mode = backward == 0 ? 0 : (backward == SVG_BACKWARD_ACCUMULATE ? SVG_BACKWARD_ACCUMULATE : 1);
-    loss_pass(ctx, ctx->xf, *cfg, Inputs{src, tgt, expected, text, mask}, B, Ts, Tt, mode, losses, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+    loss_pass(ctx, ctx->xf(), *cfg, Inputs{src, tgt, expected, text, mask}, B, Ts, Tt, mode, losses, (hipStream_t)stream);
+  });
 }
 
 extern "C" int svg_transformer_forward_train(svg_ctx* ctx, const float* src, const float* tgt, const float* text, int B, int Ts, int Tt,
                                              const float* mask, float dropout_p, uint64_t seed, float* out, void* stream) {
-  try {
-    SVG_CHECK(ctx && ctx->xf, "transformer: model not configured");
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->xf(), "transformer: model not configured");
     SVG_CHECK(src && tgt && out, "svg_transformer_forward_train: null argument");
     svg_train_cfg cfg{};
     cfg.dropout_p = dropout_p;
     cfg.seed = seed;
-    loss_pass(ctx, ctx->xf, cfg, Inputs{src, tgt, nullptr, text, mask}, B, Ts, Tt, /*train mode*/ 1, nullptr, (hipStream_t)stream, out);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+    loss_pass(ctx, ctx->xf(), cfg, Inputs{src, tgt, nullptr, text, mask}, B, Ts, Tt, /*train mode*/ 1, nullptr, (hipStream_t)stream, out);
+  });
 }
 
 extern "C" int svg_transformer_adam_step(svg_ctx* ctx, float lr, float beta1, float beta2, float eps, void* stream) {
-  try {
-    SVG_CHECK(ctx && ctx->xf && ctx->xf->train, "adam step: no gradients yet (call svg_transformer_loss with backward=1 first)");
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->xf() && ctx->xf()->train, "adam step: no gradients yet (call svg_transformer_loss with backward=1 first)");
     check_adam_hyper("adam step", lr, beta1, beta2, eps);
-    XfTrain* tr = ctx->xf->train;
+    XfTrain* tr = ctx->xf()->train;
     tr->step += 1;
     xf_adam(tr->d_tens, tr->d_chunks, tr->n_chunks, lr, beta1, beta2, eps, tr->step, tr->ema_decay > 0.f ? tr->d_ema : nullptr, tr->ema_decay,
             (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 
 extern "C" int svg_transformer_grad_norm(svg_ctx* ctx, double* out, void* stream) {
-  try {
-    SVG_CHECK(ctx && ctx->xf && out, "svg_transformer_grad_norm: null argument");
-    SVG_CHECK(ctx->xf->train && ctx->xf->train->has_grads, "gradient norm: no gradients yet (call svg_transformer_loss with backward=1 first)");
-    grad_norm_pass(ctx->xf->train, out, (hipStream_t)stream);
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->xf() && out, "svg_transformer_grad_norm: null argument");
+    SVG_CHECK(ctx->xf()->train && ctx->xf()->train->has_grads, "gradient norm: no gradients yet (call svg_transformer_loss with backward=1 first)");
+    grad_norm_pass(ctx->xf()->train, out, (hipStream_t)stream);
+  });
 }
 
 extern "C" int svg_transformer_optim_step(svg_ctx* ctx, const svg_optim_cfg* cfg, double* grad_norm_out, void* stream) {
-  try {
-    SVG_CHECK(ctx && ctx->xf && cfg, "svg_transformer_optim_step: null argument");
-    SVG_CHECK(ctx->xf->train && ctx->xf->train->has_grads, "optimizer step: no gradients yet (call svg_transformer_loss with backward=1 first)");
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->xf() && cfg, "svg_transformer_optim_step: null argument");
+    SVG_CHECK(ctx->xf()->train && ctx->xf()->train->has_grads, "optimizer step: no gradients yet (call svg_transformer_loss with backward=1 first)");
     check_adam_hyper("optimizer step", cfg->lr, cfg->beta1, cfg->beta2, cfg->eps);
     SVG_CHECK(cfg->weight_decay >= 0.f, "optimizer step: weight_decay %g is negative", cfg->weight_decay);
     SVG_CHECK(cfg->max_grad_norm >= 0.f, "optimizer step: max_grad_norm %g is negative", cfg->max_grad_norm);
     SVG_CHECK(cfg->grad_scale > 0.f, "optimizer step: grad_scale %g is not positive", cfg->grad_scale);
-    XfTrain* tr = ctx->xf->train;
+    XfTrain* tr = ctx->xf()->train;
     hipStream_t s = (hipStream_t)stream;
     const bool clip = cfg->max_grad_norm > 0.f;
     double norm = 0.0;
@@ -552,14 +553,13 @@ extern "C" int svg_transformer_optim_step(svg_ctx* ctx, const svg_optim_cfg* cfg
     xf_adamw(tr->d_tens, tr->d_chunks, tr->n_chunks, cfg->lr, cfg->beta1, cfg->beta2, cfg->eps, tr->step, cfg->weight_decay, cfg->decoupled != 0,
              cfg->grad_scale, cfg->max_grad_norm, clip ? tr->d_norm : nullptr, tr->ema_decay > 0.f ? tr->d_ema : nullptr, tr->ema_decay, s);
     if (grad_norm_out) *grad_norm_out = (double)cfg->grad_scale * norm;
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 
 extern "C" int svg_transformer_tensor(svg_ctx* ctx, int kind, const char* name, float* out, int64_t numel, void* stream) {
-  try {
-    SVG_CHECK(ctx && ctx->xf && name && out, "svg_transformer_tensor: null argument");
-    XfModel* m = ctx->xf;
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->xf() && name && out, "svg_transformer_tensor: null argument");
+    XfModel* m = ctx->xf();
     SVG_CHECK(m->ws.has(name), "svg_transformer_tensor: no tensor named %s", name);
     const Weight& w = m->ws.get(name);
     SVG_CHECK(numel == w.numel, "svg_transformer_tensor: %s has %lld elements, caller asked for %lld", name, (long long)w.numel, (long long)numel);
@@ -574,14 +574,13 @@ extern "C" int svg_transformer_tensor(svg_ctx* ctx, int kind, const char* name, 
     }
     HIP_OK(hipMemcpyAsync(out, srcp, numel * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 
 extern "C" int svg_transformer_set_tensor(svg_ctx* ctx, int kind, const char* name, const float* data, int64_t numel, void* stream) {
-  try {
-    SVG_CHECK(ctx && ctx->xf && name && data, "svg_transformer_set_tensor: null argument");
-    XfModel* m = ctx->xf;
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->xf() && name && data, "svg_transformer_set_tensor: null argument");
+    XfModel* m = ctx->xf();
     SVG_CHECK(kind == SVG_TENSOR_EXP_AVG || kind == SVG_TENSOR_EXP_AVG_SQ || kind == SVG_TENSOR_EMA,
               "svg_transformer_set_tensor: kind %d cannot be set (parameters go through svg_load_weight, gradients come from svg_transformer_loss)", kind);
     SVG_CHECK(m->ws.has(name) && strcmp(name, "positional_encoder.pos_encoding") != 0, "svg_transformer_set_tensor: no trained tensor named %s", name);
@@ -590,36 +589,32 @@ extern "C" int svg_transformer_set_tensor(svg_ctx* ctx, int kind, const char* na
     XfTrain* tr = state_for_restore(ctx, m, kind == SVG_TENSOR_EMA);
     HIP_OK(hipMemcpyAsync(slot_ptr(tr->slots.at(name), kind), data, numel * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  });
 }
 
 extern "C" int svg_transformer_optim_step_count(svg_ctx* ctx, int64_t* out) {
-  try {
-    SVG_CHECK(ctx && ctx->xf && out, "svg_transformer_optim_step_count: null argument");
-    *out = ctx->xf->train ? ctx->xf->train->step : 0;
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->xf() && out, "svg_transformer_optim_step_count: null argument");
+    *out = ctx->xf()->train ? ctx->xf()->train->step : 0;
+  });
 }
 
 extern "C" int svg_transformer_set_optim_step_count(svg_ctx* ctx, int64_t step) {
-  try {
-    SVG_CHECK(ctx && ctx->xf, "svg_transformer_set_optim_step_count: model not configured");
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->xf(), "svg_transformer_set_optim_step_count: model not configured");
     SVG_CHECK(step >= 0 && step <= 0x7fffffff, "svg_transformer_set_optim_step_count: step %lld out of range", (long long)step);
-    state_for_restore(ctx, ctx->xf, false)->step = (int)step;
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+    state_for_restore(ctx, ctx->xf(), false)->step = (int)step;
+  });
 }
 
 extern "C" int svg_transformer_ema_configure(svg_ctx* ctx, float decay) {
-  try {
-    SVG_CHECK(ctx && ctx->xf, "svg_transformer_ema_configure: model not configured");
+  return svg_guard(ctx, [&] {
+    SVG_CHECK(ctx && ctx->xf(), "svg_transformer_ema_configure: model not configured");
     SVG_CHECK(decay >= 0.f && decay < 1.f, "svg_transformer_ema_configure: decay %g is outside [0, 1)", decay);
     if (decay == 0.f) {                                   // updates off; the buffers (if any) keep their values
-      if (ctx->xf->train) ctx->xf->train->ema_decay = 0.f;
-      return 0;
+      if (ctx->xf()->train) ctx->xf()->train->ema_decay = 0.f;
+      return;
     }
-    state_for_restore(ctx, ctx->xf, true)->ema_decay = decay;
-    return 0;
-  } catch (const std::exception& e) { return svg_fail(ctx, e); }
+    state_for_restore(ctx, ctx->xf(), true)->ema_decay = decay;
+  });
 }

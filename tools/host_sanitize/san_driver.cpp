@@ -294,6 +294,81 @@ static void ops() {
   for (int mode : {0, 3}) (void)svg_op_conv3x3_mx(ctx, x.data(), w2.data(), b2.data(), nullptr, yb.data(), nullptr, nullptr, 2, 32, 32, 64, 128, mode, nullptr);
 }
 
+// a refused call: its status and (part of) its message, as recorded from the library before the C ABI got its one exception guard
+// and the models their one base; owner = the context the message is left on (nullptr: the process-wide slot)
+#define REFUSED(call, owner, code, text)                                                                                 \
+  do {                                                                                                                   \
+    int rc_ = (call);                                                                                                    \
+    const char* msg_ = svg_last_error(owner);                                                                            \
+    if (rc_ != (code) || !strstr(msg_, text)) { fprintf(stderr, "%s -> %d \"%s\", expected %d \"%s\"\n", #call, rc_, msg_, (int)(code), text); exit(6); } \
+  } while (0)
+
+// The C-ABI boundary with all six models finalised: every slot configured again in turn (each helper finalises and calls its model),
+// weights replaced under a finalised model, ids the library does not know, one refused call per source file of entry points, the
+// process-wide error slot.  Leaves all six slots occupied for svg_destroy.
+static void abi_boundary() {
+  const int64_t one = 1;
+  float f = 0.f;
+  double dv = 0.0;
+  int path[3] = {0, 0, 0};
+  // reconfigure in turn; the SD models bf16 -> fp16 -> bf16
+  transformer(0);
+  vae(0); vae(1);
+  if (strcmp(svg_model_dtype(ctx, SVG_VAE), "fp16") != 0) { fprintf(stderr, "VAE dtype %s after f16=1\n", svg_model_dtype(ctx, SVG_VAE)); exit(7); }
+  vae(0);
+  unet(0, 0); unet(1, 0);
+  if (strcmp(svg_model_dtype(ctx, SVG_UNET), "fp16") != 0) { fprintf(stderr, "UNet dtype %s after f16=1\n", svg_model_dtype(ctx, SVG_UNET)); exit(7); }
+  unet(0, 0);
+  text_towers();
+  i3d_and_fvd();
+  for (int m : {SVG_TRANSFORMER, SVG_CLIP_TEXT, SVG_MINILM, SVG_I3D})
+    if (strcmp(svg_model_dtype(ctx, m), "f32") != 0) { fprintf(stderr, "model %d dtype %s\n", m, svg_model_dtype(ctx, m)); exit(7); }
+  if (strcmp(svg_model_dtype(ctx, SVG_VAE), "bf16") != 0 || strcmp(svg_model_dtype(ctx, SVG_UNET), "bf16") != 0) { fprintf(stderr, "SD dtype after f16=0\n"); exit(7); }
+  // a weight under a finalised model (the Transformer holds optimizer state here): refused until finalised again
+  auto x = buf((size_t)6 * 64), y = buf((size_t)6 * 64);
+  load(SVG_TRANSFORMER, "out.bias", {64}, 0.02f);
+  REFUSED(svg_transformer_forward(ctx, x.data(), x.data(), 1, 6, 6, nullptr, nullptr, y.data(), nullptr), ctx, SVG_ERR_INVALID,
+          "transformer: svg_finalize has not been called");
+  int64_t steps = -1;
+  OK(svg_transformer_optim_step_count(ctx, &steps));
+  if (steps != 0) { fprintf(stderr, "optimizer step count %lld after new weights\n", (long long)steps); exit(5); }
+  OK(svg_finalize(ctx, SVG_TRANSFORMER, nullptr));
+  OK(svg_transformer_forward(ctx, x.data(), x.data(), 1, 6, 6, nullptr, nullptr, y.data(), nullptr));
+  load(SVG_UNET, "conv_out.bias", {4}, 0.02f);
+  REFUSED(svg_ddim_step(ctx, x.data(), x.data(), y.data(), 64, 980, 960, nullptr), ctx, SVG_ERR_INVALID, "unet: model not finalized");
+  REFUSED(svg_unet_forward(ctx, x.data(), 1, 4, 4, &f, x.data(), 1, y.data(), nullptr), ctx, SVG_ERR_INVALID, "unet: svg_finalize has not been called");
+  unet(0, 0);
+  // ids the library does not know
+  for (int id : {-1, 6, 7}) {
+    const std::string msg = "unknown model id " + std::to_string(id);
+    REFUSED(svg_model_configure(ctx, id, "f16=1"), ctx, SVG_ERR_INVALID, msg.c_str());
+    REFUSED(svg_load_weight(ctx, id, "w", &f, &one, 1), ctx, SVG_ERR_INVALID, msg.c_str());
+    REFUSED(svg_finalize(ctx, id, nullptr), ctx, SVG_ERR_INVALID, msg.c_str());
+    if (svg_model_dtype(ctx, id) != nullptr) { fprintf(stderr, "svg_model_dtype(%d) is not NULL\n", id); exit(7); }
+  }
+  // one refused call per file of entry points
+  REFUSED(svg_lms_step(ctx, nullptr, x.data(), x.data(), y.data(), 64, 10, 0, nullptr), ctx, SVG_ERR_INVALID, "svg_lms_step: null tensor or negative size");
+  REFUSED(svg_sample_loop(ctx, 9, x.data(), 1, 4, 4, x.data(), 1, 10, 0, 0.f, nullptr, nullptr, nullptr), ctx, SVG_ERR_INVALID, "svg_sample_loop: unknown sampler 9");
+  REFUSED(svg_resize_bilinear_f32(ctx, nullptr, 1, 4, 4, y.data(), 8, 8, nullptr), ctx, SVG_ERR_INVALID, "svg_resize_bilinear_f32: bad arguments");
+  REFUSED(svg_plan_end(ctx, nullptr), ctx, SVG_ERR_INVALID, "svg_plan_end without svg_plan_begin");
+  REFUSED(svg_transformer_forward(ctx, x.data(), x.data(), 65, 6, 6, nullptr, nullptr, y.data(), nullptr), ctx, SVG_ERR_INVALID, "");
+  REFUSED(svg_transformer_grad_norm(ctx, nullptr, nullptr), ctx, SVG_ERR_INVALID, "svg_transformer_grad_norm: null argument");
+  REFUSED(svg_op_xf_add_ln(ctx, nullptr, nullptr, x.data(), x.data(), y.data(), 1, 64, 1e-5f, nullptr), ctx, SVG_ERR_INVALID, "svg_op_xf_add_ln: null argument");
+  REFUSED(svg_op_time_mean(ctx, x.data(), y.data(), 0, 1, 1, nullptr), ctx, SVG_ERR_INVALID, "svg_op_time_mean: bad arguments");
+  REFUSED(svg_clip_text_forward(ctx, nullptr, 1, 78, y.data(), nullptr), ctx, SVG_ERR_INVALID, "clip:");
+  REFUSED(svg_minilm_encode(ctx, nullptr, nullptr, 1, 4, y.data(), nullptr, nullptr), ctx, SVG_ERR_INVALID, "minilm: null argument");
+  REFUSED(svg_op_gemm_plan(ctx, nullptr, path), ctx, SVG_ERR_INVALID, "gemm_plan: no descriptor / no result array");
+  REFUSED(svg_op_gemm_plan_f16(ctx, nullptr, path), ctx, SVG_ERR_INVALID, "gemm_plan: no descriptor / no result array");
+  // an exception that is not the library's own is a runtime failure: the number parser on a value that is no number
+  REFUSED(svg_model_configure(ctx, SVG_MINILM, "layers=two"), ctx, SVG_ERR_RUNTIME, "stoll");
+  // without a context the message goes to the process-wide slot
+  svg_ctx* none = nullptr;
+  REFUSED(svg_create(99, &none), nullptr, SVG_ERR_INVALID, "svg_create: device 99 of");
+  REFUSED(svg_model_configure(nullptr, SVG_VAE, ""), nullptr, SVG_ERR_INVALID, "null context");
+  REFUSED(svg_lms_coefs(0, 0, &dv, nullptr, nullptr, nullptr, nullptr), nullptr, SVG_ERR_INVALID, "");
+  REFUSED(svg_xf_gemm_describe(0, 1, 1, path), nullptr, SVG_ERR_INVALID, "svg_xf_gemm_describe: bad argument");
+}
+
 int main() {
   if (svg_create(0, &ctx) != 0) { fprintf(stderr, "svg_create: %s\n", svg_last_error(nullptr)); return 1; }
   EXPECT_ERR(svg_finalize(ctx, SVG_UNET, nullptr));                       // nothing loaded yet
@@ -319,6 +394,7 @@ int main() {
   unet(0, 0);
   OK(svg_prof_report(ctx, rep, sizeof(rep)));
   svg_prof_enable(ctx, 0);
+  abi_boundary();
   printf("workspace %lld bytes, %s, %s / %s\n", (long long)svg_workspace_bytes(ctx), svg_version(), svg_model_dtype(ctx, SVG_UNET), svg_model_dtype(ctx, SVG_VAE));
   svg_destroy(ctx);
   puts("host-sanitize: OK");

@@ -16,6 +16,11 @@
 #include <map>
 #include <string>
 
+// the model's lifecycle (latent_transformer.cpp, xf_trainer.cpp) is not linked and not called here: the plan reads the model's fields only
+void XfModel::configure(const char*) {}
+void XfModel::finalize(svg_ctx*, int64_t*) {}
+void XfModel::weights_changed(bool) {}
+
 // ---- made-up address space: named regions -----------------------------------------------------------------------------------------------
 struct Region { std::string name; uintptr_t lo, hi; };
 static std::vector<Region> g_regions;
