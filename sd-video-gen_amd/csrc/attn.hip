@@ -73,9 +73,7 @@ __global__ void __launch_bounds__(256) attn_kernel(const AttnArgs a) {
   // share one L2 instead of fetching K / V^T eight times (PMC: 1.25 GB fetched per launch against 0.22 GB of Q, K, V).
   int b, head, qt;
   {
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int q = nblk >> 3, rr = nblk & 7, xcd = bid & 7;
-    const int w = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+    const int w = xcd_tile(blockIdx.x, gridDim.x);
     const int nqt = (a.Sq + 128 * QB - 1) / (128 * QB);
     qt = w % nqt;
     const int bh = w / nqt;
@@ -400,9 +398,7 @@ __global__ void __launch_bounds__(256) attn_dma40_kernel(const AttnArgs a) {
   const int r = lane & 31, h = lane >> 5;
   int b, head, qt;
   {
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int q = nblk >> 3, rr = nblk & 7, xcd = bid & 7;
-    const int w = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+    const int w = xcd_tile(blockIdx.x, gridDim.x);
     const int nqt = (a.Sq + 255) / 256;
     qt = w % nqt;
     const int bh = w / nqt;
@@ -413,11 +409,9 @@ __global__ void __launch_bounds__(256) attn_dma40_kernel(const AttnArgs a) {
   const h16* __restrict__ Q = a.q + (int64_t)b * a.qb + head * D;
   const h16* __restrict__ Kp = a.k + (int64_t)b * a.kb + head * D;
   const h16* __restrict__ Vt = a.vt + (int64_t)b * a.vtb + (int64_t)head * D * a.ldvt;
-  const uint64_t pk = (uint64_t)Kp, pv = (uint64_t)Vt;
   const unsigned k_bytes = (unsigned)(((int64_t)a.Skv - 1) * a.ldk * 2 + D * 2);
   const unsigned v_bytes = (unsigned)(((int64_t)D - 1) * a.ldvt * 2 + ((a.Skv + 7) / 8 * 8) * 2);
-  const v4i srdK = {(int)(unsigned)pk, (int)((pk >> 32) & 0xffff), (int)k_bytes, 0x00020000};
-  const v4i srdV = {(int)(unsigned)pv, (int)((pv >> 32) & 0xffff), (int)v_bytes, 0x00020000};
+  const v4i srdK = buf_srd(Kp, k_bytes), srdV = buf_srd(Vt, v_bytes);
   constexpr unsigned OOB = 0x80000000u;
 
   // ---- this wave's three DMA instructions of a tile: indices wid, wid + 4, wid + 8 of (K0..K6, V0..V4) -------------------------

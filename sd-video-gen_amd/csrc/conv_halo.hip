@@ -22,10 +22,6 @@ constexpr int PW = 18;                 // patch width / height in pixels
 static_assert(PW == HALO_SIDE + 2, "the patch is the tile of output pixels the plan counts (gemm_tiles.h) plus its halo");
 constexpr int PPIX = PW * PW;          // 324
 constexpr int NPD = 6;                 // patch DMA instructions per wave: 8 waves * 64 lanes * 6 = 3072 >= 324 * 8 chunks
-// MFMA (0-based, of the 2 nm in a merged segment) behind which DMA slot o of the merged loop sits (the placement gemm_pp.hip measured best)
-__host__ __device__ constexpr int halo_slot_at(int o, int nm) {
-  return o == 0 ? nm / 2 - 1 : o == 1 ? nm + 1 : o == 2 ? nm + nm / 2 - 1 : o == 3 ? (3 * nm) / 4 : 2 * nm - 5;
-}
 
 // Ping-pong schedule: the 8 waves run as two groups of four (one wave of each group per SIMD) staggered by one barrier, so that while
 // one group multiplies (s_setprio 1) the other issues its fragment reads and DMAs — the matrix pipe always has a wave feeding it instead
@@ -59,12 +55,7 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
   const bool up2 = g.amode == A_CONV_UP2;
   const int OH = up2 ? g.Ho : g.H, OW = up2 ? g.Wo : g.W;
   const int bx_n = OW >> 4, by_n = OH >> 4;
-  int tile;
-  {
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int tile = xcd_tile(blockIdx.x, gridDim.x);
   int tn, pb;
   if (g.tn_major) {   // weight-heavy (small images): the XCD's run of tiles keeps one channel tile's weights in its L2
     const int npb = gridDim.x / tiles_n;
@@ -86,10 +77,7 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
 
   const unsigned a_bytes = (unsigned)((int64_t)(g.M / (OH * OW)) * g.H * g.W * g.Cin * 2);
   const unsigned b_bytes = (unsigned)(((int64_t)(g.n_valid - 1) * g.ldb + g.K) * 2);
-  // buffer descriptors: {base[31:0], base[47:32] (stride 0), num_records, flags}
-  const uint64_t pa = (uint64_t)g.A, pw = (uint64_t)g.Wt;
-  const v4i srdA = {(int)(unsigned)pa, (int)((pa >> 32) & 0xffff), (int)a_bytes, 0x00020000};
-  const v4i srdB = {(int)(unsigned)pw, (int)((pw >> 32) & 0xffff), (int)b_bytes, 0x00020000};
+  const v4i srdA = buf_srd(g.A, a_bytes), srdB = buf_srd(g.Wt, b_bytes);
   const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);   // LDS address of smem[0]
 
   // ---- patch DMA map: linear LDS image [pixel][8 chunks]; lane id -> (pp, position); the swizzle rides on the source chunk
@@ -105,12 +93,6 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
     const int sy = up2 ? yy >> 1 : yy, sx = up2 ? xx >> 1 : xx;
     return ok ? (unsigned)(((b * g.H + sy) * g.W + sx) * g.Cin + c * 8) * 2u : INVALID;
   };
-  // The removed lock-step loop kept the six offsets here.  Zero-filled, never read and eliminated by the compiler — yet without it (and
-  // likewise without the dead HALO_NOPAD bodies below) the prologue of the BN = 160 kernels is scheduled in another order, so both stay
-  // until that change is measured: profiles/r16_retired_variants.md.
-  unsigned p_voff[NPD];
-#pragma unroll
-  for (int i = 0; i < NPD; ++i) p_voff[i] = 0u;
   // ---- weight DMA map (as gemm.hip): rows r0 + 64 i, chunk swizzled on the source
   const int r0 = tid >> 3;                                // 0..63
   const int cB = (tid & 7) ^ (r0 & 7);
@@ -135,6 +117,9 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
     if (r0 < 32 && n < g.n_valid) b_voff_tail = (unsigned)(n * g.ldb + cB * 8) * 2u;
   }
 
+  // Padding DMAs (the 6th patch piece on waves 1-7, the slab's 32-row tail on waves 4-7, out-of-range source, into the sink) give every
+  // wave the same number of DMAs per slab and patch piece: the counted vmcnt of the main loop relies on it.  The form without them (each
+  // wave counting its own issues) was bit-identical and 3-5 % slower on every BN = 160 shape: profiles/r05_halo_nopad_ab.txt.
   constexpr int OFF_B = 2 * PBUF, OFF_DUMMY = OFF_B + NWS * B_BYTES;
   auto dma_patch_piece = [&](int cc, int buf, int i) {      // one of the NPD pieces (i is a compile-time constant after unrolling)
     const unsigned dst = lds0 + buf * PBUF + wave_u * 1024;
@@ -152,8 +137,7 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
 #pragma unroll
     for (int i = 0; i < BIT; ++i) dma16(srdB, b_voff[i], soff, dst + i * 8192);
     if (B_TAIL) {
-      // rows BIT*64 .. BIT*64+31 ride on waves 0-3 (r0 < 32); waves 4-7 issue a padding DMA into the sink so that
-      // every wave has the same number of DMAs per slab (the counted vmcnt below relies on it)
+      // rows BIT*64 .. BIT*64+31 ride on waves 0-3 (r0 < 32); waves 4-7 issue the padding DMA
       const unsigned tdst = (wave_u < 4) ? (dst + BIT * 8192) : (lds0 + OFF_DUMMY + wave_u * 1024);
       dma16(srdB, b_voff_tail, soff, tdst);
     }
@@ -177,34 +161,6 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
   //         s + 1 and the previous patch piece have landed; lgkmcnt(0).
   if (cc_begin < cc_end) {
     const int grp = wave_u >> 2;
-    // HALO_NOPAD = 1: no padding DMAs (round 5, VERDICT r04 #5: the scheme of conv_halo_fp8.hip).  The counted vmcnt of a load segment only
-    // has to leave THIS wave's just-issued DMAs in flight — a wave's counter sees its own operations, in order — so the waves need not
-    // issue equal numbers: at BN = 160 the slab's last 32 rows are DMA'd by waves 0-3 alone, the 6th patch piece (32 slots) by wave 0
-    // alone, instead of every other wave issuing those instructions with an out-of-range source into the sink region (10 of the 33 DMAs of
-    // a 64-channel chunk in waves 4-7).  Built, bit-identical, and SLOWER on every BN = 160 shape of the UNet (same box, 28 clips,
-    // profiles/r05_halo_nopad_ab.txt): 64^2 x 320 -> 320 0.187 -> 0.193 ms, 32^2 x 1920 -> 640 0.459 -> 0.478, 16^2 x 2560 -> 1280
-    // 0.295 -> 0.311 (-3 ... -5 %); BN = 128 shapes unchanged.  A reading, not a measurement: with unequal DMA counts the two wave
-    // groups' load segments differ in length; the second group's shorter segment cannot shorten the step (the barrier waits for the
-    // first group's), it only shifts its MFMAs against the first group's.  The padding DMAs stay (HALO_NOPAD 0).
-#ifndef HALO_NOPAD
-#define HALO_NOPAD 0
-#endif
-    const bool tail_w = B_TAIL && wave_u < 4;              // this wave carries a piece of the slab's 32-row tail
-    auto dma_w_own = [&](int cc, int tap, int stage) {
-      if (!HALO_NOPAD) { dma_weights(cc, tap, stage); return; }
-      const unsigned dst = lds0 + OFF_B + stage * B_BYTES + wave_u * 1024;
-      const int soff = (tap * g.Cin + cc * 64) * 2;
-#pragma unroll
-      for (int i = 0; i < BIT; ++i) dma16(srdB, b_voff[i], soff, dst + i * 8192);
-      if (tail_w) dma16(srdB, b_voff_tail, soff, dst + BIT * 8192);
-    };
-    auto dma_p_own = [&](int cc, int buf, int i) {          // patch piece i; the last piece exists on wave 0 only
-      if (!HALO_NOPAD) { dma_patch_piece(cc, buf, i); return; }
-      const unsigned dst = lds0 + buf * PBUF + wave_u * 1024;
-      const unsigned voff = patch_voff(i);
-      if (i < NPD - 1) dma16(srdA, voff, cc * 128, dst + i * 8192);
-      else if (wave_u == 0 && lane < 32) dma16(srdA, voff, cc * 128, dst + (NPD - 1) * 8192);
-    };
     auto dma_w_one = [&](int cc, int tap, int stage, int i) {   // instruction i (compile-time after unrolling) of the slab's NW
       const unsigned dst = lds0 + OFF_B + stage * B_BYTES + wave_u * 1024;
       const int soff = (tap * g.Cin + cc * 64) * 2;
@@ -212,14 +168,11 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
       else dma16(srdB, b_voff_tail, soff, (wave_u < 4) ? (dst + BIT * 8192) : (lds0 + OFF_DUMMY + wave_u * 1024));
     };
     const int km_cfg = min(__builtin_amdgcn_readfirstlane(g.pp_dma_m), NW + 1);
-    // DMAs this wave issues for a slab / for patch piece i
-    const int nw_own = HALO_NOPAD ? BIT + (tail_w ? 1 : 0) : NW;
-    auto np_own = [&](int i) { return (!HALO_NOPAD || i < NPD - 1 || wave_u == 0) ? 1 : 0; };
 #pragma unroll
-    for (int i = 0; i < NPD; ++i) dma_p_own(cc_begin, 0, i);
-    dma_w_own(cc_begin, 0, 0);
-    dma_w_own(cc_begin, 1, 1);
-    wait_vm(nw_own);                                      // patch and slab 0 have landed; slab 1 may be in flight
+    for (int i = 0; i < NPD; ++i) dma_patch_piece(cc_begin, 0, i);
+    dma_weights(cc_begin, 0, 0);
+    dma_weights(cc_begin, 1, 1);
+    wait_vm(NW);                                          // patch and slab 0 have landed; slab 1 may be in flight
 
     bar();
     if (grp == 1) bar();
@@ -268,19 +221,13 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
         // ahead of the next load segment's issues, whose counted wait therefore covers them: the RAW / WAR argument above is unchanged.
         const int kw = more_w ? (km_cfg < NW ? km_cfg : NW) : 0;          // weight instructions moved
         const bool p_in_m = pp && km_cfg > NW;                             // the patch piece moved
-        if (HALO_NOPAD) {
-          if (more_w) dma_w_own(wcc, wtap, (tap + 2) % NWS);
-          if (pp) dma_p_own(cc + 1, pbuf ^ 1, tap);
-          wait_vm((more_w ? nw_own : 0) + (pp ? np_own(tap) : 0));
-        } else {
-          if (more_w) {
+        if (more_w) {
 #pragma unroll
-            for (int i = 0; i < NW; ++i)
-              if (i < NW - kw) dma_w_one(wcc, wtap, (tap + 2) % NWS, i);
-          }
-          if (pp && !p_in_m) dma_p_own(cc + 1, pbuf ^ 1, tap);
-          wait_vm((more_w ? NW - kw : 0) + ((pp && !p_in_m) ? 1 : 0));
+          for (int i = 0; i < NW; ++i)
+            if (i < NW - kw) dma_w_one(wcc, wtap, (tap + 2) % NWS, i);
         }
+        if (pp && !p_in_m) dma_patch_piece(cc + 1, pbuf ^ 1, tap);
+        wait_vm((more_w ? NW - kw : 0) + ((pp && !p_in_m) ? 1 : 0));
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         bar();
         __builtin_amdgcn_sched_barrier(0);
@@ -293,16 +240,14 @@ __global__ void __launch_bounds__(512, 2) conv_halo_kernel(const GemmArgs g) {
             for (int j = 0; j < NT; ++j) {
               acc[i][j] = hh == 0 ? MFMA_16x16x32(w0[j], x0[i], acc[i][j]) : MFMA_16x16x32(w1[j], x1[i], acc[i][j]);
               const int idx = (hh * MT + i) * NT + j;
-              if (!HALO_NOPAD) {
 #pragma unroll
-                for (int o = 0; o <= NW; ++o)
-                  if (idx == halo_slot_at(o, MT * NT)) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (o < NW) { if (kw > o) dma_w_one(wcc, wtap, (tap + 2) % NWS, NW - 1 - o); }
-                    else if (p_in_m) dma_p_own(cc + 1, pbuf ^ 1, tap);
-                    __builtin_amdgcn_sched_barrier(0);
-                  }
-              }
+              for (int o = 0; o <= NW; ++o)
+                if (idx == dma_slot_at(o, MT * NT)) {
+                  __builtin_amdgcn_sched_barrier(0);
+                  if (o < NW) { if (kw > o) dma_w_one(wcc, wtap, (tap + 2) % NWS, NW - 1 - o); }
+                  else if (p_in_m) dma_patch_piece(cc + 1, pbuf ^ 1, tap);
+                  __builtin_amdgcn_sched_barrier(0);
+                }
             }
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);

@@ -84,12 +84,7 @@ __global__ void __launch_bounds__(512, 2) conv_halo_fp8_kernel(const Fp8ConvArgs
   const bool up2 = g.amode == A_CONV_UP2;
   const int OH = up2 ? g.Ho : g.H, OW = up2 ? g.Wo : g.W;
   const int bx_n = OW >> 4, by_n = OH >> 4;
-  int tile;
-  {
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int tile = xcd_tile(blockIdx.x, gridDim.x);
   int tn, pb;
   if (g.tn_major) {
     const int npb = gridDim.x / tiles_n;
@@ -109,11 +104,7 @@ __global__ void __launch_bounds__(512, 2) conv_halo_fp8_kernel(const Fp8ConvArgs
   const unsigned as_bytes = (unsigned)((int64_t)nimg * g.H * g.W * SB);
   const unsigned w_bytes = (unsigned)((int64_t)a.Npad * 9 * Cp);
   const unsigned ws_bytes = (unsigned)((int64_t)9 * CC * a.Npad * 4);
-  auto mk = [](const void* p, unsigned bytes) -> v4i {
-    const uint64_t u = (uint64_t)p;
-    return v4i{(int)(unsigned)u, (int)((u >> 32) & 0xffff), (int)bytes, 0x00020000};
-  };
-  const v4i srdA = mk(a.A8, a_bytes), srdAs = mk(a.As, as_bytes), srdB = mk(a.W8, w_bytes), srdBs = mk(a.Ws, ws_bytes);
+  const v4i srdA = buf_srd(a.A8, a_bytes), srdAs = buf_srd(a.As, as_bytes), srdB = buf_srd(a.W8, w_bytes), srdBs = buf_srd(a.Ws, ws_bytes);
   const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
 
   // A load segment waits for everything but the BIT weight DMAs it has just issued (the same count in every wave), so the DMAs issued

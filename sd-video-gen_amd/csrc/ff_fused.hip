@@ -73,9 +73,7 @@ __global__ void __launch_bounds__(512, 2) ff_pair_kernel(const FfArgs a, unsigne
   const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
   constexpr unsigned INVALID = 0x80000000u;
 
-  const uint64_t p1 = (uint64_t)a.W1, p2 = (uint64_t)a.W2p;
-  const v4i srd1 = {(int)(unsigned)p1, (int)((p1 >> 32) & 0xffff), (int)(2u * FH * FC * 2u), 0x00020000};
-  const v4i srd2 = {(int)(unsigned)p2, (int)((p2 >> 32) & 0xffff), (int)((unsigned)FC * FH * 2u), 0x00020000};
+  const v4i srd1 = buf_srd(a.W1, 2u * FH * FC * 2u), srd2 = buf_srd(a.W2p, (unsigned)FC * FH * 2u);
 
   const int prow = lane >> 3;
   auto dma_slab = [&](int q, int slot) {                   // slab q = (chunk q / 8, piece q % 8) into ring slot `slot`

@@ -47,12 +47,7 @@ __global__ void __launch_bounds__(256, 2) igemm_kernel(const GemmArgs g) {
   // XCD-aware tile order: blocks that share an XCD (bid % 8) get a contiguous run of tiles,
   // consecutive tiles share the A row panel (same tm) so its re-reads hit that XCD's L2.
   const int tiles_n = (g.N + BN - 1) / BN;
-  int tile;
-  {
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int tile = xcd_tile(blockIdx.x, gridDim.x);
   int tm, tn;
   if (g.tn_major) {   // weight-heavy problem: the XCD's run of tiles walks the rows for a fixed column tile
     const int tiles_m = (g.M + BM - 1) / BM;

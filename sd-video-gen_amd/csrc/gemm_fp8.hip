@@ -40,12 +40,7 @@ __global__ void __launch_bounds__(256, 2) gemm_fp8_kernel(const Fp8Args a) {
   const int l15 = lane & 15, lq = lane >> 4;
 
   const int tiles_n = (g.N + BN - 1) / BN;
-  int tile;
-  {
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int tile = xcd_tile(blockIdx.x, gridDim.x);
   const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
   const int KT = g.K >> 7;                                  // K % 128 == 0

@@ -10,8 +10,6 @@
 //   waves 4 (M) x 2 (N); wave tile 64 x BN/2; v_mfma_f32_16x16x32_bf16 with the W fragment as the A operand.
 //   LDS rows are 128 B, chunk c of row r at c ^ (r & 7) (swizzle applied on the DMA source side).
 #include "igemm_epi.h"
-#include <algorithm>
-#include <cstdlib>
 #include <vector>
 
 namespace SDNS {
@@ -26,12 +24,6 @@ namespace {
 #else
 #define PSTAMP(v) do { } while (0)
 #endif
-
-// MFMA (0-based, of the 2 nm in a merged segment) behind which DMA slot o sits: the first three at the middle of the first k half, the
-// second MFMA and the middle of the second k half (the placement measured best), the next three between them
-__host__ __device__ constexpr int pp_slot_at(int o, int nm) {
-  return o == 0 ? nm / 2 - 1 : o == 1 ? nm + 1 : o == 2 ? nm + nm / 2 - 1 : o == 3 ? (3 * nm) / 4 : o == 4 ? 2 * nm - 5 : o == 5 ? 3 : nm + nm / 4;
-}
 
 // WIDE: the wide tile epilogue (igemm_epi.h; 16-bit output without GEGLU — the launcher decides)
 template <int BN, bool WIDE>
@@ -57,12 +49,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const GemmArgs g) {
   const int l15 = lane & 15, lq = lane >> 4;
 
   const int tiles_n = (g.N + BN - 1) / BN;
-  int tile;
-  {
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int tile = xcd_tile(blockIdx.x, gridDim.x);
   // Tile order inside an XCD's contiguous run: groups of g.group_m row tiles, the column tile walking slowest inside a group
   // and the row tile fastest, so the ~32 workgroups an XCD runs at a time cover a compact group_m x (32 / group_m) rectangle
   // whose A and W panels fit its 4 MiB L2 (row-major order at N = 10240 keeps 33 panels live per XCD: 780 MB per launch
@@ -82,9 +69,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const GemmArgs g) {
 
   const unsigned a_bytes = (unsigned)(((int64_t)(g.M - 1) * g.lda + g.K) * 2);
   const unsigned b_bytes = (unsigned)(((int64_t)(g.n_valid - 1) * g.ldb + g.K) * 2);
-  const uint64_t pa = (uint64_t)g.A, pw = (uint64_t)g.Wt;
-  const v4i srdA = {(int)(unsigned)pa, (int)((pa >> 32) & 0xffff), (int)a_bytes, 0x00020000};
-  const v4i srdB = {(int)(unsigned)pw, (int)((pw >> 32) & 0xffff), (int)b_bytes, 0x00020000};
+  const v4i srdA = buf_srd(g.A, a_bytes), srdB = buf_srd(g.Wt, b_bytes);
   const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
 
   // DMA maps: a wave instruction fills 8 LDS rows (64 lanes x 16 B); lane (r0, p) fetches logical chunk p ^ (r0 & 7).
@@ -152,6 +137,9 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const GemmArgs g) {
   // ---- main loop: same phase structure, RAW / WAR argument and vmcnt accounting as conv_halo.hip's ping-pong loop:
   // step s (slab s, stage s % 3) = phase 0 [reads of its second k half; first NA DMAs of slab s+2; wait until only those
   // are in flight -> slab s+1 landed] + phase 1 [reads of the first k half of slab s+1; the other DMAs of slab s+2].
+  // Every launch runs the merged form (the launcher sets pp_merge = 1; the two-phase loop was measured slower in round 6).  The two-phase
+  // branch stays compiled: with it deleted the compiler schedules <128, false> (the GEGLU projections) 1.5 % slower at 7168 x 10240 x 1280
+  // in ten of ten repeats — profiles/r30_pp_halo_one_loop.md.
   if (g.pp_merge) {
     // merged form (as conv_halo.hip's MODE 2): a slab is ONE phase of 2 * MT * NT MFMAs between two barriers; its fragments are read in
     // its own load segment (one register set), whose latency runs beside the other group's MFMA segment.
@@ -195,7 +183,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const GemmArgs g) {
       PSTAMP(p3);
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_setprio(1);
-      // slot o (compile-time position pp_slot_at(o)) carries DMA instruction NW - 1 - o when km > o.  (A run-time slot mask with a
+      // slot o (compile-time position dma_slot_at(o)) carries DMA instruction NW - 1 - o when km > o.  (A run-time slot mask with a
       // run-time instruction index was measured too: its address arithmetic and ten scalar slot tests per segment cost more than the
       // move gains — profiles/r06_pp_dma_in_mfma.txt.)
 #pragma unroll
@@ -208,7 +196,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const GemmArgs g) {
             const int idx = (h * MT + i) * NT + j;
 #pragma unroll
             for (int o = 0; o < 7; ++o)
-              if (idx == pp_slot_at(o, MT * NT) && o < NW) {
+              if (idx == dma_slot_at(o, MT * NT) && o < NW) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (km > o) dma_part(s + 2, st2, NW - 1 - o, NW - o);
                 __builtin_amdgcn_sched_barrier(0);
@@ -274,27 +262,32 @@ template <int BN>
 void launch_pp(const GemmArgs& g, hipStream_t s) {
   constexpr int smem = 3 * (256 * 128 + BN * 128) + 1024;
   const int tiles = cdiv(g.M, 256) * cdiv(g.N, BN);
-  if (g.act == ACT_GEGLU || g.out_f32) hipLaunchKernelGGL((gemm_pp_kernel<BN, false>), dim3(tiles), dim3(512), smem, s, g);
-  else hipLaunchKernelGGL((gemm_pp_kernel<BN, true>), dim3(tiles), dim3(512), smem, s, g);
+  if (g.act == ACT_GEGLU || g.out_f32) {
+    // the plan gives GEGLU the 128-column tile and refuses f32 output (gemm_plan.cpp: gemm_pp_supported): <160, false> is not instantiated
+    if constexpr (BN == 128) hipLaunchKernelGGL((gemm_pp_kernel<BN, false>), dim3(tiles), dim3(512), smem, s, g);
+    else SVG_CHECK(false, "gemm_pp: no %d-column kernel for GEGLU / f32 output (act %d, out_f32 %d)", BN, g.act, g.out_f32);
+  } else {
+    hipLaunchKernelGGL((gemm_pp_kernel<BN, true>), dim3(tiles), dim3(512), smem, s, g);
+  }
 }
+
+constexpr int PP_GROUP_M = 4;          // row tiles per group of the grouped tile order (the kernel reads GemmArgs::group_m at run time)
+constexpr int PP_DMA_M = 6;            // DMA instructions of a slab issued among its MFMAs (the kernel reads GemmArgs::pp_dma_m at run time)
 
 }  // namespace
 
 void gemm_pp_init_device() {
   HIP_OK(hipFuncSetAttribute((const void*)gemm_pp_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (256 * 128 + 128 * 128) + 1024));
   HIP_OK(hipFuncSetAttribute((const void*)gemm_pp_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (256 * 128 + 128 * 128) + 1024));
-  HIP_OK(hipFuncSetAttribute((const void*)gemm_pp_kernel<160, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (256 * 128 + 160 * 128) + 1024));
   HIP_OK(hipFuncSetAttribute((const void*)gemm_pp_kernel<160, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (256 * 128 + 160 * 128) + 1024));
 }
 
 // bn: the column-tile width of the plan (gemm_plan.cpp), 128 or 160
 void launch_gemm_pp(const GemmArgs& g0, int bn, hipStream_t s) {
-  const int gm_env = (int)svg_env_i64("SVG_PP_GROUPM", 4);
   GemmArgs g = g0;
-  g.group_m = gm_env;
-  g.pp_merge = (int)svg_env_i64("SVG_PP_MERGE", 1);        // 0 = the two-phase loop
-  // DMA instructions of a slab that ride among the MFMAs (see the merged loop)
-  g.pp_dma_m = std::max(0, std::min(7, (int)svg_env_i64("SVG_PP_DMA_M", 6)));
+  g.group_m = PP_GROUP_M;
+  g.pp_dma_m = PP_DMA_M;
+  g.pp_merge = 1;                        // the merged loop (see the kernel's main loop for why the other branch is still there)
 #ifdef PP_STAMP
   const int tiles_dbg = cdiv(g.M, 256) * cdiv(g.N, bn);
   unsigned long long* dbg = nullptr;

@@ -66,8 +66,7 @@ __global__ void __launch_bounds__(512, 2) gemm_ws_kernel(const GemmArgs g, int n
   // W[n0 + 16 j + r][32 ks + 8 q .. +7] into bytes [16 lane, +16) of the piece
   {
     const unsigned w_bytes = (unsigned)(((int64_t)(g.n_valid - 1) * g.ldb + g.K) * 2);
-    const uint64_t pw = (uint64_t)g.Wt;
-    const v4i srdW = {(int)(unsigned)pw, (int)((pw >> 32) & 0xffff), (int)w_bytes, 0x00020000};
+    const v4i srdW = buf_srd(g.Wt, w_bytes);
     const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
     for (int p = wid; p < WS_PIECES; p += 8) {
       const int j = p / KS, ks = p - j * KS;

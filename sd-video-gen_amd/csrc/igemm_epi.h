@@ -504,6 +504,26 @@ __device__ __forceinline__ void epi_tile(const GemmArgs& g, int z, int mr, int m
 // ---- helpers of the LDS-DMA pipelines (conv_halo.hip, gemm_pp.hip) ----------------------------------------------
 typedef int v4i __attribute__((ext_vector_type(4)));
 
+// raw buffer descriptor of `bytes` bytes at p: {base[31:0], base[47:32] (stride 0), num_records, flags}; offsets past num_records read as zeros
+__device__ __forceinline__ v4i buf_srd(const void* p, unsigned bytes) {
+  const uint64_t u = (uint64_t)p;
+  return v4i{(int)(unsigned)u, (int)((u >> 32) & 0xffff), (int)bytes, 0x00020000};
+}
+
+// XCD tile remap: workgroups are dealt to the 8 XCDs round robin (bid & 7); this gives workgroup bid of nblk the tile index that makes every
+// XCD's workgroups a contiguous run of tiles (the first nblk & 7 runs one longer), so neighbouring tiles share operands in one L2
+__device__ __forceinline__ int xcd_tile(int bid, int nblk) {
+  const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
+// merged ping-pong loops (gemm_pp.hip, conv_halo.hip): MFMA (0-based, of the 2 nm in a merged segment) behind which DMA slot o sits: the
+// first three at the middle of the first k half, the second MFMA and the middle of the second k half (the placement measured best), the
+// next three between them
+__host__ __device__ constexpr int dma_slot_at(int o, int nm) {
+  return o == 0 ? nm / 2 - 1 : o == 1 ? nm + 1 : o == 2 ? nm + nm / 2 - 1 : o == 3 ? (3 * nm) / 4 : o == 4 ? 2 * nm - 5 : o == 5 ? 3 : nm + nm / 4;
+}
+
 // LDS-direct 16-byte buffer load issued from inline asm: hipcc's waitcnt pass does not see it, so it cannot add its own
 // conservative vmcnt(0) in front of the fragment reads (it does for the builtin form here: the stage index is dynamic) —
 // every wait for these DMAs is one of the explicit counted s_waitcnt below.  M0 (LDS base of the wave's 1-KiB piece) is

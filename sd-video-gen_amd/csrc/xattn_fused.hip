@@ -63,13 +63,15 @@ __global__ void __launch_bounds__(512, 2) xattn_fused_kernel(const XaArgs a) {
   const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
   constexpr unsigned INVALID = 0x80000000u;
 
-  const uint64_t pq = (uint64_t)a.Wq, po = (uint64_t)a.Wo, pp = (uint64_t)a.Wp;
-  const v4i srdp = {(int)(unsigned)pp, (int)((pp >> 32) & 0xffff), (int)((unsigned)XC * XC * 2u), 0x00020000};
-  const uint64_t pk = (uint64_t)(a.Kp + (int64_t)sample * XH * X_HEAD_ELEMS), pv = (uint64_t)(a.Vp + (int64_t)sample * XH * X_HEAD_ELEMS);
-  const v4i srdq = {(int)(unsigned)pq, (int)((pq >> 32) & 0xffff), (int)((unsigned)XQ * XC * 2u), 0x00020000};
-  const v4i srdo = {(int)(unsigned)po, (int)((po >> 32) & 0xffff), (int)((unsigned)XC * XQ * 2u), 0x00020000};
-  const v4i srdk = {(int)(unsigned)pk, (int)((pk >> 32) & 0xffff), (int)((unsigned)XH * X_HEAD_ELEMS * 2u), 0x00020000};
-  const v4i srdv = {(int)(unsigned)pv, (int)((pv >> 32) & 0xffff), (int)((unsigned)XH * X_HEAD_ELEMS * 2u), 0x00020000};
+  // (statement order as measured: with the K / V bases formed behind the other descriptors the <true> kernel's schedule moves an s_add —
+  // profiles/r30_pp_halo_one_loop.md)
+  const v4i srdp = buf_srd(a.Wp, (unsigned)XC * XC * 2u);
+  const auto* pk = a.Kp + (int64_t)sample * XH * X_HEAD_ELEMS;
+  const auto* pv = a.Vp + (int64_t)sample * XH * X_HEAD_ELEMS;
+  const v4i srdq = buf_srd(a.Wq, (unsigned)XQ * XC * 2u);
+  const v4i srdo = buf_srd(a.Wo, (unsigned)XC * XQ * 2u);
+  const v4i srdk = buf_srd(pk, (unsigned)XH * X_HEAD_ELEMS * 2u);
+  const v4i srdv = buf_srd(pv, (unsigned)XH * X_HEAD_ELEMS * 2u);
 
   // ring slab q: [0, 15) Wq k-slab q / 3, row block q % 3; [15, 31) head (q - 15) / 2: K_h then V_h^T; [31, 49) W_out k-slab, row block
   const int prow = lane >> 3;

@@ -516,6 +516,10 @@ CASES = (
         ("pp-int-biasbn-lnswap", (PP, 128, 1), dict(M=16421, N=640, K=1280, bias_bn=(1024, 16), ln="swapped", n_valid=620, alpha=0.5)),
         ("pp-rand-silu", (PP, 128, 1), dict(M=16421, N=640, K=1280, data="rand", bias="col", res_pad=8, act=ACT_SILU)),
         ("pp-rand-gelu-ln", (PP, 128, 1), dict(M=16421, N=640, K=1280, data="rand", alpha=0.7, bias="col", ln="normal", act=ACT_GELU)),
+        # gemm_pp at 160 columns: 26 row tiles (the last one 37 rows) x 8 column tiles in one round, 16 slabs — the shortest K it takes
+        ("pp160-int-colbias-res-ln", (PP, 160, 1), dict(M=6437, N=1280, K=1024, ldc_pad=8, n_valid=1276, alpha=2.0, bias="col", res_pad=8,
+                                                        ln="normal")),
+        ("pp160-rand-silu", (PP, 160, 1), dict(M=6437, N=1280, K=1024, data="rand", bias="col", res_pad=8, act=ACT_SILU)),
         # gemm_ws: K = 320, >= 16384 rows, whole 160-column groups
         ("ws-int-colbias-res-ln", (WS, 160, 1), dict(M=16421, N=320, K=320, ldc_pad=8, alpha=2.0, bias="col", res_pad=8, ln="normal")),
         ("ws-int-960", (WS, 160, 1), dict(M=16384, N=960, K=320, lda_pad=8, ldc_pad=16, alpha=0.5, bias="col", res_pad=0)),
@@ -547,6 +551,15 @@ for _mode, _H in (("S1", 32), ("UP2", 16)):
             (_pre + "-rand-gelu", (HALO, 128, _sk), dict(M=_M, N=320, K=_K, conv=_cv, halo_min=True, data="rand", bias="col", res_pad=0,
                                                          act=ACT_GELU)),
         ]
+# conv_halo at 160 columns: 13 x 4 pixel blocks x 4 channel tiles = 208 workgroups (no split-K), two 64-channel chunks — the second patch
+# buffer, the next chunk's patch pieces among the taps and the chunk boundary of the weight slabs all run
+_cv = (13, 32, 32, 128, "S1")
+CASES += [
+    ("halo160-int-biasbn-res", (HALO, 160, 1), dict(M=13312, N=640, K=1152, conv=_cv, halo_min=True, n_valid=632, bias="col",
+                                                    bias_bn=(1024, 8), res_pad=8)),
+    ("halo160-rand-gelu", (HALO, 160, 1), dict(M=13312, N=640, K=1152, conv=_cv, halo_min=True, data="rand", bias="col", res_pad=0,
+                                               act=ACT_GELU)),
+]
 
 
 @pytest.mark.parametrize("path,kw", [pytest.param(p, kw, id=i) for i, p, kw in CASES])
